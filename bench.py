@@ -3,7 +3,7 @@
 proposal points filtered per second through MLFriends.inside + region-rebuild ms, N=4000 live
 points, d=50.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -22,6 +22,11 @@ AffineLayer, 30 bootstrap rounds, proposal set "E" = uniform draws inside the wr
 ellipsoid (every proposal passes the ellipsoid test and reaches the neighbour scan).
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+Everything else it can measure -- the comparison with the exact FP64 scan, the per-launch and per-stage passes and the roofline
+built from them, the strong-scaling leg (unless it is the headline), the rebuild timings, the host-API path and the CPU baseline --
+runs with --full.  --dump-outputs DIR writes the mask the timed path returned in its last step (rank 0) as DIR/inside_mask.npy.
 """
 import argparse
 import json
@@ -50,6 +55,23 @@ PREP_MFMA_PER_GROUP = 42         # v_mfma_f32_32x32x16_f16 of the per-proposal s
 PREP_MFMA_PER_GROUP_SAME_FORM = 24   # ... where the ellipsoid's matrix is T T^T of the layer (AffineLayer, one cluster -- this workload):
 # k_prep_sweep<.., SQ> reads the ellipsoid form off the whitening chain, the L^T chain is not executed (debug_stats: same_quadratic_form)
 SET_BYTES_PER_SLOT = lambda ks: ks * 32 + 16   # noqa: E731 -- a compacted proposal: K = 16 ks binary16 columns + T_lo, T_hi, index, minimum
+METRIC = "proposal-points filtered/sec (MLFriends.inside) + region-rebuild ms, N=4000 d=50"
+
+
+def workload_config(world):
+    """The `config` object of the line as far as a plain run knows it (--full adds what its own passes establish)."""
+    return {"workload": "C5: N=4000 live points, d=50, P=1e6 proposals/step/GPU drawn uniformly inside the "
+                        "wrapping ellipsoid (set E), AffineLayer, 30 bootstraps; one step = MLFriends.inside "
+                        "on a batch resident in HBM; the timed loop visits %d distinct batches in turn" % NBATCHES,
+            "n_live": N_LIVE, "d": NDIM, "proposals_per_step_per_gpu": NPROPOSALS, "bootstraps": NBOOT,
+            "distinct_batches_in_the_timed_loop": NBATCHES,
+            "parallelism": "proposal rows sharded over " + str(world) + " GPU(s), region replicated"}
+
+
+def dump_outputs(path, mask):
+    """--dump-outputs: the uint8 mask one timed step returned (1 = inside the region), as float32 (4 MB at P = 10^6)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "inside_mask.npy"), mask.cpu().numpy().astype(np.float32))
 
 
 def build_region(group):
@@ -423,15 +445,22 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--cpu-sample", type=int, default=150000, help="proposals timed on the CPU oracle (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: exact-scan comparison, per-launch / per-stage passes and the "
+                         "roofline, strong-scaling leg, rebuild timings, host API, CPU baseline (off: the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the mask the timed path returned in its last step (rank 0) as DIR/inside_mask.npy, float32")
+    ap.add_argument("--cpu-sample", type=int, default=150000, help="proposals timed on the CPU oracle (rank 0, N=1; --full)")
+    ap.add_argument("--no-cpu", action="store_true", help="no CPU baseline (--full)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="which leg is the headline `value`: weak = P proposals per rank and step (default), strong = ONE "
-                         "batch of P proposals per step sharded over the ranks; the other leg is reported beside it")
+                         "batch of P proposals per step sharded over the ranks; the other leg is reported beside it (the strong one with --full)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline path (no single-sweep / filter-off / host-API comparison passes): used for "
-                         "the rocprofv3 runs, so that the per-kernel averages of the summary are those of the timed steps")
+                    help="with --full: only the headline path (no single-sweep / filter-off / host-API comparison passes): used "
+                         "for the rocprofv3 runs, so that the per-kernel averages of the summary are those of the timed steps")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -516,11 +545,102 @@ def main():
         handle.inside_dev(pts.data_ptr(), NPROPOSALS, mask.data_ptr(), stream)
         torch.cuda.synchronize()
 
+    from ultranest_amd import distributed
+
+    def maxed(x):
+        if not use_dist:
+            return float(x)
+        import torch.distributed as dist
+        t = torch.tensor([x], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return float(t.item())
+
+    def strong_leg():
+        """Strong scaling: ONE batch of P proposals per step, rows sharded over the ranks (distributed.shard_bounds; no
+        collective in the data path, integrator.py:1916-1928 gathers only accepted rows), and the 30-round bootstrap of
+        the rebuild sharded over the ranks INCLUDING its all-reduce (integrator.py:375-415).  Returns the `strong_scaling`
+        object, this rank's seconds of the timed loop and of one sharded bootstrap, and the mask of its last step."""
+        lo, hi = distributed.shard_bounds(NPROPOSALS, rank, world)
+        ranks_agree = None
+        if world > 1:
+            full = proposals_in_ellipsoid(region, NPROPOSALS, 1000, dev)     # the SAME batch on every rank; each takes its rows
+            shard = full[lo:hi].contiguous()
+            # every rank also filters the SAME first 65536 rows of that batch: a digest of the mask must be the same number on
+            # every rank (MIN == MAX over the ranks) -- a rank whose region, library or device disagrees fails the run loudly
+            nshared = 65536
+            shared_mask = torch.empty(nshared, dtype=torch.uint8, device=dev)
+            handle.inside_dev(full.data_ptr(), nshared, shared_mask.data_ptr(), stream)
+            torch.cuda.synchronize()
+            digest = int((shared_mask.long() * (torch.arange(nshared, device=dev, dtype=torch.int64) % 1000003 + 1)).sum().item())
+            import torch.distributed as dist
+            dg = torch.tensor([digest, -digest], dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(dg, op=dist.ReduceOp.MAX)
+            ranks_agree = bool(int(dg[0].item()) == -int(dg[1].item()))
+            assert ranks_agree, "rank %d: the ranks' masks on the shared rows differ (digest %d, max %d, min %d)" % (
+                rank, digest, int(dg[0].item()), -int(dg[1].item()))
+            del full, shared_mask
+        else:
+            shard = pts
+        smask = torch.empty(hi - lo, dtype=torch.uint8, device=dev)
+        for _ in range(CLOCK_SETTLE_STEPS + args.warmup):
+            handle.inside_dev(shard.data_ptr(), hi - lo, smask.data_ptr(), stream)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            handle.inside_dev(shard.data_ptr(), hi - lo, smask.data_ptr(), stream)
+        barrier()
+        strong_mine = time.perf_counter() - t0
+        strong_elapsed = maxed(strong_mine)
+        strong_accept = float(smask.float().mean().item())
+        # sharded bootstrap: masks drawn once, broadcast, 30 rounds over the ranks, ONE all-reduce(MAX) of 3 doubles
+        boot_reps = max(3, min(10, args.steps))
+        r2_keep, f_keep = region.maxradiussq, region.enlarge
+        rs_b = np.random.RandomState(5)
+        distributed.update_region_bootstrap(region, NBOOT, minvol=0., group=group, rng=rs_b)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(boot_reps):
+            r_b, f_b = distributed.update_region_bootstrap(region, NBOOT, minvol=0., group=group, rng=rs_b)
+        barrier()
+        boot_mine = (time.perf_counter() - t0) / boot_reps
+        boot_elapsed = maxed(boot_mine)
+        region.maxradiussq, region.enlarge = r2_keep, f_keep     # the timed batches (and the CPU baseline below) belong to THIS region
+        ranks_seen = 1
+        collective_library = None
+        if use_dist:
+            import torch.distributed as dist
+            ones = torch.ones(1, dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(ones, op=dist.ReduceOp.SUM)
+            ranks_seen = int(round(float(ones.item())))
+            if backend == "nccl":
+                try:
+                    collective_library = "RCCL %s (torch.cuda.nccl.version(); backend 'nccl' IS RCCL on ROCm)" % ".".join(
+                        str(x) for x in torch.cuda.nccl.version())
+                except Exception as e:       # noqa: BLE001 -- the version string is a report field, not a requirement
+                    collective_library = "RCCL (version unavailable: %s)" % e
+            else:
+                collective_library = "gloo (ranks share this box's device(s): rehearsal, not RCCL)"
+        strong = {
+            "what": "ONE batch of %d proposals per step, rows sharded over %d rank(s) by shard_bounds (region replicated, no "
+                    "collective in the data path); value = P x steps / max-over-ranks seconds between two barriers" % (NPROPOSALS, world),
+            "value": NPROPOSALS * args.steps / strong_elapsed, "unit": "proposals/s", "ms_per_step": strong_elapsed / args.steps * 1e3,
+            "rows_this_rank": hi - lo, "accept_fraction_this_rank": strong_accept,
+            "bootstrap30_sharded_ms": boot_elapsed * 1e3,
+            "bootstrap30_sharded_what": "distributed.update_region_bootstrap: 30 selection masks drawn on every rank, rank 0's "
+                                        "broadcast, ceil(30 / ranks) rounds per rank on the device, ONE all-reduce(MAX) of (r2, f, "
+                                        "error flag), INCLUDED in the time; max over ranks",
+            "bootstrap_result": [r_b, f_b],
+            "collective_backend": (backend if use_dist else None), "collective_library": collective_library,
+            "ranks_seen_by_allreduce": ranks_seen,
+            "ranks_agree_on_the_shared_rows": ranks_agree,
+        }
+        return strong, strong_mine, boot_mine, smask
+
     lib_mod.set_option("time_filter_launches", 0)
     exact_elapsed = ncalls_x = ms_scan_x = scan_flops = ell_pass = None
     nsteps_x = max(3, args.steps // 4)
     masks_exact = None
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         # ---- the reference answer first: the exact FP64 scan kernel alone (MFMA pre-filter switched off) on the same
         # batches.  Its masks are what the timed path is compared with below; its time is `roofline_exact_scan`.
         lib_mod.set_option("filter", 0)
@@ -531,6 +651,44 @@ def main():
     # ---- the headline: W warm-up steps, then exactly K steps; NO events inside the loop (the event pairs around the
     # matrix launches cost 7 %; the per-launch times come from the separate pass below) -------------------------------------
     elapsed, elapsed_mine = run_steps(args.steps, False, settle=CLOCK_SETTLE_STEPS)
+    if args.dump_outputs and args.scaling == "weak" and rank == 0:
+        dump_outputs(args.dump_outputs, masks[(args.steps - 1) % NBATCHES])     # step i filtered batch i mod NBATCHES
+    if not args.full:
+        # ---- plain run: the headline line and nothing else ----------------------------------------------------------
+        strong = None
+        strong_mine = boot_mine = 0.0
+        if args.scaling == "strong":
+            strong, strong_mine, boot_mine, smask = strong_leg()
+            if args.dump_outputs and rank == 0:
+                dump_outputs(args.dump_outputs, smask)
+        per_rank = [elapsed_mine]
+        per_rank_strong = [(strong_mine, boot_mine)]
+        if use_dist:
+            import torch.distributed as dist
+            gathered = [None] * world
+            dist.all_gather_object(gathered, (elapsed_mine, strong_mine, boot_mine))
+            per_rank = [a for a, _, _ in gathered]
+            per_rank_strong = [(b, c) for _, b, c in gathered]
+        if rank == 0:
+            weak = {"what": "%d proposals per rank and step (the per-GPU work is fixed as ranks are added)" % NPROPOSALS,
+                    "value": NPROPOSALS * world * args.steps / elapsed, "unit": "proposals/s",
+                    "ms_per_step": elapsed / args.steps * 1e3, "per_rank_ms_per_step": [t / args.steps * 1e3 for t in per_rank]}
+            if strong is not None:
+                strong["per_rank_ms_per_step"] = [a / args.steps * 1e3 for a, _ in per_rank_strong]
+                strong["per_rank_bootstrap30_ms"] = [b * 1e3 for _, b in per_rank_strong]
+            headline = strong if args.scaling == "strong" else weak
+            out = {"metric": METRIC, "value": headline["value"], "unit": "proposals/s", "n_gpus": world, "steps": args.steps,
+                   "warmup": args.warmup, "ms_per_step": headline["ms_per_step"], "higher_is_better": True, "scaling": args.scaling,
+                   "clock_settle_steps": CLOCK_SETTLE_STEPS, "weak_scaling": weak, "strong_scaling": strong,
+                   "vs_baseline": None, "dtype": "f64", "data": "synthetic", "config": workload_config(world),
+                   "per_rank_ms_per_step": weak["per_rank_ms_per_step"], "accept_fraction": float(mask.float().mean().item()),
+                   "full": False}
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     for i in range(NBATCHES):      # every batch's mask is the timed path's (a short loop may not have reached all three)
         handle.inside_dev(batches[i].data_ptr(), NPROPOSALS, masks[i].data_ptr(), stream)
     batch0_once()
@@ -601,93 +759,10 @@ def main():
         if rank == 0:
             hostapi = host_api(region, pts)
 
-    # ---- strong scaling: ONE batch of P proposals per step, rows sharded over the ranks (distributed.shard_bounds; no
-    # collective in the data path, integrator.py:1916-1928 gathers only accepted rows), and the 30-round bootstrap of
-    # the rebuild sharded over the ranks INCLUDING its all-reduce (integrator.py:375-415) -------------------------
-    from ultranest_amd import distributed
-
-    def maxed(x):
-        if not use_dist:
-            return float(x)
-        import torch.distributed as dist
-        t = torch.tensor([x], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return float(t.item())
-
-    lo, hi = distributed.shard_bounds(NPROPOSALS, rank, world)
-    ranks_agree = None
-    if world > 1:
-        full = proposals_in_ellipsoid(region, NPROPOSALS, 1000, dev)     # the SAME batch on every rank; each takes its rows
-        shard = full[lo:hi].contiguous()
-        # every rank also filters the SAME first 65536 rows of that batch: a digest of the mask must be the same number on
-        # every rank (MIN == MAX over the ranks) -- a rank whose region, library or device disagrees fails the run loudly
-        nshared = 65536
-        shared_mask = torch.empty(nshared, dtype=torch.uint8, device=dev)
-        handle.inside_dev(full.data_ptr(), nshared, shared_mask.data_ptr(), stream)
-        torch.cuda.synchronize()
-        digest = int((shared_mask.long() * (torch.arange(nshared, device=dev, dtype=torch.int64) % 1000003 + 1)).sum().item())
-        import torch.distributed as dist
-        dg = torch.tensor([digest, -digest], dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
-        dist.all_reduce(dg, op=dist.ReduceOp.MAX)
-        ranks_agree = bool(int(dg[0].item()) == -int(dg[1].item()))
-        assert ranks_agree, "rank %d: the ranks' masks on the shared rows differ (digest %d, max %d, min %d)" % (
-            rank, digest, int(dg[0].item()), -int(dg[1].item()))
-        del full, shared_mask
-    else:
-        shard = pts
-    smask = torch.empty(hi - lo, dtype=torch.uint8, device=dev)
-    for _ in range(CLOCK_SETTLE_STEPS + args.warmup):
-        handle.inside_dev(shard.data_ptr(), hi - lo, smask.data_ptr(), stream)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        handle.inside_dev(shard.data_ptr(), hi - lo, smask.data_ptr(), stream)
-    barrier()
-    strong_mine = time.perf_counter() - t0
-    strong_elapsed = maxed(strong_mine)
-    strong_accept = float(smask.float().mean().item())
-    # sharded bootstrap: masks drawn once, broadcast, 30 rounds over the ranks, ONE all-reduce(MAX) of 3 doubles
-    boot_reps = max(3, min(10, args.steps))
-    r2_keep, f_keep = region.maxradiussq, region.enlarge
-    rs_b = np.random.RandomState(5)
-    distributed.update_region_bootstrap(region, NBOOT, minvol=0., group=group, rng=rs_b)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(boot_reps):
-        r_b, f_b = distributed.update_region_bootstrap(region, NBOOT, minvol=0., group=group, rng=rs_b)
-    barrier()
-    boot_mine = (time.perf_counter() - t0) / boot_reps
-    boot_elapsed = maxed(boot_mine)
-    region.maxradiussq, region.enlarge = r2_keep, f_keep     # the timed batches (and the CPU baseline below) belong to THIS region
-    ranks_seen = 1
-    collective_library = None
-    if use_dist:
-        import torch.distributed as dist
-        ones = torch.ones(1, dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-        dist.all_reduce(ones, op=dist.ReduceOp.SUM)
-        ranks_seen = int(round(float(ones.item())))
-        if backend == "nccl":
-            try:
-                collective_library = "RCCL %s (torch.cuda.nccl.version(); backend 'nccl' IS RCCL on ROCm)" % ".".join(
-                    str(x) for x in torch.cuda.nccl.version())
-            except Exception as e:       # noqa: BLE001 -- the version string is a report field, not a requirement
-                collective_library = "RCCL (version unavailable: %s)" % e
-        else:
-            collective_library = "gloo (ranks share this box's device(s): rehearsal, not RCCL)"
-    strong = {
-        "what": "ONE batch of %d proposals per step, rows sharded over %d rank(s) by shard_bounds (region replicated, no "
-                "collective in the data path); value = P x steps / max-over-ranks seconds between two barriers" % (NPROPOSALS, world),
-        "value": NPROPOSALS * args.steps / strong_elapsed, "unit": "proposals/s", "ms_per_step": strong_elapsed / args.steps * 1e3,
-        "rows_this_rank": hi - lo, "accept_fraction_this_rank": strong_accept,
-        "bootstrap30_sharded_ms": boot_elapsed * 1e3,
-        "bootstrap30_sharded_what": "distributed.update_region_bootstrap: 30 selection masks drawn on every rank, rank 0's "
-                                    "broadcast, ceil(30 / ranks) rounds per rank on the device, ONE all-reduce(MAX) of (r2, f, "
-                                    "error flag), INCLUDED in the time; max over ranks",
-        "bootstrap_result": [r_b, f_b],
-        "collective_backend": (backend if use_dist else None), "collective_library": collective_library,
-        "ranks_seen_by_allreduce": ranks_seen,
-        "ranks_agree_on_the_shared_rows": ranks_agree,
-    }
+    # ---- strong scaling (strong_leg above) ----------------------------------------------------------------------------
+    strong, strong_mine, boot_mine, smask = strong_leg()
+    if args.dump_outputs and args.scaling == "strong" and rank == 0:
+        dump_outputs(args.dump_outputs, smask)
 
     first_ms, rebuild_ms, rebuild_all = time_rebuild(u, group)
     _, rebuild_dev_ms, rebuild_dev_all = time_rebuild(u, group, device_resident=True) if world == 1 else (None, None, None)
@@ -750,18 +825,13 @@ def main():
     prep_bytes = NPROPOSALS * (8 * NDIM + 2 * kdim + 8 + 1 + 4 + 4 + 1)
     prep_mfma_flops = NPROPOSALS / 32 * PREP_MFMA_PER_GROUP * MFMA_F16_FLOPS   # k_prep4 in its own launch runs both chains
     out = {
-        "metric": "proposal-points filtered/sec (MLFriends.inside) + region-rebuild ms, N=4000 d=50",
+        "metric": METRIC, "full": True,
         "value": headline["value"], "unit": "proposals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": headline["ms_per_step"], "higher_is_better": True, "scaling": args.scaling,
         "clock_settle_steps": CLOCK_SETTLE_STEPS,
         "weak_scaling": weak, "strong_scaling": strong,
         "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "C5: N=4000 live points, d=50, P=1e6 proposals/step/GPU drawn uniformly inside the "
-                               "wrapping ellipsoid (set E), AffineLayer, 30 bootstraps; one step = MLFriends.inside "
-                               "on a batch resident in HBM; the timed loop visits %d distinct batches in turn" % NBATCHES,
-                   "n_live": N_LIVE, "d": NDIM, "proposals_per_step_per_gpu": NPROPOSALS, "bootstraps": NBOOT,
-                   "distinct_batches_in_the_timed_loop": NBATCHES,
-                   "parallelism": "proposal rows sharded over " + str(world) + " GPU(s), region replicated",
+        "config": {**workload_config(world),
                    "mfma_prefilter": bool(filter_on),
                    "arithmetic": "inputs, thresholds and every decision that depends on the reference's rounding: binary64 "
                                  "(non-fused); deciding bounds for the other 99.99 %% of the pairs: binary16 operands / "

@@ -22,7 +22,7 @@ python scripts/collect_r04_pmc.py $O/$P profiles/r04 > $O/${P}_collect.log 2>&1;
 cp profiles/pmc_scan_traffic.json profiles/r04_pmc_summary.json $O/ 2>/dev/null
 echo "== pytest -m gpu"; timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; grep -n "passed\|failed\|Error" $O/pytest_gpu.log | tail -5
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-echo "== bench"; timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; python - <<'PY'
+echo "== bench"; timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/bench.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d.get('rebuild_ms'), d.get('rebuild_device_resident_ms'))
@@ -33,7 +33,7 @@ PY
 tail -3 $O/bench.err
 cd /tmp
 echo "== bench under rocprofv3 (kernel statistics of the same command)"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${P}_bench_stats -o st -- python $R/bench.py --steps 20 --warmup 5 --headline-only --no-cpu > $O/${P}_bench_stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${P}_bench_stats -o st -- python $R/bench.py --full --steps 20 --warmup 5 --headline-only --no-cpu > $O/${P}_bench_stats.log 2>&1
 head -12 $(find $O/${P}_bench_stats -name "*kernel_stats.csv" | head -1) | cut -c1-160
 cd $R
 echo "== reference grid"; timeout 600 python scripts/reference_grid_bench.py > $O/reference_grid.json 2> $O/reference_grid.err; tail -5 $O/reference_grid.err | cut -c1-300

@@ -23,7 +23,7 @@ python scripts/collect_pmc.py $O/$P profiles/r05 > $O/${P}_collect.log 2>&1; tai
 cp profiles/pmc_scan_traffic.json profiles/r05_pmc_summary.json $O/ 2>/dev/null
 echo "== pytest -m gpu"; timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; grep -n "passed\|failed\|Error" $O/pytest_gpu.log | tail -5; grep -B5 -A25 "^E " $O/pytest_gpu.log | head -50
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-echo "== bench"; timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; python - <<'PY'
+echo "== bench"; timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/bench.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d.get('rebuild_ms'), d.get('rebuild_device_resident_ms'))
@@ -34,7 +34,7 @@ PY
 tail -3 $O/bench.err
 cd /tmp
 echo "== bench under rocprofv3 (kernel statistics of the same command)"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${P}_bench_stats -o st -- python $R/bench.py --steps 20 --warmup 5 --headline-only --no-cpu > $O/${P}_bench_stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${P}_bench_stats -o st -- python $R/bench.py --full --steps 20 --warmup 5 --headline-only --no-cpu > $O/${P}_bench_stats.log 2>&1
 head -12 $(find $O/${P}_bench_stats -name "*kernel_stats.csv" | head -1) | cut -c1-160
 cd $R
 echo "== reference grid"; timeout 600 python scripts/reference_grid_bench.py > $O/reference_grid.json 2> $O/reference_grid.err; tail -3 $O/reference_grid.err | cut -c1-300
@@ -54,7 +54,7 @@ cp $(find $O/r05_d100_stats -name "*kernel_stats.csv" | head -1) $O/r05_d100_ker
 cd $R
 echo "== end-to-end runs"; timeout 900 python scripts/e2e_run.py > $O/e2e_run.log 2>&1; tail -4 $O/e2e_run.log | cut -c1-700
 echo "== 8 ranks on this box's single device over gloo (rehearsal of the driver's multi-GPU pass: rendezvous, barriers, collectives)"
-timeout 900 python bench.py --gpus 8 --scaling strong --steps 5 --warmup 2 --no-cpu > $O/bench_8rank_selfspawn_gloo.json 2> $O/bench_8rank.err; python - <<'PY'
+timeout 900 python bench.py --full --gpus 8 --scaling strong --steps 5 --warmup 2 --no-cpu > $O/bench_8rank_selfspawn_gloo.json 2> $O/bench_8rank.err; python - <<'PY'
 import json
 try:
     d=json.loads(open('gpurun_out/bench_8rank_selfspawn_gloo.json').read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd $R
 timeout 1200 python -m pytest tests/test_gpu_filter.py tests/test_config_sizes.py -m gpu -x -q --durations=5 > $O/r05p_pytest.log 2>&1; grep -E "passed|failed|error" $O/r05p_pytest.log | tail -3; grep -B5 -A30 "^E " $O/r05p_pytest.log | head -80
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/r05p_bench.json 2> $O/r05p_bench.err; tail -3 $O/r05p_bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/r05p_bench.json 2> $O/r05p_bench.err; tail -3 $O/r05p_bench.err
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r05p_bench.json').read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ echo "== e2e, one round per call (as round 5)"
 timeout 300 python scripts/e2e_run.py max_rounds=1 > $O/r06b_e2e_single.log 2>&1; cut -c1-330 $O/r06b_e2e_single.log | tail -3
 echo "== mid-size traces"
 bash scripts/gpu_trace_mid.sh r06b 16384 65536 131072 2>&1 | tail -30
-echo "== bench"; timeout 900 python bench.py --steps 20 --warmup 5 > $O/r06b_bench.json 2> $O/r06b_bench.err; tail -3 $O/r06b_bench.err; python - <<'PY'
+echo "== bench"; timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r06b_bench.json 2> $O/r06b_bench.err; tail -3 $O/r06b_bench.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06b_bench.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d.get('rebuild_ms'), d.get('rebuild_device_resident_ms'), d['strong_scaling']['ms_per_step'])

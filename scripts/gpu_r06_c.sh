@@ -8,7 +8,7 @@ echo "== fused A/B"
 timeout 300 python scripts/fused_ab.py 300 > $O/r06c_fused_ab.jsonl 2> $O/r06c_fused_ab.err; cut -c1-900 $O/r06c_fused_ab.jsonl; tail -3 $O/r06c_fused_ab.err
 echo "== filter tests"
 timeout 900 python -m pytest tests/test_config_sizes.py tests/test_gpu_filter.py -m gpu -x -q 2>&1 | tail -3
-echo "== bench"; timeout 900 python bench.py --steps 20 --warmup 5 > $O/r06c_bench.json 2> $O/r06c_bench.err; tail -3 $O/r06c_bench.err; python - <<'PY'
+echo "== bench"; timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r06c_bench.json 2> $O/r06c_bench.err; tail -3 $O/r06c_bench.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06c_bench.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d.get('rebuild_ms'), d.get('rebuild_device_resident_ms'), d['strong_scaling']['ms_per_step'])

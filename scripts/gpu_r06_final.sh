@@ -25,7 +25,7 @@ cp profiles/pmc_scan_traffic.json profiles/r06_pmc_summary.json $O/ 2>/dev/null
 for f in sq wait FETCH_SIZE WRITE_SIZE; do cp $O/${P}_pmc_$f.txt $O/r06_pmc_$f.txt; done
 echo "== pytest -m gpu"; timeout 1500 python -m pytest tests -m gpu -x -q > $O/r06_pytest_gpu.log 2>&1; grep -n "passed\|failed\|Error" $O/r06_pytest_gpu.log | tail -5; grep -B5 -A25 "^E " $O/r06_pytest_gpu.log | head -50
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/r06_smoke.log 2>&1; tail -2 $O/r06_smoke.log
-echo "== bench"; timeout 600 python bench.py --steps 20 --warmup 5 > $O/r06_bench.json 2> $O/r06_bench.err; python - <<'PY'
+echo "== bench"; timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/r06_bench.json 2> $O/r06_bench.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06_bench.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d.get('rebuild_ms'), d.get('rebuild_device_resident_ms'), d['strong_scaling']['ms_per_step'])
@@ -37,7 +37,7 @@ PY
 tail -3 $O/r06_bench.err
 cd /tmp
 echo "== bench under rocprofv3 (kernel statistics of the same command)"
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${P}_bench_stats -o st -- python $R/bench.py --steps 20 --warmup 5 --headline-only --no-cpu > $O/${P}_bench_stats.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${P}_bench_stats -o st -- python $R/bench.py --full --steps 20 --warmup 5 --headline-only --no-cpu > $O/${P}_bench_stats.log 2>&1
 head -8 $(find $O/${P}_bench_stats -name "*kernel_stats.csv" | head -1) | cut -c1-160
 cp $(find $O/${P}_bench_stats -name "*kernel_stats.csv" | head -1) $O/r06_bench_rocprofv3_kernel_stats.csv
 cd $R
@@ -53,7 +53,7 @@ timeout 300 python scripts/walk_bench.py > $O/r06_walk_bench.json 2> $O/r06_walk
 timeout 300 python scripts/sample_bench.py > $O/r06_sample_bench.json 2> $O/r06_sample_bench.err; tail -c 700 $O/r06_sample_bench.json
 timeout 200 python scripts/refill_profile.py 10 --all > $O/r06_refill.json 2> $O/r06_refill.err; cat $O/r06_refill.json
 echo "== 8 ranks on this box's single device over gloo (rehearsal of the driver's multi-GPU pass)"
-timeout 600 python bench.py --gpus 8 --scaling strong --steps 5 --warmup 2 --no-cpu > $O/r06_bench_8rank_selfspawn_gloo.json 2> $O/r06_bench_8rank.err; python - <<'PY'
+timeout 600 python bench.py --full --gpus 8 --scaling strong --steps 5 --warmup 2 --no-cpu > $O/r06_bench_8rank_selfspawn_gloo.json 2> $O/r06_bench_8rank.err; python - <<'PY'
 import json
 try:
     d=json.loads(open('gpurun_out/r06_bench_8rank_selfspawn_gloo.json').read().strip().splitlines()[-1])
