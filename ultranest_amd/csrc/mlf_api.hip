@@ -2,6 +2,7 @@
 // device buffers, host<->device staging and kernel sequencing.  No numerics live here.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -118,6 +119,45 @@ long long opt_clamp(int id, long long value) {
   }
 }
 
+// ---- routing of one batch of rows through the membership / neighbour test -----------------------------------------
+enum BatchKind : int {
+  BATCH_INSIDE,   // region_inside_enqueue: cube-space proposals, per-proposal stage + neighbour test
+  BATCH_TSPACE,   // region_scan_mask: whitened rows, neighbour test only
+  BATCH_GATE,     // region_ellipsoid_gate: the wrapping-ellipsoid test only
+  BATCH_HOST,     // scan_host: rows against live points handed over with the call (the context's FilterCtx, no region)
+};
+
+// the stage that turns the proposals into what the neighbour test reads
+enum Stage : int {
+  STAGE_NONE,     // the rows arrive whitened
+  STAGE_PREP4,    // bounded matrix-core stage (mlf_prep4.hip): ellipsoid test, approximate whitening into the filter operand
+  STAGE_PREP3,    // binary64 matrix-core stage (mlf_prep3.hip), quantising for the filter where it applies
+  STAGE_PREP64,   // 65 ... 128 dimensions (mlf_prep64.hip)
+  STAGE_PREP,     // vector kernel (k_prep), a scaling layer's transform behind it
+};
+
+// Every choice the routing of one batch makes.  plan_batch decides them once; the launch sequences only read them.
+struct BatchPlan {
+  bool filter = false;          // matrix-core pre-filter in front of the exact scan (else the exact scan alone)
+  bool host_refs = false;       // BATCH_HOST: quantise the live points for the filter, then plan the batch again
+  Stage stage = STAGE_NONE;
+  bool mid = false;             // stage, sweep, re-check and answers in one launch (k_inside_mid)
+  bool time_launches = false;   // "time_filter_launches": event pairs around the matrix launches, k_inside_mid's stamps
+  bool ordered = false;         // sweep the centre-first copy of the live points (refFm / refRm)
+  int nphase = 1;               // live-point ranges of the sweep
+  int narrow = 0;               // later ranges with two query groups per wave
+  int split = 1;                // tile ranges of a single sweep (filter_tile_split)
+  bool own_recheck = false;     // the sweeping waves re-check their own segments: no re-check launch
+  bool fold_finish = false;     // two ranges, finalise in the scan launch: no k_phase_finish
+  bool min_path = false;        // min-only sweep (mlf_sweepmin.hip) + k_uncertain
+  int cut[2] = {0, 0};          // tile cuts of two ranges: [0, cut[0]) [cut[0], ntiles32); three: cut[1] starts the last
+  bool defer = false;           // the bounded stage runs inside the first sweep launch (k_prep_sweep)
+  unsigned fused_variant = 0;   // k_prep_sweep: bit 0 LDS-DMA fragments, bit 1 same quadratic form, bit 2 pre-gated
+  int fused_waves = 4;          // waves per workgroup of k_prep_sweep
+  long long nsegs = 0;          // list segments the re-check walks
+  long long seg_room = 0;       // list segments any launch of the batch writes
+};
+
 struct FilterCtx {
   bool refs_ready = false;   // live points quantised
   bool refs_dirty = false;   // a live point was replaced since: requantise before the next batch that uses the operands
@@ -133,7 +173,6 @@ struct FilterCtx {
   // phased sweep: two compacted query sets (ping-pong)
   DevBuf pqF[2], ptlo[2], pthi[2], pmap[2], png, pmin, pmin2;
   DevBuf mid_rec, mid_meta, mid_arrive;   // one-launch path (mlf_mid.hip): records of the tile ranges, arrival counters
-  bool mid_last = false;                  // the last batch took that path (debug_stats)
   bool mid_dirty = false;                 // a launch of that path failed: its self-resetting counters are zeroed before the next batch
   DevBuf fstamps;                         // diagnostics: stage stamps of one k_prep_sweep wave
   int stamp_block = -1;
@@ -145,11 +184,8 @@ struct FilterCtx {
   // batch (mlf_region_debug_stats)
   DevBuf ell_list, misc;
   unsigned batch_parity = 0;
-  size_t last_nsegs = 0;      // list segments of the last filtered batch
-  int last_cut[2] = {0, 0};   // tile cuts of the last min-only batch (second: 0 with two ranges)
-  bool last_same_form = false;   // the last fused launch read the ellipsoid form off the whitening chain (debug_stats)
-  bool ell_pending = false;   // band list of the running call not decided yet (the tail of the re-check launch decides it)
-  EllExactArgs ell_args{};
+  BatchPlan last;             // the route of the last filtered batch (debug_stats) ...
+  BatchPlan last_min;         // ... and of the last one that took the min-only sweep
   // (start, stop) event pairs around every k_filter launch of the timed calls
   std::vector<hipEvent_t> kev;
   size_t kev_used = 0;
@@ -383,565 +419,11 @@ int filter_refresh_refs(FilterCtx &f, const double *refR, int n, int d, int dp, 
   return 0;
 }
 
-// host-side eligibility of one batch (the kernels re-check per query and fall back on their own)
-bool filter_applies(const FilterCtx &f, long long nq, double r2) {
-  if (!opt(f, OPT_FILTER) || !f.refs_ready || !f.usable || nq < opt(f, OPT_MIN_QUERIES)) return false;
-  // below ~2000 proposals the five launches of the filter path (~45 us) only pay when the exact scan has real work:
-  // 400 proposals against 400 x 5 live coordinates take 43 us through the exact scan, 51 us through the filter
-  if (opt(f, OPT_MIN_QUERIES) == kFilterMinQueriesDefault && nq < 2048 && (long long)f.ntiles32 * 32 * f.ks * 16 < 40000) return false;
-  if (!(r2 > 0.0) || !(r2 < 1e150)) return false;
-  const double sr2 = f.sigma * f.sigma * r2;
-  return sr2 < 4096.0 && sr2 > 1e-30;
-}
-
 // self-resetting counters of the bounded stage: zeroed once, when allocated
 int misc_reserve(FilterCtx &f) {
   if (f.misc.p) return 0;
   CK(f.misc.reserve(8 * sizeof(unsigned)));
   CK(hipMemset(f.misc.p, 0, 8 * sizeof(unsigned)));
-  return 0;
-}
-
-// Device buffers of one filtered batch.
-int filter_reserve(FilterCtx &f, long long nq, unsigned *cap_out) {
-  const long long nqpad = (nq + 31) / 32 * 32;
-  long long nwaves = filter_wave_count(f.ks, nqpad / 32, f.ks == 4 ? 2 : (f.ks < 4 ? 1 : 0));   // room for a narrow later range
-  {   // ... and for the tile ranges of a small batch (filter_tile_split): one segment per (wave, range)
-    const long long plain = (filter_wave_count(f.ks, nqpad / 32) + 3) / 4 * 4;
-    const long long split = filter_tile_split(f.ks, nqpad / 32, f.ntiles32, (int)opt(f, OPT_SPLIT_WAVES));
-    if (split * plain > nwaves) nwaves = split * plain;
-  }
-  const unsigned cap = kFilterSegCap;   // uncertain pairs per filter wave (expected: tens)
-  CK(f.qF.reserve((size_t)nqpad * f.ks * 16 * 2));
-  CK(f.tlo.reserve((size_t)nqpad * sizeof(float)));
-  CK(f.thi.reserve((size_t)nqpad * sizeof(float)));
-  CK(f.route.reserve((size_t)nq));
-  CK(f.best.reserve((size_t)nq * sizeof(int)));
-  CK(f.counters.reserve(4 * sizeof(unsigned)));
-  CK(f.list.reserve((size_t)nwaves * cap * sizeof(unsigned long long)));
-  CK(f.segcnt.reserve((size_t)nwaves * sizeof(unsigned)));
-  CK(f.gate2.reserve((size_t)nq));
-  if (int rc = misc_reserve(f)) return rc;
-  *cap_out = cap;
-  return 0;
-}
-
-// Filter pipeline on device data: answers for all nq queries in out_mask (bytes) and/or out_idx.
-// Query element (j, k) is q[j*ldq + k*ldk].  quantised = true: the fused per-proposal stage has already
-// produced the binary16 fragments, thresholds and routes of this batch.
-// Where the exact whitened coordinates come from when the per-proposal stage did not store them (k_prep4): the
-// proposals themselves and the layer; the queries that need coordinates are whitened after the sweeps.
-struct ExactSrc {
-  const double *pts;
-  const double *lay_ctr;
-  const double *T8;   // row-major layer matrix, row stride ldt
-  int ldt;
-  const double *T64;  // the same as 64 x 64, zero padded (d <= 64)
-  const Prep4Args *prep;   // not null: the per-proposal stage has NOT run yet -- the min-only path runs it inside its first launch
-  const Prep4Consts *same; // not null: constants of the "same quadratic form" variant of that launch (region_prep4_setup)
-  bool pregated;           // the gate array holds a pre-gate on entry (device-side sampling: the cube test) for that launch to honour
-};
-
-// does a batch of nq queries take the min-only path?  (the phase rule of filter_run)
-// Tile ranges of the min-only sweep, every range at least 4 tiles.  Two ranges: [0, c1) [c1, ntiles32) with c1 = first_pct of
-// the tiles (c2 = 0).  Three -- batches of at least min_work (proposals x tiles), where the pairs a third range saves outweigh
-// its launch and its compaction: the last range starts at c2 = second_pct of the tiles and [0, c2) is split at first_pct of
-// c2 (30 % of 50 % = 15 %, 50 %: profiles/r05_three_range_ab.jsonl).
-void filter_range_cuts(int ntiles32, long long nq, int first_pct, int second_pct, long long min_work, int *c1, int *c2) {
-  const int cut = (int)((long long)ntiles32 * first_pct / 100);
-  *c1 = cut < 4 ? 4 : (cut > ntiles32 - 4 ? ntiles32 - 4 : cut);
-  *c2 = 0;
-  if (second_pct <= 0 || nq * ntiles32 < min_work) return;
-  const int cut2 = (int)((long long)ntiles32 * second_pct / 100);
-  int a = (int)((long long)cut2 * first_pct / 100);
-  a = a < 4 ? 4 : a;
-  if (cut2 >= a + 4 && cut2 <= ntiles32 - 4) {
-    *c1 = a;
-    *c2 = cut2;
-  }
-}
-
-bool filter_takes_min_path(const FilterCtx &f, long long nq) {
-  const int want_phases = (int)opt(f, OPT_PHASES);
-  const long long phase_min = opt(f, OPT_PHASE_MIN_QUERIES);
-  int nphase = 1;
-  if (want_phases && nq >= phase_min && (phase_min < 32768 || nq * f.ntiles32 >= 30000000ll))
-    nphase = want_phases >= 2 ? (want_phases <= f.ntiles32 / 4 ? want_phases : (f.ntiles32 >= 16 ? 2 : 1)) : (f.ntiles32 >= 16 ? 2 : 1);
-  return nphase == 2 && f.ks <= 4 && opt(f, OPT_SWEEP_MIN);
-}
-
-int filter_run(FilterCtx &f, const double *refT, const double *refR, int n, int npad, int d, int dp,
-               const double *q, long long ldq, long long ldk, long long nq, double r2, const uint8_t *gate,
-               uint8_t *out_mask, long long *out_idx, hipStream_t s, bool quantised,
-               hipEvent_t ev_after_filter = nullptr, const ExactSrc *xs = nullptr) {
-  const long long ngroups = (nq + 31) / 32;
-  const long long nqpad = ngroups * 32;
-  unsigned cap = 0;
-  f.mid_last = false;
-  if (int rc = filter_reserve(f, nq, &cap)) return rc;
-  // mask mode sweeps the centre-first copy of the live points (any hit decides); the first-index mode keeps storage order
-  const bool use_m = out_idx == nullptr && f.ordered && opt(f, OPT_ORDER);
-  const void *const opF = use_m ? f.refFm.p : f.refF.p;
-  const double *const opR = use_m ? f.refRm.as<double>() : refR;
-  if (!quantised)
-  launch_quant_queries(q, ldq, nq, nqpad, d, dp, f.ks, f.stats.as<double>(), r2, gate, f.qF.p, f.tlo.as<float>(),
-                       f.thi.as<float>(), f.route.as<uint8_t>(), f.best.as<int>(), f.counters.as<unsigned>(), s);
-  CK(hipGetLastError());
-  FilterArgs fa{};
-  fa.refF = opF;
-  fa.qF = f.qF.p;
-  fa.tlo = f.tlo.as<float>();
-  fa.thi = f.thi.as<float>();
-  fa.ntiles32 = f.ntiles32;
-  fa.ngroups = ngroups;
-  fa.nq = nq;
-  fa.best = f.best.as<int>();
-  fa.list = f.list.as<unsigned long long>();
-  fa.seg_cap = cap;
-  fa.seg_count = f.segcnt.as<unsigned>();
-  fa.counters = f.counters.as<unsigned>();
-  // Phased sweep: the live-point tiles are split into nphase ranges; after each range the queries that
-  // are decided (certain hit) leave, the rest is compacted into fresh 32-query groups.  Every launch
-  // is sized for the worst case and reads the actual group count from device memory: no host sync.
-  int nphase = 1;
-  // worth it when the sweep is long compared with one compaction (~25 us + 40 us per 10^6 queries)
-  const int want_phases = (int)opt(f, OPT_PHASES);
-  const long long phase_min = opt(f, OPT_PHASE_MIN_QUERIES);
-  const int narrow_tail = (int)opt(f, OPT_NARROW_TAIL);
-  if (want_phases && nq >= phase_min && (phase_min < 32768 || nq * f.ntiles32 >= 30000000ll))
-    nphase = want_phases >= 2 ? (want_phases <= f.ntiles32 / 4 ? want_phases : (f.ntiles32 >= 16 ? 2 : 1))
-                                  : (f.ntiles32 >= 16 ? 2 : 1);
-  if (nphase > 1) {
-    for (int i = 0; i < 2; ++i) {
-      CK(f.pqF[i].reserve((size_t)nqpad * f.ks * 16 * 2));
-      CK(f.ptlo[i].reserve((size_t)nqpad * sizeof(float)));
-      CK(f.pthi[i].reserve((size_t)nqpad * sizeof(float)));
-      CK(f.pmap[i].reserve((size_t)nqpad * sizeof(int)));
-    }
-    if (!f.png.p) {   // group counts + the slot counter of the fused compaction (returns to zero by itself: k_phase_finish)
-      // words: [0] groups after the first range, [1] size of the uncertain set (statistics of the last batch), [2] [3] [4] slot
-      // counters of the compacted sets, [5] groups after the second of three ranges
-      CK(f.png.reserve(8 * sizeof(unsigned)));
-      CK(hipMemset(f.png.p, 0, 8 * sizeof(unsigned)));
-    } else if (f.png_dirty) {   // an earlier phased batch failed between its first compaction and its scan launch (ADVICE r4)
-      CK(hipMemsetAsync(f.png.p, 0, 8 * sizeof(unsigned), s));
-    }
-    f.png_dirty = true;   // until the scan launch of this batch is queued
-  }
-  const bool fused = nphase > 1;   // the compaction of the undecided queries rides in the matrix kernel's epilogue
-  // mask mode behind the bounded per-proposal stage, single-sweep batches (below ~262144 proposals at N = 4000): the
-  // re-check (binary64 whitening of the queries of the uncertain pairs + the reference's distance loop) runs inside the
-  // sweep launch, each wave on the segment it has just written, and the ellipsoid band rides in the same launch: three
-  // launches per batch instead of four (131072 proposals: 104 -> 96 us).  Phased sweeps keep the separate re-check launch:
-  // there the waves' re-check tails cost more than the launch they save (10^6: 0.473 -> 0.51 ms)
-  const bool own_recheck = xs != nullptr && out_idx == nullptr && nphase == 1;
-  if (own_recheck) {
-    fa.rw.list = f.list.as<unsigned long long>();
-    fa.rw.seg_cap = cap;
-    fa.rw.seg_count = f.segcnt.as<unsigned>();
-    fa.rw.refR = opR;
-    fa.rw.n = n;
-    fa.rw.d = d;
-    fa.rw.dp = dp;
-    fa.rw.pts = xs->pts;
-    fa.rw.nq = nq;
-    fa.rw.lay_ctr = xs->lay_ctr;
-    fa.rw.T64 = xs->T64;
-    fa.rw.r2 = r2;
-    fa.rw.best = f.best.as<int>();
-  }
-  fa.split = nphase == 1 ? filter_tile_split(f.ks, ngroups, f.ntiles32, (int)opt(f, OPT_SPLIT_WAVES)) : 1;
-  // two ranges, compaction inside the first, finalise tail in the scan launch: nobody pads the compacted set or publishes
-  // its group count (k_phase_finish: a 5 us launch) -- the second range reads the slot counter itself, the tail resets it
-  const bool fold_finish = fused && nphase == 2 && xs != nullptr;
-
-  // Two ranges in mask mode behind the bounded per-proposal stage: the min-only sweep (mlf_sweepmin.hip).  The two long
-  // launches carry the running minimum only; the queries whose minimum ends in the band are swept once more by
-  // k_uncertain (band pairs found, queries whitened, pairs decided in one launch), which also carries the ellipsoid band.
-  const bool min_path = fold_finish && out_idx == nullptr && f.ks <= 4 && opt(f, OPT_SWEEP_MIN);
-  // filter_second_range_pct > 0: three ranges (the middle one reads set 0 and writes set 1 with a second array of minima;
-  // the uncertain set then reuses set 0's arrays, which nobody reads any more)
-  int c = 0, c2 = 0;
-  filter_range_cuts(f.ntiles32, nq, (int)opt(f, OPT_FIRST_RANGE_PCT), (int)opt(f, OPT_SECOND_RANGE_PCT), opt(f, OPT_THIRD_MIN_WORK), &c, &c2);
-  const bool min3 = min_path && c2 > c;
-  if (xs && xs->prep && !min_path) CK(launch_prep4(*xs->prep, s));   // (the caller's forecast and this routing agree: belt and braces)
-  if (min_path) {
-    const long long lw = uncertain_blocks();
-    CK(f.segcnt.reserve((size_t)(lw + 8) * sizeof(unsigned)));
-    CK(f.pmin.reserve((size_t)nqpad * sizeof(int)));
-    if (min3) CK(f.pmin2.reserve((size_t)nqpad * sizeof(int)));
-    f.last_cut[0] = c;
-    f.last_cut[1] = min3 ? c2 : 0;
-    auto timed = [&](auto &&launch) -> int {
-      const bool time_launch = ev_after_filter || opt(f, OPT_TIME_LAUNCHES);
-      if (time_launch) {
-        while (f.kev.size() < f.kev_used + 2) {
-          hipEvent_t e;
-          CK(hipEventCreate(&e));
-          f.kev.push_back(e);
-        }
-        CK(hipEventRecord(f.kev[f.kev_used], s));
-      }
-      CK(launch());
-      if (time_launch) {
-        CK(hipEventRecord(f.kev[f.kev_used + 1], s));
-        f.kev_used += 2;
-      }
-      return 0;
-    };
-    MinArgs m{};
-    m.refF = opF;
-    m.ntiles32 = f.ntiles32;
-    m.nq = nq;
-    m.best = f.best.as<int>();
-    m.ngroups = ngroups;
-    m.ccap = (unsigned)nqpad;
-    // first range: slot = query; the queries without a certain hit go to set 0 with their minimum
-    m.tile0 = 0;
-    m.tile1 = c;
-    m.qF = f.qF.p;
-    m.tlo = f.tlo.as<float>();
-    m.thi = f.thi.as<float>();
-    m.cq = f.pqF[0].p;
-    m.ctlo = f.ptlo[0].as<float>();
-    m.cthi = f.pthi[0].as<float>();
-    m.cmap = f.pmap[0].as<int>();
-    m.cmin = f.pmin.as<int>();
-    m.ccount = f.png.as<unsigned>() + 2;
-    m.last = 0;
-    if (xs->prep) {   // per-proposal stage + first range in one launch: the operand never leaves the registers
-      FusedArgs fu{};
-      fu.p = *xs->prep;
-      fu.refF = opF;
-      fu.ntiles32 = f.ntiles32;
-      fu.tile0 = 0;
-      fu.tile1 = c;
-      fu.cq = m.cq;
-      fu.ctlo = m.ctlo;
-      fu.cthi = m.cthi;
-      fu.cmap = m.cmap;
-      fu.cmin = m.cmin;
-      fu.ccount = m.ccount;
-      fu.ccap = m.ccap;
-      if (f.stamp_block >= 0 && f.stamp_block < 1000000) {   // diagnostics (mlf_region_debug_fused_stamps)
-        CK(f.fstamps.reserve(16 * sizeof(unsigned long long)));
-        fu.stamps = f.fstamps.as<unsigned long long>();
-        fu.stamp_block = (unsigned)f.stamp_block;
-      }
-      fu.variant = (unsigned)(opt(f, OPT_FUSED_VARIANT) & 0xff);
-      if ((fu.variant & 2u) && xs->same)
-        fu.p.c = *xs->same;
-      else
-        fu.variant &= ~2u;
-      f.last_same_form = (fu.variant & 2u) != 0u;
-      if (xs->pregated) fu.variant |= 4u;
-      const int fused_waves = (int)opt(f, OPT_FUSED_WAVES);
-      if (int rc = timed([&] { return launch_prep_sweep(fu, s, fused_waves); })) return rc;
-    } else if (int rc = timed([&] { return launch_sweep_min(f.ks, filter_groups_per_wave(f.ks, 0), m, s); })) return rc;
-    // next range: set 0 with its minima.  Two ranges: this is the last, the uncertain queries go to set 1.  Three: the
-    // queries still without a certain hit go to set 1 with their minima, and the last range sweeps those into set 0's arrays
-    const int usrc = min3 ? 0 : 1;   // the set that holds the uncertain queries in the end
-    m.tile0 = c;
-    m.tile1 = min3 ? c2 : f.ntiles32;
-    m.qF = f.pqF[0].p;
-    m.tlo = f.ptlo[0].as<float>();
-    m.thi = f.pthi[0].as<float>();
-    m.qmap = f.pmap[0].as<int>();
-    m.qmin = f.pmin.as<int>();
-    m.nslots_dev = f.png.as<unsigned>() + 2;
-    m.cq = f.pqF[1].p;
-    m.ctlo = f.ptlo[1].as<float>();
-    m.cthi = f.pthi[1].as<float>();
-    m.cmap = f.pmap[1].as<int>();
-    m.cmin = min3 ? f.pmin2.as<int>() : nullptr;
-    m.ccount = f.png.as<unsigned>() + 3;
-    m.last = min3 ? 0 : 1;
-    // diagnostics: stage stamps of one k_sweep_min workgroup -- block 1 000 000 + b: the launch that follows the first range,
-    // 2 000 000 + b: the one after it
-    auto sweep_stamps = [&](int which) -> int {
-      m.stamps = nullptr;
-      if (f.stamp_block >= which * 1000000 && f.stamp_block < (which + 1) * 1000000) {
-        CK(f.fstamps.reserve(16 * sizeof(unsigned long long)));
-        m.stamps = f.fstamps.as<unsigned long long>();
-        m.stamp_block = (unsigned)(f.stamp_block - which * 1000000);
-      }
-      return 0;
-    };
-    if (int rc = sweep_stamps(1)) return rc;
-    if (min3) {
-      if (int rc = timed([&] { return launch_sweep_min(f.ks, filter_groups_per_wave(f.ks, 0), m, s); })) return rc;
-      if (int rc = sweep_stamps(2)) return rc;
-      m.tile0 = c2;
-      m.tile1 = f.ntiles32;
-      m.qF = f.pqF[1].p;
-      m.tlo = f.ptlo[1].as<float>();
-      m.thi = f.pthi[1].as<float>();
-      m.qmap = f.pmap[1].as<int>();
-      m.qmin = f.pmin2.as<int>();
-      m.nslots_dev = f.png.as<unsigned>() + 3;
-      m.cq = f.pqF[0].p;
-      m.ctlo = f.ptlo[0].as<float>();
-      m.cthi = f.pthi[0].as<float>();
-      m.cmap = f.pmap[0].as<int>();
-      m.cmin = nullptr;
-      m.ccount = f.png.as<unsigned>() + 4;
-      m.last = 1;
-    }
-    // four query groups per wave here too: with the min-only loop the narrow form (two groups, twice the waves) that paid for
-    // k_sweep's second range loses (0.080 against 0.085-0.088 ms; profiles/r04_first_range_ab.jsonl)
-    if (int rc = timed([&] { return launch_sweep_min(f.ks, filter_groups_per_wave(f.ks, 0), m, s); })) return rc;
-    // the uncertain set: band pairs, exact whitening, exact distances -- one launch; the ellipsoid band rides along
-    UncertainArgs ua{};
-    ua.refF = opF;
-    ua.ntiles32 = f.ntiles32;
-    ua.qF = f.pqF[usrc].p;
-    ua.thi = f.pthi[usrc].as<float>();
-    ua.qmap = f.pmap[usrc].as<int>();
-    ua.nslots_dev = f.png.as<unsigned>() + (min3 ? 4 : 3);
-    ua.pts = xs->pts;
-    ua.d = d;
-    ua.dp = dp;
-    ua.lay_ctr = xs->lay_ctr;
-    ua.T8 = xs->T8;
-    ua.ldt8 = xs->ldt;
-    ua.refR = opR;
-    ua.n = n;
-    ua.r2 = r2;
-    ua.best = f.best.as<int>();
-    ua.counters = f.counters.as<unsigned>();
-    ua.seg_count = f.segcnt.as<unsigned>();
-    if (f.ell_pending) {   // the band proposals of k_prep4: trailing workgroups of this launch
-      ua.ell = f.ell_args;
-      f.ell_pending = false;
-    }
-    if (int rc = timed([&] { return launch_uncertain(f.ks, ua, s); })) return rc;
-    if (ev_after_filter) CK(hipEventRecord(ev_after_filter, s));
-    f.last_nsegs = (size_t)lw;
-  } else {
-  for (int ph = 0; ph < nphase; ++ph) {
-    fa.tile0 = (int)((long long)f.ntiles32 * ph / nphase);
-    fa.tile1 = (int)((long long)f.ntiles32 * (ph + 1) / nphase);
-    if (nphase == 2) {   // two ranges: the first takes filter_first_range_pct per cent of the tiles
-      const int cut = (int)((long long)f.ntiles32 * opt(f, OPT_FIRST_RANGE_PCT) / 100);
-      const int c = cut < 4 ? 4 : (cut > f.ntiles32 - 4 ? f.ntiles32 - 4 : cut);
-      fa.tile0 = ph == 0 ? 0 : c;
-      fa.tile1 = ph == 0 ? c : f.ntiles32;
-    }
-    fa.append = ph > 0;
-    fa.seg_first_extra = filter_wave_count(f.ks, ngroups);   // segments beyond the first launch's own: for a narrow later range
-    fa.seg_extra = (narrow_tail && nphase > 1 && f.ks <= 4) ? filter_wave_count(f.ks, ngroups, narrow_tail) - fa.seg_first_extra : 0;
-    if (fa.seg_extra < 0) fa.seg_extra = 0;
-    fa.cq = nullptr;
-    if (fused && ph > 0) {   // the previous launch compacted its undecided queries into set (ph - 1) & 1
-      const int src = (ph - 1) & 1;
-      fa.qF = f.pqF[src].p;
-      fa.tlo = f.ptlo[src].as<float>();
-      fa.thi = f.pthi[src].as<float>();
-      fa.qmap = f.pmap[src].as<int>();
-      fa.ngroups_dev = f.png.as<unsigned>() + src;
-      if (fold_finish) {
-        fa.ngroups_dev = nullptr;
-        fa.nslots_dev = f.png.as<unsigned>() + 2;
-      }
-    }
-    if (fused && ph + 1 < nphase) {   // ... and this one compacts into set ph & 1
-      const int dst = ph & 1;
-      fa.cq = f.pqF[dst].p;
-      fa.ctlo = f.ptlo[dst].as<float>();
-      fa.cthi = f.pthi[dst].as<float>();
-      fa.cmap = f.pmap[dst].as<int>();
-      fa.ccount = f.png.as<unsigned>() + 2;
-      fa.ccap = (unsigned)nqpad;
-      fa.route = f.route.as<uint8_t>();
-    }
-    const bool time_launch = ev_after_filter || opt(f, OPT_TIME_LAUNCHES);
-    if (time_launch) {   // timed call: bracket the matrix kernel itself (the compaction kernels stay outside)
-      while (f.kev.size() < f.kev_used + 2) {
-        hipEvent_t e;
-        CK(hipEventCreate(&e));
-        f.kev.push_back(e);
-      }
-      CK(hipEventRecord(f.kev[f.kev_used], s));
-    }
-    const int narrow = (f.ks <= 4 && ph > 0) ? narrow_tail : 0;
-    if (own_recheck) {   // the sweeping waves re-check their own segments; the first launch carries the ellipsoid band
-      fa.append = 0;
-      fa.seg_extra = 0;
-      fa.rw.ell = EllExactArgs{};
-      if (ph == 0 && f.ell_pending) {
-        fa.rw.ell = f.ell_args;
-        f.ell_pending = false;
-      }
-    }
-    CK(launch_filter(f.ks, fa, out_idx != nullptr, s, narrow));
-    if (time_launch) {
-      CK(hipEventRecord(f.kev[f.kev_used + 1], s));
-      f.kev_used += 2;
-    }
-    if (fa.cq && !fold_finish) {
-      const int dst = ph & 1;
-      launch_phase_finish(fa.cq, fa.ctlo, fa.cthi, fa.cmap, fa.ccount, f.png.as<unsigned>() + dst, f.ks, s);
-      CK(hipGetLastError());
-    }
-  }
-  if (ev_after_filter) CK(hipEventRecord(ev_after_filter, s));
-  const int any_narrow = (f.ks <= 4 && nphase > 1) ? narrow_tail : 0;
-  long long nsegs_all = filter_wave_count(f.ks, ngroups, any_narrow);
-  if (nsegs_all < filter_wave_count(f.ks, ngroups)) nsegs_all = filter_wave_count(f.ks, ngroups);
-  if (fa.split > 1) nsegs_all = (filter_wave_count(f.ks, ngroups) + 3) / 4 * 4 * fa.split;
-  f.last_nsegs = (size_t)nsegs_all;
-  }   // k_sweep / k_filter phases
-  long long nsegs_all = f.last_nsegs;
-  if (own_recheck || min_path) {
-    // nothing left to do here: every sweeping wave has re-checked its own pairs
-  } else if (xs) {   // no whitened coordinates were stored: the re-check whitens the queries of its pairs itself
-    RecheckWArgs rw{};
-    rw.list = f.list.as<unsigned long long>();
-    rw.seg_cap = cap;
-    rw.seg_count = f.segcnt.as<unsigned>();
-    rw.nsegs = nsegs_all;
-    rw.unit_cap = (unsigned)(nphase * (f.ks <= 4 ? 4 : (f.ks <= 8 ? 2 : 1)) * 32);   // queries per filter wave, all phases (a narrow later range has fewer)
-    rw.refR = opR;
-    rw.n = n;
-    rw.d = d;
-    rw.dp = dp;
-    rw.pts = xs->pts;
-    rw.nq = nq;
-    rw.lay_ctr = xs->lay_ctr;
-    rw.T64 = xs->T64;
-    rw.r2 = r2;
-    rw.best = f.best.as<int>();
-    if (f.ell_pending) {   // the band proposals of k_prep4 are decided by the last waves of this launch (before the finalise)
-      rw.ell = f.ell_args;
-      f.ell_pending = false;
-    }
-    launch_recheck_whiten(rw, s);
-    CK(hipGetLastError());
-  } else {
-    RecheckArgs ra{};
-    ra.list = f.list.as<unsigned long long>();
-    ra.seg_cap = cap;
-    ra.seg_count = f.segcnt.as<unsigned>();
-    ra.refR = opR;
-    ra.n = n;
-    ra.d = d;
-    ra.dp = dp;
-    ra.q = q;
-    ra.ldq = ldq;
-    ra.ldk = ldk;
-    ra.nq = nq;
-    ra.r2 = r2;
-    ra.best = f.best.as<int>();
-    launch_recheck(ra, nsegs_all, s);
-    CK(hipGetLastError());
-  }
-  // answers of the filtered queries + the gate of the exact scan that follows: (a) queries that do not
-  // fit binary16 and (b) every filtered query if the uncertain-pair list overflowed
-  if (!xs)
-    launch_filter_finalize(f.route.as<uint8_t>(), f.best.as<int>(), f.counters.as<unsigned>(), nq, out_mask,
-                           out_idx, f.gate2.as<uint8_t>(), s);
-  {
-    ScanArgs a{};
-    a.refT = refT;
-    a.n = n;
-    a.npad = npad;
-    a.ntiles = npad / kWave;
-    a.q = q;
-    a.ldq = ldq;
-    a.ldk = ldk;
-    a.nq = nq;
-    a.d = d;
-    a.r2 = r2;
-    a.mode = out_idx ? SCAN_FIRST : SCAN_MASK;
-    a.gate = f.gate2.as<uint8_t>();
-    a.out_idx = out_idx;
-    a.out_mask = out_mask;
-    a.only_gated = 1;   // leave the outputs of ungated queries alone
-    if (xs) {   // the finalise work rides in the scan launch; its gate is the routing itself; the (rare) workgroups
-                // that do scan whiten their own queries
-      a.q = xs->pts;
-      a.ldq = d;
-      a.ldk = 1;
-      a.raw_ctr = xs->lay_ctr;
-      a.raw_T8 = xs->T8;
-      a.raw_ldt = xs->ldt;
-      a.route = f.route.as<uint8_t>();
-      a.counters = f.counters.as<unsigned>();
-      a.fin_best = f.best.as<int>();
-      a.any_flag = f.misc.as<unsigned>() + 2 + f.batch_parity;
-      a.fin_reset = f.misc.as<unsigned>() + 2 + (f.batch_parity ^ 1u);
-      if (fold_finish) {
-        a.fin_slots = f.png.as<unsigned>() + 2;
-        a.fin_groups = f.png.as<unsigned>();   // where k_phase_finish would have left the group count (debug_stats)
-        if (min_path) a.fin_slots2 = f.png.as<unsigned>() + (min3 ? 4 : 3);
-        if (min3) a.fin_slots3 = f.png.as<unsigned>() + 3;
-      }
-    }
-    CK(launch_scan(dp, a, s));
-  }
-  CK(hipGetLastError());
-  // only a PHASED batch's scan tail (or its k_phase_finish) returns the slot counters to zero: a single-sweep batch that
-  // follows a failed phased one must leave the flag standing for the next phased batch (ADVICE r5)
-  if (nphase > 1) f.png_dirty = false;
-  return 0;
-}
-
-int scan_host(const double *apts, size_t na, const double *bpts, size_t nb, size_t d, double r2,
-              int mode, int64_t *out) {
-  if (int rc = check_dims(d)) return rc;
-  if (nb == 0) return 0;
-  if (!bpts || !out || (na && !apts)) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (na == 0) {  // the reference loops over zero live points
-    for (size_t j = 0; j < nb; ++j) out[j] = mode == SCAN_FIRST ? -1 : 0;
-    return 0;
-  }
-  if (int rc = ensure_ctx()) return rc;
-  Ctx &c = g_ctx;
-  const int dp = pick_dp((int)d);
-  const int npad = round_up((int)na, kWave);
-  if (int rc = stage_live_points(apts, na, d, dp, npad, false)) return rc;
-  if (int rc = upload(c.q, bpts, nb * d * sizeof(double), c.stream)) return rc;
-  CK(c.out.reserve(nb * sizeof(long long)));
-  ScanArgs a{};
-  a.refT = c.refT.as<double>();
-  a.n = (int)na;
-  a.npad = npad;
-  a.ntiles = npad / kWave;
-  a.q = c.q.as<double>();
-  a.ldq = (long long)d;
-  a.nq = (long long)nb;
-  a.d = (int)d;
-  a.r2 = r2;
-  a.mode = mode;
-  a.out_idx = c.out.as<long long>();
-  bool filtered = false;
-  // The stateless call pays the filter's live-point preparation every time and first-index mode keeps sweeping after
-  // a hit, so the pre-filter only pays for larger batches than in the resident mask path (measured at N = 4000,
-  // d = 50: exact scan 0.23-0.35 ms against 0.45-1.05 ms at 4000 queries; break-even between 16000 and 50000)
-  const long long host_min = opt(c.filter, OPT_MIN_QUERIES) != kFilterMinQueriesDefault ? opt(c.filter, OPT_MIN_QUERIES) : 32768;
-  if (mode == SCAN_FIRST && opt(c.filter, OPT_FILTER) && (long long)nb >= host_min && na >= 256) {
-    if (int rc = filter_prepare_refs(c.filter, c.refR.as<double>(), (int)na, (int)d, dp, c.stream, true)) return rc;
-    if (filter_applies(c.filter, (long long)nb, r2)) {
-      if (int rc = filter_run(c.filter, c.refT.as<double>(), c.refR.as<double>(), (int)na, npad, (int)d, dp,
-                              c.q.as<double>(), (long long)d, 1, (long long)nb, r2, nullptr, nullptr,
-                              c.out.as<long long>(), c.stream, false))
-        return rc;
-      filtered = true;
-    }
-  }
-  if (!filtered) CK(launch_scan(dp, a, c.stream));
-  CK(hipMemcpyAsync(out, c.out.p, nb * sizeof(long long), hipMemcpyDefault, c.stream));   // host or device destination
-  CK(hipStreamSynchronize(c.stream));
-  return 0;
-}
-
-int prep_consts(DevBuf &ctr_b, DevBuf &mat_b, const double *ctr, const double *mat, int d, int dp,
-                bool transpose, hipStream_t s) {
-  std::vector<double> pc = pad_vector(ctr, d, dp);
-  std::vector<double> pm = pad_matrix(mat, d, dp, transpose);
-  if (int rc = upload(ctr_b, pc.data(), pc.size() * sizeof(double), s)) return rc;
-  if (int rc = upload(mat_b, pm.data(), pm.size() * sizeof(double), s)) return rc;
-  if (!arena_active()) CK(hipStreamSynchronize(s));  // host vectors go out of scope
   return 0;
 }
 
@@ -979,6 +461,604 @@ struct mlf_region {
 };
 
 namespace {
+
+// The live points an exact test runs against: refT / refR as stage_live_points lays them out
+struct LiveSet {
+  const double *refT, *refR;
+  int n, npad, d, dp;
+  double r2;
+};
+
+LiveSet region_live(const mlf_region *r) { return {r->refT.as<double>(), r->refR.as<double>(), r->n, r->npad, r->d, r->dp, r->r2}; }
+
+// The routing of one batch of nq rows.  `r` is null for BATCH_HOST (the stateless call: live set of host_nlive rows);
+// first_index: the first neighbour's index per row instead of the membership mask; pregate: the gate array arrives with
+// a pre-gate (device-side sampling: the cube test); pts: the rows on the device (the bounded stage reads 16-byte pieces).
+BatchPlan plan_batch(const FilterCtx &f, const mlf_region *r, BatchKind kind, long long nq, double r2, bool first_index = false,
+                     bool pregate = false, const void *pts = nullptr, size_t host_nlive = 0) {
+  BatchPlan p{};
+  p.time_launches = opt(f, OPT_TIME_LAUNCHES) != 0;
+  const bool scan = kind == BATCH_HOST || kind == BATCH_TSPACE || (kind == BATCH_INSIDE && r->use_scan);
+  // host-side eligibility of the filter (the kernels re-check per query and fall back on their own)
+  bool eligible = opt(f, OPT_FILTER) && f.refs_ready && f.usable && nq >= opt(f, OPT_MIN_QUERIES);
+  // below ~2000 proposals the five launches of the filter path (~45 us) only pay when the exact scan has real work:
+  // 400 proposals against 400 x 5 live coordinates take 43 us through the exact scan, 51 us through the filter
+  if (opt(f, OPT_MIN_QUERIES) == kFilterMinQueriesDefault && nq < 2048 && (long long)f.ntiles32 * 32 * f.ks * 16 < 40000) eligible = false;
+  const double sr2 = f.sigma * f.sigma * r2;
+  eligible = eligible && r2 > 0.0 && r2 < 1e150 && sr2 < 4096.0 && sr2 > 1e-30;
+  if (kind == BATCH_HOST) {
+    // The stateless call pays the filter's live-point preparation every time and first-index mode keeps sweeping after
+    // a hit, so the pre-filter only pays for larger batches than in the resident mask path (measured at N = 4000,
+    // d = 50: exact scan 0.23-0.35 ms against 0.45-1.05 ms at 4000 queries; break-even between 16000 and 50000)
+    const long long host_min = opt(f, OPT_MIN_QUERIES) != kFilterMinQueriesDefault ? opt(f, OPT_MIN_QUERIES) : 32768;
+    p.host_refs = first_index && opt(f, OPT_FILTER) && nq >= host_min && host_nlive >= 256;
+    p.filter = p.host_refs && eligible;
+  } else {
+    p.filter = scan && eligible;
+  }
+  if (kind == BATCH_INSIDE || kind == BATCH_GATE) {
+    // fused stage (coalesced staging, coordinate-major output, optional quantisation) for affine layers
+    const bool fused = r->layer_kind == 0 && opt(f, OPT_FUSED_PREP) && prep3_usable(r->d) && r->chol_ready;
+    const bool bounded = fused && opt(f, OPT_PREP_BOUNDED) && r->p4_ready && !r->has_wrap && (p.filter || !scan) &&
+                         nq < 0x7fffffffll && (reinterpret_cast<uintptr_t>(pts) & 15) == 0;   // 16-byte pieces
+    if (bounded)
+      p.stage = STAGE_PREP4;
+    else if (kind == BATCH_GATE)
+      p.stage = STAGE_PREP;   // the binary64 ellipsoid test alone
+    else if (fused)
+      p.stage = STAGE_PREP3;
+    else if (r->layer_kind == 0 && prep64_usable(r->d) && r->chol_ready && r->chol_ok && opt(f, OPT_FUSED_PREP))
+      p.stage = STAGE_PREP64;
+    else
+      p.stage = STAGE_PREP;
+  }
+  if (!p.filter) return p;
+  // mask mode sweeps the centre-first copy of the live points (any hit decides); the first-index mode keeps storage order
+  p.ordered = !first_index && f.ordered && opt(f, OPT_ORDER);
+  const bool bounded = p.stage == STAGE_PREP4;
+  // The batch sizes of a real run (ndraw 128 ... 65536): per-proposal stage, sweep, re-check and answers in ONE launch
+  // (mlf_mid.hip); the exact-scan launch behind it only works if a proposal was routed to it.
+  p.mid = bounded && !pregate && !first_index && f.ks <= 4 && mid_usable(r->dp) && nq <= opt(f, OPT_MID_MAX);
+  if (p.mid) return p;
+  // Phased sweep: the live-point tiles are split into nphase ranges; after each range the queries that are decided
+  // (certain hit) leave, the rest is compacted into fresh 32-query groups.  Worth it when the sweep is long compared with
+  // one compaction (~25 us + 40 us per 10^6 queries).
+  const int want_phases = (int)opt(f, OPT_PHASES);
+  const long long phase_min = opt(f, OPT_PHASE_MIN_QUERIES);
+  if (want_phases && nq >= phase_min && (phase_min < 32768 || nq * f.ntiles32 >= 30000000ll))
+    p.nphase = want_phases >= 2 ? (want_phases <= f.ntiles32 / 4 ? want_phases : (f.ntiles32 >= 16 ? 2 : 1))
+                                : (f.ntiles32 >= 16 ? 2 : 1);
+  p.narrow = (p.nphase > 1 && f.ks <= 4) ? (int)opt(f, OPT_NARROW_TAIL) : 0;
+  const long long ngroups = (nq + 31) / 32;
+  p.split = p.nphase == 1 ? filter_tile_split(f.ks, ngroups, f.ntiles32, (int)opt(f, OPT_SPLIT_WAVES)) : 1;
+  // mask mode behind the bounded per-proposal stage, single-sweep batches (below ~262144 proposals at N = 4000): the
+  // re-check (binary64 whitening of the queries of the uncertain pairs + the reference's distance loop) runs inside the
+  // sweep launch, each wave on the segment it has just written, and the ellipsoid band rides in the same launch: three
+  // launches per batch instead of four (131072 proposals: 104 -> 96 us).  Phased sweeps keep the separate re-check launch:
+  // there the waves' re-check tails cost more than the launch they save (10^6: 0.473 -> 0.51 ms)
+  p.own_recheck = bounded && !first_index && p.nphase == 1;
+  // two ranges, compaction inside the first, finalise tail in the scan launch: nobody pads the compacted set or publishes
+  // its group count (k_phase_finish: a 5 us launch) -- the second range reads the slot counter itself, the tail resets it
+  p.fold_finish = bounded && p.nphase == 2;
+  // Two ranges in mask mode behind the bounded per-proposal stage: the min-only sweep (mlf_sweepmin.hip).  The two long
+  // launches carry the running minimum only; the queries whose minimum ends in the band are swept once more by
+  // k_uncertain (band pairs found, queries whitened, pairs decided in one launch), which also carries the ellipsoid band.
+  p.min_path = p.fold_finish && !first_index && f.ks <= 4 && opt(f, OPT_SWEEP_MIN);
+  // Tile ranges, every range at least 4 tiles.  Two ranges: [0, c1) [c1, ntiles32) with c1 = first_pct of the tiles.  Three
+  // (min-only sweep) -- batches of at least min_work (proposals x tiles), where the pairs a third range saves outweigh its
+  // launch and its compaction: the last range starts at c2 = second_pct of the tiles and [0, c2) is split at first_pct of
+  // c2 (30 % of 50 % = 15 %, 50 %: profiles/r05_three_range_ab.jsonl).
+  if (p.nphase == 2) {
+    const int nt = f.ntiles32, first_pct = (int)opt(f, OPT_FIRST_RANGE_PCT), second_pct = (int)opt(f, OPT_SECOND_RANGE_PCT);
+    const int cut = (int)((long long)nt * first_pct / 100);
+    p.cut[0] = cut < 4 ? 4 : (cut > nt - 4 ? nt - 4 : cut);
+    if (p.min_path && second_pct > 0 && nq * nt >= opt(f, OPT_THIRD_MIN_WORK)) {
+      const int cut2 = (int)((long long)nt * second_pct / 100);
+      int a = (int)((long long)cut2 * first_pct / 100);
+      a = a < 4 ? 4 : a;
+      if (cut2 >= a + 4 && cut2 <= nt - 4) {
+        p.cut[0] = a;
+        p.cut[1] = cut2;
+      }
+    }
+  }
+  // large batches on the min-only path: the per-proposal stage runs inside the first sweep launch (mlf_fused.hip)
+  p.defer = p.min_path && opt(f, OPT_FUSED_FIRST) && fused_usable(r->dp);
+  if (p.defer) {
+    p.fused_waves = (int)opt(f, OPT_FUSED_WAVES);
+    p.fused_variant = (unsigned)(opt(f, OPT_FUSED_VARIANT) & 0xff);
+    if (!(r->same_matrix && r->same_centres)) p.fused_variant &= ~2u;   // the region does not have the same quadratic form
+    if (pregate) p.fused_variant |= 4u;   // the pre-gate is read out of the gate array
+  }
+  const long long waves = filter_wave_count(f.ks, ngroups);
+  if (p.min_path)
+    p.nsegs = uncertain_blocks();
+  else if (p.split > 1)   // one segment per (wave, range), whole workgroups
+    p.nsegs = (waves + 3) / 4 * 4 * p.split;
+  else   // a narrow later range has more waves than the first
+    p.nsegs = std::max(waves, filter_wave_count(f.ks, ngroups, p.narrow));
+  p.seg_room = std::max(p.nsegs, (waves + 3) / 4 * 4 * p.split);   // the padding waves of a grid write (empty) segments too
+  return p;
+}
+
+// Device buffers of one filtered batch.
+int filter_reserve(FilterCtx &f, const BatchPlan &p, long long nq) {
+  const long long nqpad = (nq + 31) / 32 * 32;
+  CK(f.qF.reserve((size_t)nqpad * f.ks * 16 * 2));
+  CK(f.tlo.reserve((size_t)nqpad * sizeof(float)));
+  CK(f.thi.reserve((size_t)nqpad * sizeof(float)));
+  CK(f.route.reserve((size_t)nq));
+  CK(f.best.reserve((size_t)nq * sizeof(int)));
+  CK(f.counters.reserve(4 * sizeof(unsigned)));
+  CK(f.list.reserve((size_t)p.seg_room * kFilterSegCap * sizeof(unsigned long long)));
+  CK(f.segcnt.reserve((size_t)p.seg_room * sizeof(unsigned)));
+  CK(f.gate2.reserve((size_t)nq));
+  return misc_reserve(f);
+}
+
+// Where the exact whitened coordinates come from when the per-proposal stage did not store them (k_prep4): the proposals
+// themselves and the layer; the queries that need coordinates are whitened after the sweeps.  Also what the stage hands
+// over to the launches behind it.
+struct ExactSrc {
+  const double *pts;
+  const double *lay_ctr;
+  const double *T8;   // row-major layer matrix, row stride ldt
+  int ldt;
+  const double *T64;  // the same as 64 x 64, zero padded (d <= 64)
+  Prep4Args prep;     // plan.defer: the per-proposal stage, run inside the first sweep launch
+  Prep4Consts same;   // its constants in the "same quadratic form" variant (plan.fused_variant bit 1; region_prep4_setup)
+  EllExactArgs ell;   // the ellipsoid band, decided by the trailing waves of a later launch (count == nullptr: none)
+};
+
+ExactSrc region_exact_src(const mlf_region *r, const double *pts) {
+  ExactSrc x{};
+  x.pts = pts;
+  x.lay_ctr = r->lay_ctr.as<double>();
+  x.T8 = r->lay_T8.as<double>();
+  x.ldt = (r->dp + 7) / 8 * 8;
+  x.T64 = r->lay_T64.as<double>();
+  return x;
+}
+
+// One filtered batch: query element (j, k) is q[j*ldq + k*ldk]; answers for all nq queries in out_mask (bytes) and/or out_idx
+struct FilterBatch {
+  FilterCtx &f;
+  const BatchPlan &p;
+  LiveSet L;
+  const double *q;
+  long long ldq, ldk, nq;
+  const uint8_t *gate;     // queries not quantised by the per-proposal stage: the gate their quantisation honours
+  uint8_t *out_mask;
+  long long *out_idx;
+  hipStream_t s;
+  hipEvent_t ev_after;     // recorded behind the last matrix launch (stage events of a timed call)
+  const ExactSrc *xs;      // plan.stage == STAGE_PREP4, else null
+  const void *opF() const { return p.ordered ? f.refFm.p : f.refF.p; }
+  const double *opR() const { return p.ordered ? f.refRm.as<double>() : L.refR; }
+  long long ngroups() const { return (nq + 31) / 32; }
+};
+
+// exact scan of nq rows (element (j, k) at q[j*ldq + k*ldk]) against the live set
+ScanArgs scan_args(const LiveSet &L, const double *q, long long ldq, long long ldk, long long nq, int mode) {
+  ScanArgs a{};
+  a.refT = L.refT;
+  a.n = L.n;
+  a.npad = L.npad;
+  a.ntiles = L.npad / kWave;
+  a.q = q;
+  a.ldq = ldq;
+  a.ldk = ldk;
+  a.nq = nq;
+  a.d = L.d;
+  a.r2 = L.r2;
+  a.mode = mode;
+  return a;
+}
+
+// The finalise work of a batch behind the bounded stage rides in its exact-scan launch: the gate is the routing itself
+// (route 2: proposals the pre-filter cannot take), the launch is idle unless the batch's flag is up, and the (rare)
+// workgroups that do scan whiten their own queries
+void scan_finalise(ScanArgs &a, const FilterCtx &f, const ExactSrc &xs) {
+  a.only_gated = 1;   // leave the outputs of ungated queries alone
+  a.raw_ctr = xs.lay_ctr;
+  a.raw_T8 = xs.T8;
+  a.raw_ldt = xs.ldt;
+  a.route = f.route.as<uint8_t>();
+  a.counters = f.counters.as<unsigned>();
+  a.any_flag = f.misc.as<unsigned>() + 2 + f.batch_parity;
+  a.fin_reset = f.misc.as<unsigned>() + 2 + (f.batch_parity ^ 1u);
+}
+
+// a matrix-kernel launch of a timed call, bracketed by an event pair (mlf_region_timing_filter_launches)
+template <class Launch>
+int timed_launch(const FilterBatch &b, Launch &&launch) {
+  FilterCtx &f = b.f;
+  const bool timed = b.ev_after || b.p.time_launches;
+  if (timed) {
+    while (f.kev.size() < f.kev_used + 2) {
+      hipEvent_t e;
+      CK(hipEventCreate(&e));
+      f.kev.push_back(e);
+    }
+    CK(hipEventRecord(f.kev[f.kev_used], b.s));
+  }
+  CK(launch());
+  if (timed) {
+    CK(hipEventRecord(f.kev[f.kev_used + 1], b.s));
+    f.kev_used += 2;
+  }
+  return 0;
+}
+
+// The min-only sweep in two or three ranges, then k_uncertain on the queries whose minimum ended in the band.
+// filter_second_range_pct > 0: three ranges (the middle one reads set 0 and writes set 1 with a second array of minima;
+// the uncertain set then reuses set 0's arrays, which nobody reads any more)
+int filter_sweep_min(const FilterBatch &b) {
+  FilterCtx &f = b.f;
+  const BatchPlan &p = b.p;
+  const ExactSrc &xs = *b.xs;
+  const long long nqpad = b.ngroups() * 32;
+  const bool min3 = p.cut[1] > 0;
+  CK(f.segcnt.reserve((size_t)(p.nsegs + 8) * sizeof(unsigned)));
+  CK(f.pmin.reserve((size_t)nqpad * sizeof(int)));
+  if (min3) CK(f.pmin2.reserve((size_t)nqpad * sizeof(int)));
+  MinArgs m{};
+  m.refF = b.opF();
+  m.ntiles32 = f.ntiles32;
+  m.nq = b.nq;
+  m.best = f.best.as<int>();
+  m.ngroups = b.ngroups();
+  m.ccap = (unsigned)nqpad;
+  // first range: slot = query; the queries without a certain hit go to set 0 with their minimum
+  m.tile0 = 0;
+  m.tile1 = p.cut[0];
+  m.qF = f.qF.p;
+  m.tlo = f.tlo.as<float>();
+  m.thi = f.thi.as<float>();
+  m.cq = f.pqF[0].p;
+  m.ctlo = f.ptlo[0].as<float>();
+  m.cthi = f.pthi[0].as<float>();
+  m.cmap = f.pmap[0].as<int>();
+  m.cmin = f.pmin.as<int>();
+  m.ccount = f.png.as<unsigned>() + 2;
+  m.last = 0;
+  if (p.defer) {   // per-proposal stage + first range in one launch: the operand never leaves the registers
+    FusedArgs fu{};
+    fu.p = xs.prep;
+    fu.refF = b.opF();
+    fu.ntiles32 = f.ntiles32;
+    fu.tile0 = 0;
+    fu.tile1 = p.cut[0];
+    fu.cq = m.cq;
+    fu.ctlo = m.ctlo;
+    fu.cthi = m.cthi;
+    fu.cmap = m.cmap;
+    fu.cmin = m.cmin;
+    fu.ccount = m.ccount;
+    fu.ccap = m.ccap;
+    if (f.stamp_block >= 0 && f.stamp_block < 1000000) {   // diagnostics (mlf_region_debug_fused_stamps)
+      CK(f.fstamps.reserve(16 * sizeof(unsigned long long)));
+      fu.stamps = f.fstamps.as<unsigned long long>();
+      fu.stamp_block = (unsigned)f.stamp_block;
+    }
+    fu.variant = p.fused_variant;
+    if (fu.variant & 2u) fu.p.c = xs.same;
+    if (int rc = timed_launch(b, [&] { return launch_prep_sweep(fu, b.s, p.fused_waves); })) return rc;
+  } else if (int rc = timed_launch(b, [&] { return launch_sweep_min(f.ks, filter_groups_per_wave(f.ks, 0), m, b.s); })) {
+    return rc;
+  }
+  // next range: set 0 with its minima.  Two ranges: this is the last, the uncertain queries go to set 1.  Three: the
+  // queries still without a certain hit go to set 1 with their minima, and the last range sweeps those into set 0's arrays
+  const int usrc = min3 ? 0 : 1;   // the set that holds the uncertain queries in the end
+  m.tile0 = p.cut[0];
+  m.tile1 = min3 ? p.cut[1] : f.ntiles32;
+  m.qF = f.pqF[0].p;
+  m.tlo = f.ptlo[0].as<float>();
+  m.thi = f.pthi[0].as<float>();
+  m.qmap = f.pmap[0].as<int>();
+  m.qmin = f.pmin.as<int>();
+  m.nslots_dev = f.png.as<unsigned>() + 2;
+  m.cq = f.pqF[1].p;
+  m.ctlo = f.ptlo[1].as<float>();
+  m.cthi = f.pthi[1].as<float>();
+  m.cmap = f.pmap[1].as<int>();
+  m.cmin = min3 ? f.pmin2.as<int>() : nullptr;
+  m.ccount = f.png.as<unsigned>() + 3;
+  m.last = min3 ? 0 : 1;
+  // diagnostics: stage stamps of one k_sweep_min workgroup -- block 1 000 000 + b: the launch that follows the first range,
+  // 2 000 000 + b: the one after it
+  auto sweep_stamps = [&](int which) -> int {
+    m.stamps = nullptr;
+    if (f.stamp_block >= which * 1000000 && f.stamp_block < (which + 1) * 1000000) {
+      CK(f.fstamps.reserve(16 * sizeof(unsigned long long)));
+      m.stamps = f.fstamps.as<unsigned long long>();
+      m.stamp_block = (unsigned)(f.stamp_block - which * 1000000);
+    }
+    return 0;
+  };
+  if (int rc = sweep_stamps(1)) return rc;
+  if (min3) {
+    if (int rc = timed_launch(b, [&] { return launch_sweep_min(f.ks, filter_groups_per_wave(f.ks, 0), m, b.s); })) return rc;
+    if (int rc = sweep_stamps(2)) return rc;
+    m.tile0 = p.cut[1];
+    m.tile1 = f.ntiles32;
+    m.qF = f.pqF[1].p;
+    m.tlo = f.ptlo[1].as<float>();
+    m.thi = f.pthi[1].as<float>();
+    m.qmap = f.pmap[1].as<int>();
+    m.qmin = f.pmin2.as<int>();
+    m.nslots_dev = f.png.as<unsigned>() + 3;
+    m.cq = f.pqF[0].p;
+    m.ctlo = f.ptlo[0].as<float>();
+    m.cthi = f.pthi[0].as<float>();
+    m.cmap = f.pmap[0].as<int>();
+    m.cmin = nullptr;
+    m.ccount = f.png.as<unsigned>() + 4;
+    m.last = 1;
+  }
+  // four query groups per wave here too: with the min-only loop the narrow form (two groups, twice the waves) that paid for
+  // k_sweep's second range loses (0.080 against 0.085-0.088 ms; profiles/r04_first_range_ab.jsonl)
+  if (int rc = timed_launch(b, [&] { return launch_sweep_min(f.ks, filter_groups_per_wave(f.ks, 0), m, b.s); })) return rc;
+  // the uncertain set: band pairs, exact whitening, exact distances -- one launch; the ellipsoid band rides along
+  UncertainArgs ua{};
+  ua.refF = b.opF();
+  ua.ntiles32 = f.ntiles32;
+  ua.qF = f.pqF[usrc].p;
+  ua.thi = f.pthi[usrc].as<float>();
+  ua.qmap = f.pmap[usrc].as<int>();
+  ua.nslots_dev = f.png.as<unsigned>() + (min3 ? 4 : 3);
+  ua.pts = xs.pts;
+  ua.d = b.L.d;
+  ua.dp = b.L.dp;
+  ua.lay_ctr = xs.lay_ctr;
+  ua.T8 = xs.T8;
+  ua.ldt8 = xs.ldt;
+  ua.refR = b.opR();
+  ua.n = b.L.n;
+  ua.r2 = b.L.r2;
+  ua.best = f.best.as<int>();
+  ua.counters = f.counters.as<unsigned>();
+  ua.seg_count = f.segcnt.as<unsigned>();
+  ua.ell = xs.ell;   // the band proposals of k_prep4: trailing workgroups of this launch
+  if (int rc = timed_launch(b, [&] { return launch_uncertain(f.ks, ua, b.s); })) return rc;
+  if (b.ev_after) CK(hipEventRecord(b.ev_after, b.s));
+  return 0;
+}
+
+// Re-check of the uncertain pairs behind the bounded stage: the queries of the pairs are whitened from the proposals, and
+// the ellipsoid band of the stage rides in the same launch
+RecheckWArgs recheck_w_args(const FilterBatch &b) {
+  RecheckWArgs rw{};
+  rw.list = b.f.list.as<unsigned long long>();
+  rw.seg_cap = kFilterSegCap;
+  rw.seg_count = b.f.segcnt.as<unsigned>();
+  rw.refR = b.opR();
+  rw.n = b.L.n;
+  rw.d = b.L.d;
+  rw.dp = b.L.dp;
+  rw.pts = b.xs->pts;
+  rw.nq = b.nq;
+  rw.lay_ctr = b.xs->lay_ctr;
+  rw.T64 = b.xs->T64;
+  rw.r2 = b.L.r2;
+  rw.best = b.f.best.as<int>();
+  rw.ell = b.xs->ell;
+  return rw;
+}
+
+// k_sweep (mask mode) / k_filter (first index) over the plan's ranges; every launch is sized for the worst case and reads
+// the actual group count from device memory: no host sync
+int filter_phases(const FilterBatch &b) {
+  FilterCtx &f = b.f;
+  const BatchPlan &p = b.p;
+  const long long ngroups = b.ngroups();
+  FilterArgs fa{};
+  fa.refF = b.opF();
+  fa.qF = f.qF.p;
+  fa.tlo = f.tlo.as<float>();
+  fa.thi = f.thi.as<float>();
+  fa.ntiles32 = f.ntiles32;
+  fa.ngroups = ngroups;
+  fa.nq = b.nq;
+  fa.best = f.best.as<int>();
+  fa.list = f.list.as<unsigned long long>();
+  fa.seg_cap = kFilterSegCap;
+  fa.seg_count = f.segcnt.as<unsigned>();
+  fa.counters = f.counters.as<unsigned>();
+  fa.split = p.split;
+  if (p.own_recheck) fa.rw = recheck_w_args(b);   // the sweeping waves re-check their own segments
+  const bool fused = p.nphase > 1;   // the compaction of the undecided queries rides in the matrix kernel's epilogue
+  for (int ph = 0; ph < p.nphase; ++ph) {
+    fa.tile0 = (int)((long long)f.ntiles32 * ph / p.nphase);
+    fa.tile1 = (int)((long long)f.ntiles32 * (ph + 1) / p.nphase);
+    if (p.nphase == 2) {   // two ranges: the first takes filter_first_range_pct per cent of the tiles
+      fa.tile0 = ph == 0 ? 0 : p.cut[0];
+      fa.tile1 = ph == 0 ? p.cut[0] : f.ntiles32;
+    }
+    fa.append = ph > 0;
+    fa.seg_first_extra = filter_wave_count(f.ks, ngroups);   // segments beyond the first launch's own: for a narrow later range
+    fa.seg_extra = p.narrow ? filter_wave_count(f.ks, ngroups, p.narrow) - fa.seg_first_extra : 0;
+    if (fa.seg_extra < 0) fa.seg_extra = 0;
+    fa.cq = nullptr;
+    if (fused && ph > 0) {   // the previous launch compacted its undecided queries into set (ph - 1) & 1
+      const int src = (ph - 1) & 1;
+      fa.qF = f.pqF[src].p;
+      fa.tlo = f.ptlo[src].as<float>();
+      fa.thi = f.pthi[src].as<float>();
+      fa.qmap = f.pmap[src].as<int>();
+      fa.ngroups_dev = f.png.as<unsigned>() + src;
+      if (p.fold_finish) {
+        fa.ngroups_dev = nullptr;
+        fa.nslots_dev = f.png.as<unsigned>() + 2;
+      }
+    }
+    if (fused && ph + 1 < p.nphase) {   // ... and this one compacts into set ph & 1
+      const int dst = ph & 1;
+      fa.cq = f.pqF[dst].p;
+      fa.ctlo = f.ptlo[dst].as<float>();
+      fa.cthi = f.pthi[dst].as<float>();
+      fa.cmap = f.pmap[dst].as<int>();
+      fa.ccount = f.png.as<unsigned>() + 2;
+      fa.ccap = (unsigned)(ngroups * 32);
+      fa.route = f.route.as<uint8_t>();
+    }
+    const int narrow = ph > 0 ? p.narrow : 0;
+    if (int rc = timed_launch(b, [&] { return launch_filter(f.ks, fa, b.out_idx != nullptr, b.s, narrow); })) return rc;
+    if (fa.cq && !p.fold_finish) {
+      const int dst = ph & 1;
+      launch_phase_finish(fa.cq, fa.ctlo, fa.cthi, fa.cmap, fa.ccount, f.png.as<unsigned>() + dst, f.ks, b.s);
+      CK(hipGetLastError());
+    }
+  }
+  if (b.ev_after) CK(hipEventRecord(b.ev_after, b.s));
+  return 0;
+}
+
+// the separate re-check launch of the uncertain pairs
+int filter_recheck(const FilterBatch &b) {
+  FilterCtx &f = b.f;
+  const BatchPlan &p = b.p;
+  if (b.xs) {   // no whitened coordinates were stored: the re-check whitens the queries of its pairs itself
+    RecheckWArgs rw = recheck_w_args(b);   // (the band proposals of k_prep4: the last waves of this launch, before the finalise)
+    rw.nsegs = p.nsegs;
+    rw.unit_cap = (unsigned)(p.nphase * (f.ks <= 4 ? 4 : (f.ks <= 8 ? 2 : 1)) * 32);   // queries per filter wave, all phases (a narrow later range has fewer)
+    launch_recheck_whiten(rw, b.s);
+  } else {
+    RecheckArgs ra{};
+    ra.list = f.list.as<unsigned long long>();
+    ra.seg_cap = kFilterSegCap;
+    ra.seg_count = f.segcnt.as<unsigned>();
+    ra.refR = b.opR();
+    ra.n = b.L.n;
+    ra.d = b.L.d;
+    ra.dp = b.L.dp;
+    ra.q = b.q;
+    ra.ldq = b.ldq;
+    ra.ldk = b.ldk;
+    ra.nq = b.nq;
+    ra.r2 = b.L.r2;
+    ra.best = f.best.as<int>();
+    launch_recheck(ra, p.nsegs, b.s);
+  }
+  CK(hipGetLastError());
+  return 0;
+}
+
+// answers of the filtered queries + the exact scan of the queries the filter did not decide: (a) queries that do not fit
+// binary16 and (b) every filtered query if the uncertain-pair list overflowed
+int filter_scan_tail(const FilterBatch &b) {
+  FilterCtx &f = b.f;
+  const BatchPlan &p = b.p;
+  const int mode = b.out_idx ? SCAN_FIRST : SCAN_MASK;
+  if (!b.xs)
+    launch_filter_finalize(f.route.as<uint8_t>(), f.best.as<int>(), f.counters.as<unsigned>(), b.nq, b.out_mask,
+                           b.out_idx, f.gate2.as<uint8_t>(), b.s);
+  ScanArgs a = b.xs ? scan_args(b.L, b.xs->pts, b.L.d, 1, b.nq, mode) : scan_args(b.L, b.q, b.ldq, b.ldk, b.nq, mode);
+  a.gate = f.gate2.as<uint8_t>();
+  a.out_idx = b.out_idx;
+  a.out_mask = b.out_mask;
+  a.only_gated = 1;   // leave the outputs of ungated queries alone
+  if (b.xs) {
+    scan_finalise(a, f, *b.xs);
+    a.fin_best = f.best.as<int>();
+    if (p.fold_finish) {
+      a.fin_slots = f.png.as<unsigned>() + 2;
+      a.fin_groups = f.png.as<unsigned>();   // where k_phase_finish would have left the group count (debug_stats)
+      if (p.min_path) a.fin_slots2 = f.png.as<unsigned>() + (p.cut[1] > 0 ? 4 : 3);
+      if (p.cut[1] > 0) a.fin_slots3 = f.png.as<unsigned>() + 3;
+    }
+  }
+  CK(launch_scan(b.L.dp, a, b.s));
+  CK(hipGetLastError());
+  return 0;
+}
+
+// Filter pipeline on device data along the plan's route
+int filter_run(const FilterBatch &b) {
+  FilterCtx &f = b.f;
+  const BatchPlan &p = b.p;
+  const long long nqpad = b.ngroups() * 32;
+  f.last = p;
+  if (p.min_path) f.last_min = p;
+  if (int rc = filter_reserve(f, p, b.nq)) return rc;
+  if (p.stage != STAGE_PREP4 && p.stage != STAGE_PREP3)   // the fused per-proposal stage has not quantised this batch
+    launch_quant_queries(b.q, b.ldq, b.nq, nqpad, b.L.d, b.L.dp, f.ks, f.stats.as<double>(), b.L.r2, b.gate, f.qF.p,
+                         f.tlo.as<float>(), f.thi.as<float>(), f.route.as<uint8_t>(), f.best.as<int>(),
+                         f.counters.as<unsigned>(), b.s);
+  CK(hipGetLastError());
+  if (p.nphase > 1) {   // two compacted query sets (ping-pong)
+    for (int i = 0; i < 2; ++i) {
+      CK(f.pqF[i].reserve((size_t)nqpad * f.ks * 16 * 2));
+      CK(f.ptlo[i].reserve((size_t)nqpad * sizeof(float)));
+      CK(f.pthi[i].reserve((size_t)nqpad * sizeof(float)));
+      CK(f.pmap[i].reserve((size_t)nqpad * sizeof(int)));
+    }
+    if (!f.png.p) {   // group counts + the slot counter of the fused compaction (returns to zero by itself: k_phase_finish)
+      // words: [0] groups after the first range, [1] size of the uncertain set (statistics of the last batch), [2] [3] [4] slot
+      // counters of the compacted sets, [5] groups after the second of three ranges
+      CK(f.png.reserve(8 * sizeof(unsigned)));
+      CK(hipMemset(f.png.p, 0, 8 * sizeof(unsigned)));
+    } else if (f.png_dirty) {   // an earlier phased batch failed between its first compaction and its scan launch (ADVICE r4)
+      CK(hipMemsetAsync(f.png.p, 0, 8 * sizeof(unsigned), b.s));
+    }
+    f.png_dirty = true;   // until the scan launch of this batch is queued
+  }
+  if (int rc = p.min_path ? filter_sweep_min(b) : filter_phases(b)) return rc;
+  // the min-only sweep and the single sweep behind the bounded stage have re-checked every pair in their own launches
+  if (!p.min_path && !p.own_recheck)
+    if (int rc = filter_recheck(b)) return rc;
+  if (int rc = filter_scan_tail(b)) return rc;
+  // only a PHASED batch's scan tail (or its k_phase_finish) returns the slot counters to zero: a single-sweep batch that
+  // follows a failed phased one must leave the flag standing for the next phased batch (ADVICE r5)
+  if (p.nphase > 1) f.png_dirty = false;
+  return 0;
+}
+
+int scan_host(const double *apts, size_t na, const double *bpts, size_t nb, size_t d, double r2,
+              int mode, int64_t *out) {
+  if (int rc = check_dims(d)) return rc;
+  if (nb == 0) return 0;
+  if (!bpts || !out || (na && !apts)) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (na == 0) {  // the reference loops over zero live points
+    for (size_t j = 0; j < nb; ++j) out[j] = mode == SCAN_FIRST ? -1 : 0;
+    return 0;
+  }
+  if (int rc = ensure_ctx()) return rc;
+  Ctx &c = g_ctx;
+  const int dp = pick_dp((int)d);
+  const int npad = round_up((int)na, kWave);
+  if (int rc = stage_live_points(apts, na, d, dp, npad, false)) return rc;
+  if (int rc = upload(c.q, bpts, nb * d * sizeof(double), c.stream)) return rc;
+  CK(c.out.reserve(nb * sizeof(long long)));
+  const LiveSet live{c.refT.as<double>(), c.refR.as<double>(), (int)na, npad, (int)d, dp, r2};
+  BatchPlan p = plan_batch(c.filter, nullptr, BATCH_HOST, (long long)nb, r2, mode == SCAN_FIRST, false, nullptr, na);
+  if (p.host_refs) {   // quantise the live points, then route with their statistics
+    if (int rc = filter_prepare_refs(c.filter, c.refR.as<double>(), (int)na, (int)d, dp, c.stream, true)) return rc;
+    p = plan_batch(c.filter, nullptr, BATCH_HOST, (long long)nb, r2, mode == SCAN_FIRST, false, nullptr, na);
+  }
+  if (p.filter) {
+    if (int rc = filter_run({c.filter, p, live, c.q.as<double>(), (long long)d, 1, (long long)nb, nullptr, nullptr,
+                             c.out.as<long long>(), c.stream, nullptr, nullptr}))
+      return rc;
+  } else {
+    ScanArgs a = scan_args(live, c.q.as<double>(), (long long)d, 0, (long long)nb, mode);
+    a.out_idx = c.out.as<long long>();
+    CK(launch_scan(dp, a, c.stream));
+  }
+  CK(hipMemcpyAsync(out, c.out.p, nb * sizeof(long long), hipMemcpyDefault, c.stream));   // host or device destination
+  CK(hipStreamSynchronize(c.stream));
+  return 0;
+}
+
+int prep_consts(DevBuf &ctr_b, DevBuf &mat_b, const double *ctr, const double *mat, int d, int dp,
+                bool transpose, hipStream_t s) {
+  std::vector<double> pc = pad_vector(ctr, d, dp);
+  std::vector<double> pm = pad_matrix(mat, d, dp, transpose);
+  if (int rc = upload(ctr_b, pc.data(), pc.size() * sizeof(double), s)) return rc;
+  if (int rc = upload(mat_b, pm.data(), pm.size() * sizeof(double), s)) return rc;
+  if (!arena_active()) CK(hipStreamSynchronize(s));  // host vectors go out of scope
+  return 0;
+}
 
 float f32_up(double x) {
   float f = (float)x;
@@ -1197,6 +1277,148 @@ int region_whiten_rows(mlf_region *r, const double *d_u, size_t n, double *d_t, 
   return 0;
 }
 
+// Arguments of the bounded per-proposal stage (k_prep4) of np rows: the ellipsoid test into `gate`, its band proposals listed
+// for the exact test (region_ell_args); whiten: also the approximate whitening into this batch's filter operand (filter_reserve
+// first, and the batch's parity turned)
+int region_prep4_args(mlf_region *r, const double *pts, long long np, uint8_t *gate, bool whiten, Prep4Args *out) {
+  FilterCtx &f = r->filter;
+  if (int rc = misc_reserve(f)) return rc;
+  CK(f.ell_list.reserve((size_t)np * sizeof(int)));
+  Prep4Args &pa = *out;
+  pa = Prep4Args{};
+  pa.pts = pts;
+  pa.np = np;
+  pa.d = r->d;
+  pa.dp = r->dp;
+  pa.LtF = r->p4_LtF.p;
+  pa.y0 = r->p4_y0.as<float>();
+  pa.TtF = r->p4_TtF.p;
+  pa.lay_ctr = r->use_scan ? r->lay_ctr.as<double>() : r->ell_ctr.as<double>();   // the centre the chain's start values belong to
+  pa.c = r->p4c;
+  pa.c.enl_lo = f32_dn(r->enlarge);
+  pa.c.enl_hi = f32_up(r->enlarge);
+  pa.gate = gate;
+  pa.do_tr = whiten ? 1 : 0;
+  pa.ell_count = f.misc.as<unsigned>();
+  pa.ell_list = f.ell_list.as<int>();
+  pa.ell_cap = (unsigned)np;
+  if (whiten) {
+    pa.stats = f.stats.as<double>();
+    pa.r2 = r->r2;
+    pa.qF = f.qF.p;
+    pa.tlo = f.tlo.as<float>();
+    pa.thi = f.thi.as<float>();
+    pa.route = f.route.as<uint8_t>();
+    pa.best = f.best.as<int>();
+    pa.counters = f.counters.as<unsigned>();
+    pa.scan_flag = f.misc.as<unsigned>() + 2 + f.batch_parity;
+    pa.ks = f.ks;
+    pa.nqpad = (np + 31) / 32 * 32;
+  }
+  return 0;
+}
+
+// the exact test of the ellipsoid band that k_prep4 listed (k_ell_exact, or trailing waves of a later launch of the batch)
+EllExactArgs region_ell_args(mlf_region *r, const double *pts, long long np, uint8_t *gate, uint8_t *route) {
+  FilterCtx &f = r->filter;
+  EllExactArgs ea{};
+  ea.count = f.misc.as<unsigned>();
+  ea.done = f.misc.as<unsigned>() + 1;
+  ea.last = f.misc.as<unsigned>() + 4;
+  ea.list = f.ell_list.as<int>();
+  ea.cap = (unsigned)np;
+  ea.pts = pts;
+  ea.d = r->d;
+  ea.dp = r->dp;
+  ea.ell_ctr = r->ell_ctr.as<double>();
+  ea.ell_Lt = r->ell_Lt.as<double>();
+  ea.ell_L = r->ell_L.as<double>();
+  ea.ell_A = r->ell_A.as<double>();
+  ea.eps_scale = r->ell_eps_scale;
+  ea.enlarge = r->enlarge;
+  ea.chol_ok = r->chol_ok ? 1 : 0;
+  ea.gate = gate;
+  ea.route = route;
+  return ea;
+}
+
+// plan.mid: the whole batch in one launch (k_inside_mid) and the exact scan behind it, idle unless a proposal was routed to it
+int region_inside_mid(mlf_region *r, const BatchPlan &p, const double *d_pts, long long np, uint8_t *d_mask, hipStream_t s,
+                      hipEvent_t *ev) {
+  FilterCtx &f = r->filter;
+  f.last = p;
+  if (int rc = misc_reserve(f)) return rc;
+  CK(f.route.reserve((size_t)np));
+  CK(f.counters.reserve(4 * sizeof(unsigned)));
+  const long long ngroups = (np + 31) / 32, nsets = (ngroups + 3) / 4;
+  const int ny = mid_range_quads(ngroups, f.ntiles32), R = 4 * ny;
+  CK(f.mid_rec.reserve((size_t)nsets * R * 3 * sizeof(unsigned long long)));
+  CK(f.mid_meta.reserve((size_t)nsets * 4 * sizeof(unsigned long long)));
+  {
+    const size_t before = f.mid_arrive.cap;
+    CK(f.mid_arrive.reserve((size_t)nsets * sizeof(unsigned)));
+    // they return to zero by themselves afterwards -- unless a launch failed part-way: then the next batch starts clean
+    if (f.mid_arrive.cap != before || f.mid_dirty) CK(hipMemsetAsync(f.mid_arrive.p, 0, f.mid_arrive.cap, s));
+    if (f.mid_dirty && f.misc.p) CK(hipMemsetAsync(f.misc.p, 0, 8 * sizeof(unsigned), s));
+    f.mid_dirty = false;
+  }
+  MidArgs ma{};
+  ma.pts = d_pts;
+  ma.np = np;
+  ma.d = r->d;
+  ma.dp = r->dp;
+  ma.ks = f.ks;
+  ma.LtF = r->p4_LtF.p;
+  ma.y0 = r->p4_y0.as<float>();
+  ma.TtF = r->p4_TtF.p;
+  ma.lay_ctr = r->lay_ctr.as<double>();
+  ma.c = r->p4c;
+  ma.c.enl_lo = f32_dn(r->enlarge);
+  ma.c.enl_hi = f32_up(r->enlarge);
+  ma.stats = f.stats.as<double>();
+  ma.r2 = r->r2;
+  ma.ell_ctr = r->ell_ctr.as<double>();
+  ma.ell_L = r->ell_L.as<double>();
+  ma.ell_A = r->ell_A.as<double>();
+  ma.ell_eps_scale = r->ell_eps_scale;
+  ma.enlarge = r->enlarge;
+  ma.chol_ok = r->chol_ok ? 1 : 0;
+  ma.refF = p.ordered ? f.refFm.p : f.refF.p;
+  ma.ntiles32 = f.ntiles32;
+  ma.refR = p.ordered ? f.refRm.as<double>() : r->refR.as<double>();
+  ma.n = r->n;
+  ma.T64 = r->lay_T64.as<double>();
+  ma.rec = f.mid_rec.as<unsigned long long>();
+  ma.meta = f.mid_meta.as<unsigned long long>();
+  ma.arrive = f.mid_arrive.as<unsigned>();
+  ma.mask = d_mask;
+  ma.route = f.route.as<uint8_t>();
+  f.batch_parity ^= 1u;
+  ma.scan_flag = f.misc.as<unsigned>() + 2 + f.batch_parity;
+  ma.counters = f.counters.as<unsigned>();
+  if (p.time_launches) {   // diagnostics: stage stamps of workgroup (0, 0) (mlf_region_debug_stats)
+    CK(f.segcnt.reserve(16 * sizeof(unsigned)));
+    ma.stamps = f.segcnt.as<unsigned>();
+  }
+  if (hipError_t le = launch_inside_mid(ma, ny, s); le != hipSuccess) {
+    f.mid_dirty = true;
+    CK(le);
+  }
+  if (ev) {
+    CK(hipEventRecord(ev[1], s));
+    CK(hipEventRecord(ev[2], s));
+  }
+  ScanArgs a = scan_args(region_live(r), d_pts, r->d, 1, np, SCAN_MASK);   // proposals the pre-filter cannot take (route 2)
+  a.out_mask = d_mask;
+  scan_finalise(a, f, region_exact_src(r, d_pts));
+  if (hipError_t le = launch_scan(r->dp, a, s); le != hipSuccess) {
+    f.mid_dirty = true;
+    CK(le);
+  }
+  if (ev) CK(hipEventRecord(ev[3], s));
+  return 0;
+}
+
 int region_inside_enqueue(mlf_region *r, const double *d_pts, size_t np, uint8_t *d_mask,
                           hipStream_t s, hipEvent_t *ev /* 4 events or null */,
                           long long *d_idx = nullptr, const uint8_t *pregate = nullptr) {
@@ -1206,203 +1428,39 @@ int region_inside_enqueue(mlf_region *r, const double *d_pts, size_t np, uint8_t
     if (int rc = filter_refresh_refs(r->filter, r->refR.as<double>(), r->n, r->d, r->dp, s)) return rc;
   CK(r->gate.reserve(np));
   uint8_t *gate = r->use_scan ? r->gate.as<uint8_t>() : d_mask;
-  const bool use_filter = r->use_scan && filter_applies(r->filter, (long long)np, r->r2);
-  // fused stage (coalesced staging, coordinate-major output, optional quantisation) for affine layers
-  const bool fused = r->layer_kind == 0 && opt(r->filter, OPT_FUSED_PREP) && prep3_usable(r->d) && r->chol_ready;
+  FilterCtx &f = r->filter;
+  const BatchPlan p = plan_batch(f, r, BATCH_INSIDE, (long long)np, r->r2, d_idx != nullptr, pregate != nullptr, d_pts);
   long long ldq = r->d, ldk = 1;
-  const bool bounded = fused && opt(r->filter, OPT_PREP_BOUNDED) && r->p4_ready && !r->has_wrap && (use_filter || !r->use_scan) &&
-                       np < (size_t)0x7fffffff && (reinterpret_cast<uintptr_t>(d_pts) & 15) == 0;   // 16-byte pieces
-  ExactSrc xsrc{};
-  if (r->use_scan && !bounded) CK(r->tq.reserve(np * (size_t)r->d * sizeof(double)));
+  if (r->use_scan && p.stage != STAGE_PREP4) CK(r->tq.reserve(np * (size_t)r->d * sizeof(double)));
   if (ev) CK(hipEventRecord(ev[0], s));
-  // The batch sizes of a real run (ndraw 128 ... 65536): per-proposal stage, sweep, re-check and answers in ONE launch
-  // (mlf_mid.hip); the exact-scan launch behind it only works if a proposal was routed to it.
-  const bool mid = bounded && r->use_scan && use_filter && !pregate && !d_idx && r->filter.ks <= 4 && mid_usable(r->dp) &&
-                   (long long)np <= opt(r->filter, OPT_MID_MAX);
-  if (mid) {
-    FilterCtx &f = r->filter;
-    if (int rc = misc_reserve(f)) return rc;
-    CK(f.route.reserve(np));
-    CK(f.counters.reserve(4 * sizeof(unsigned)));
-    const long long ngroups = ((long long)np + 31) / 32, nsets = (ngroups + 3) / 4;
-    const int ny = mid_range_quads(ngroups, f.ntiles32), R = 4 * ny;
-    CK(f.mid_rec.reserve((size_t)nsets * R * 3 * sizeof(unsigned long long)));
-    CK(f.mid_meta.reserve((size_t)nsets * 4 * sizeof(unsigned long long)));
-    {
-      const size_t before = f.mid_arrive.cap;
-      CK(f.mid_arrive.reserve((size_t)nsets * sizeof(unsigned)));
-      // they return to zero by themselves afterwards -- unless a launch failed part-way: then the next batch starts clean
-      if (f.mid_arrive.cap != before || f.mid_dirty) CK(hipMemsetAsync(f.mid_arrive.p, 0, f.mid_arrive.cap, s));
-      if (f.mid_dirty && f.misc.p) CK(hipMemsetAsync(f.misc.p, 0, 8 * sizeof(unsigned), s));
-      f.mid_dirty = false;
-    }
-    MidArgs ma{};
-    ma.pts = d_pts;
-    ma.np = (long long)np;
-    ma.d = r->d;
-    ma.dp = r->dp;
-    ma.ks = f.ks;
-    ma.LtF = r->p4_LtF.p;
-    ma.y0 = r->p4_y0.as<float>();
-    ma.TtF = r->p4_TtF.p;
-    ma.lay_ctr = r->lay_ctr.as<double>();
-    ma.c = r->p4c;
-    ma.c.enl_lo = f32_dn(r->enlarge);
-    ma.c.enl_hi = f32_up(r->enlarge);
-    ma.stats = f.stats.as<double>();
-    ma.r2 = r->r2;
-    ma.ell_ctr = r->ell_ctr.as<double>();
-    ma.ell_L = r->ell_L.as<double>();
-    ma.ell_A = r->ell_A.as<double>();
-    ma.ell_eps_scale = r->ell_eps_scale;
-    ma.enlarge = r->enlarge;
-    ma.chol_ok = r->chol_ok ? 1 : 0;
-    const bool use_m = f.ordered && opt(f, OPT_ORDER);
-    ma.refF = use_m ? f.refFm.p : f.refF.p;
-    ma.ntiles32 = f.ntiles32;
-    ma.refR = use_m ? f.refRm.as<double>() : r->refR.as<double>();
-    ma.n = r->n;
-    ma.T64 = r->lay_T64.as<double>();
-    ma.rec = f.mid_rec.as<unsigned long long>();
-    ma.meta = f.mid_meta.as<unsigned long long>();
-    ma.arrive = f.mid_arrive.as<unsigned>();
-    ma.mask = d_mask;
-    ma.route = f.route.as<uint8_t>();
-    f.batch_parity ^= 1u;
-    ma.scan_flag = f.misc.as<unsigned>() + 2 + f.batch_parity;
-    ma.counters = f.counters.as<unsigned>();
-    if (opt(f, OPT_TIME_LAUNCHES)) {   // diagnostics: stage stamps of workgroup (0, 0) (mlf_region_debug_stats)
-      CK(f.segcnt.reserve(16 * sizeof(unsigned)));
-      ma.stamps = f.segcnt.as<unsigned>();
-    }
-    f.mid_last = ma.stamps != nullptr;
-    if (hipError_t le = launch_inside_mid(ma, ny, s); le != hipSuccess) {
-      f.mid_dirty = true;
-      CK(le);
-    }
-    if (ev) {
-      CK(hipEventRecord(ev[1], s));
-      CK(hipEventRecord(ev[2], s));
-    }
-    ScanArgs a{};   // proposals the pre-filter cannot take (route 2): the exact scan, idle unless the batch's flag is up
-    a.refT = r->refT.as<double>();
-    a.n = r->n;
-    a.npad = r->npad;
-    a.ntiles = r->npad / kWave;
-    a.q = d_pts;
-    a.ldq = r->d;
-    a.ldk = 1;
-    a.nq = (long long)np;
-    a.d = r->d;
-    a.r2 = r->r2;
-    a.mode = SCAN_MASK;
-    a.out_mask = d_mask;
-    a.only_gated = 1;
-    a.raw_ctr = r->lay_ctr.as<double>();
-    a.raw_T8 = r->lay_T8.as<double>();
-    a.raw_ldt = (r->dp + 7) / 8 * 8;
-    a.route = f.route.as<uint8_t>();
-    a.counters = f.counters.as<unsigned>();
-    a.any_flag = f.misc.as<unsigned>() + 2 + f.batch_parity;
-    a.fin_reset = f.misc.as<unsigned>() + 2 + (f.batch_parity ^ 1u);
-    if (hipError_t le = launch_scan(r->dp, a, s); le != hipSuccess) {
-      f.mid_dirty = true;
-      CK(le);
-    }
-    f.last_nsegs = 0;
-    if (ev) CK(hipEventRecord(ev[3], s));
-    return 0;
-  }
-  if (bounded) {   // matrix cores (split binary16): bounded ellipsoid test + approximate whitening straight into the filter operand
-    FilterCtx &f = r->filter;
-    if (int rc = misc_reserve(f)) return rc;
-    CK(f.ell_list.reserve(np * sizeof(int)));
-    Prep4Args pa{};
-    pa.pts = d_pts;
-    pa.np = (long long)np;
-    pa.d = r->d;
-    pa.dp = r->dp;
-    pa.LtF = r->p4_LtF.p;
-    pa.y0 = r->p4_y0.as<float>();
-    pa.TtF = r->p4_TtF.p;
-    pa.lay_ctr = r->use_scan ? r->lay_ctr.as<double>() : r->ell_ctr.as<double>();
-    pa.c = r->p4c;
-    pa.c.enl_lo = f32_dn(r->enlarge);
-    pa.c.enl_hi = f32_up(r->enlarge);
-    pa.gate = gate;
-    pa.do_tr = r->use_scan ? 1 : 0;
-    pa.ell_count = f.misc.as<unsigned>();
-    pa.ell_list = f.ell_list.as<int>();
-    pa.ell_cap = (unsigned)np;
-    if (r->use_scan) {
-      unsigned cap = 0;
-      if (int rc = filter_reserve(f, (long long)np, &cap)) return rc;
-      pa.stats = f.stats.as<double>();
-      pa.r2 = r->r2;
-      pa.qF = f.qF.p;
-      pa.tlo = f.tlo.as<float>();
-      pa.thi = f.thi.as<float>();
-      pa.route = f.route.as<uint8_t>();
-      pa.best = f.best.as<int>();
-      pa.counters = f.counters.as<unsigned>();
-      f.batch_parity ^= 1u;
-      pa.scan_flag = f.misc.as<unsigned>() + 2 + f.batch_parity;
-      pa.ks = f.ks;
-      pa.nqpad = ((long long)np + 31) / 32 * 32;
-      xsrc.pts = d_pts;
-      xsrc.lay_ctr = r->lay_ctr.as<double>();
-      xsrc.T8 = r->lay_T8.as<double>();
-      xsrc.ldt = (r->dp + 7) / 8 * 8;
-      xsrc.T64 = r->lay_T64.as<double>();
-    }
-    // large batches on the min-only path: the per-proposal stage runs inside the first sweep launch (mlf_fused.hip)
-    const bool defer_prep = r->use_scan && use_filter && !d_idx && opt(f, OPT_FUSED_FIRST) && fused_usable(r->dp) &&
-                            filter_takes_min_path(f, (long long)np);
-    static thread_local Prep4Args deferred;
-    static thread_local Prep4Consts deferred_same;
-    if (defer_prep) {
-      deferred = pa;
-      xsrc.prep = &deferred;
+  if (p.mid) return region_inside_mid(r, p, d_pts, (long long)np, d_mask, s, ev);
+  if (p.filter)
+    if (int rc = filter_reserve(f, p, (long long)np)) return rc;
+  ExactSrc xs = region_exact_src(r, d_pts);
+  if (p.stage == STAGE_PREP4) {   // matrix cores (split binary16): bounded ellipsoid test + approximate whitening straight into the filter operand
+    if (r->use_scan) f.batch_parity ^= 1u;
+    Prep4Args pa;
+    if (int rc = region_prep4_args(r, d_pts, (long long)np, gate, r->use_scan != 0, &pa)) return rc;
+    if (p.defer) {   // the stage runs inside the first sweep launch
+      xs.prep = pa;
+      xs.same = r->p4c_same;
+      xs.same.enl_lo = pa.c.enl_lo;
+      xs.same.enl_hi = pa.c.enl_hi;
       if (pregate) {   // the fused first launch reads the pre-gate out of the gate array and writes its own verdict over it
         CK(hipMemcpyAsync(gate, pregate, np, hipMemcpyDeviceToDevice, s));
-        xsrc.pregated = true;
         pregate = nullptr;   // honoured there: no k_apply_pregate, and the ellipsoid band rides in the re-check launch as usual
-      }
-      if (r->same_matrix && r->same_centres) {
-        deferred_same = r->p4c_same;
-        deferred_same.enl_lo = pa.c.enl_lo;
-        deferred_same.enl_hi = pa.c.enl_hi;
-        xsrc.same = &deferred_same;
       }
     } else {
       CK(launch_prep4(pa, s));
     }
-    EllExactArgs ea{};
-    ea.count = f.misc.as<unsigned>();
-    ea.done = f.misc.as<unsigned>() + 1;
-    ea.last = f.misc.as<unsigned>() + 4;
-    ea.list = f.ell_list.as<int>();
-    ea.cap = (unsigned)np;
-    ea.pts = d_pts;
-    ea.d = r->d;
-    ea.dp = r->dp;
-    ea.ell_ctr = r->ell_ctr.as<double>();
-    ea.ell_Lt = r->ell_Lt.as<double>();
-    ea.ell_L = r->ell_L.as<double>();
-    ea.ell_A = r->ell_A.as<double>();
-    ea.eps_scale = r->ell_eps_scale;
-    ea.enlarge = r->enlarge;
-    ea.chol_ok = r->chol_ok ? 1 : 0;
-    ea.gate = gate;
-    ea.route = r->use_scan ? f.route.as<uint8_t>() : nullptr;
-    if (r->use_scan && !pregate) {   // decided by the tail of the re-check launch (k_recheck_whiten)
-      f.ell_args = ea;
-      f.ell_pending = true;
+    const EllExactArgs ea = region_ell_args(r, d_pts, (long long)np, gate, r->use_scan ? f.route.as<uint8_t>() : nullptr);
+    if (r->use_scan && !pregate) {   // decided by the tail of the re-check launch (k_recheck_whiten, k_sweep, k_uncertain)
+      xs.ell = ea;
     } else {
       launch_ell_exact(ea, s);
       CK(hipGetLastError());
     }
-  } else if (fused) {   // FP64 matrix-core version of the fused stage (v_mfma_f64_16x16x4_f64: the reference's FMA chain bit for bit)
+  } else if (p.stage == STAGE_PREP3) {   // FP64 matrix-core version of the fused stage (v_mfma_f64_16x16x4_f64: the reference's FMA chain bit for bit)
     Prep3Args pa{};
     pa.pts = d_pts;
     pa.np = (long long)np;
@@ -1427,14 +1485,9 @@ int region_inside_enqueue(mlf_region *r, const double *d_pts, size_t np, uint8_t
       pa.t_ldk = (long long)np;
       ldq = 1;
       ldk = (long long)np;
-      if (use_filter) {   // the exact re-check gathers single proposals: rows of d contiguous doubles
+      if (p.filter) {   // the exact re-check gathers single proposals: rows of d contiguous doubles
         pa.t_ldq = ldq = (long long)r->d;
         pa.t_ldk = ldk = 1;
-      }
-      if (use_filter) {
-        unsigned cap = 0;
-        FilterCtx &f = r->filter;
-        if (int rc = filter_reserve(f, (long long)np, &cap)) return rc;
         pa.qF = f.qF.p;
         pa.tlo = f.tlo.as<float>();
         pa.thi = f.thi.as<float>();
@@ -1448,7 +1501,7 @@ int region_inside_enqueue(mlf_region *r, const double *d_pts, size_t np, uint8_t
       }
     }
     CK(launch_prep3(pa, s));
-  } else if (r->layer_kind == 0 && prep64_usable(r->d) && r->chol_ready && r->chol_ok && opt(r->filter, OPT_FUSED_PREP)) {
+  } else if (p.stage == STAGE_PREP64) {
     // 65 ... 128 dimensions: the bounded quadratic form and the whitening chain on the FP64 matrix cores, the matrices streamed
     // from L2 (mlf_prep64.hip; rounds 1-4: the vector kernel below, 4-6 ms per 10^6 x 100)
     Prep64Args pa{};
@@ -1504,30 +1557,18 @@ int region_inside_enqueue(mlf_region *r, const double *d_pts, size_t np, uint8_t
     }
   }
   if (pregate) {   // proposals rejected before the region test (outside the unit cube): never scanned
-    const bool ff = fused && use_filter;
-    launch_apply_pregate(pregate, (long long)np, gate, ff ? r->filter.route.as<uint8_t>() : nullptr,
-                         ff ? r->filter.tlo.as<float>() : nullptr, ff ? r->filter.thi.as<float>() : nullptr, s);
+    const bool ff = p.filter && (p.stage == STAGE_PREP4 || p.stage == STAGE_PREP3);   // the stage has routed the batch
+    launch_apply_pregate(pregate, (long long)np, gate, ff ? f.route.as<uint8_t>() : nullptr, ff ? f.tlo.as<float>() : nullptr,
+                         ff ? f.thi.as<float>() : nullptr, s);
     CK(hipGetLastError());
   }
   if (ev) CK(hipEventRecord(ev[1], s));
-  if (use_filter) {
-    if (int rc = filter_run(r->filter, r->refT.as<double>(), r->refR.as<double>(), r->n, r->npad, r->d, r->dp,
-                            r->tq.as<double>(), ldq, ldk, (long long)np, r->r2, gate, d_idx ? nullptr : d_mask,
-                            d_idx, s, fused, ev ? ev[2] : nullptr, bounded ? &xsrc : nullptr))
+  if (p.filter) {
+    if (int rc = filter_run({f, p, region_live(r), r->tq.as<double>(), ldq, ldk, (long long)np, gate, d_idx ? nullptr : d_mask,
+                             d_idx, s, ev ? ev[2] : nullptr, p.stage == STAGE_PREP4 ? &xs : nullptr}))
       return rc;
   } else if (r->use_scan) {
-    ScanArgs a{};
-    a.refT = r->refT.as<double>();
-    a.n = r->n;
-    a.npad = r->npad;
-    a.ntiles = r->npad / kWave;
-    a.q = r->tq.as<double>();
-    a.ldq = ldq;
-    a.ldk = ldk;
-    a.nq = (long long)np;
-    a.d = r->d;
-    a.r2 = r->r2;
-    a.mode = d_idx ? SCAN_FIRST : SCAN_MASK;
+    ScanArgs a = scan_args(region_live(r), r->tq.as<double>(), ldq, ldk, (long long)np, d_idx ? SCAN_FIRST : SCAN_MASK);
     a.gate = gate;
     a.out_mask = d_mask;
     a.out_idx = d_idx;
@@ -2532,17 +2573,7 @@ int mlf_region_find_nearby_dev(mlf_region *r, const double *d_tpts, size_t np, i
   if (!r->ready || !r->use_scan) return fail_arg(MLF_E_STATE, "region has no live points set");
   if (np == 0) return 0;
   if (!d_tpts || !d_idx) return fail_arg(MLF_E_BADARG, "null pointer");
-  ScanArgs a{};
-  a.refT = r->refT.as<double>();
-  a.n = r->n;
-  a.npad = r->npad;
-  a.ntiles = r->npad / kWave;
-  a.q = d_tpts;
-  a.ldq = r->d;
-  a.nq = (long long)np;
-  a.d = r->d;
-  a.r2 = r->r2;
-  a.mode = SCAN_FIRST;
+  ScanArgs a = scan_args(region_live(r), d_tpts, r->d, 0, (long long)np, SCAN_FIRST);
   a.out_idx = reinterpret_cast<long long *>(d_idx);
   CK(launch_scan(r->dp, a, (hipStream_t)stream));
   return 0;
@@ -2598,20 +2629,10 @@ namespace {
 // neighbour test of t-space points against the resident live points (MFMA pre-filter when it applies)
 int region_scan_mask(mlf_region *r, const double *d_t, long long np, uint8_t *d_mask, hipStream_t s) {
   if (int rc = filter_refresh_refs(r->filter, r->refR.as<double>(), r->n, r->d, r->dp, s)) return rc;
-  if (filter_applies(r->filter, np, r->r2))
-    return filter_run(r->filter, r->refT.as<double>(), r->refR.as<double>(), r->n, r->npad, r->d, r->dp, d_t,
-                      (long long)r->d, 1, np, r->r2, nullptr, d_mask, nullptr, s, false);
-  ScanArgs a{};
-  a.refT = r->refT.as<double>();
-  a.n = r->n;
-  a.npad = r->npad;
-  a.ntiles = r->npad / kWave;
-  a.q = d_t;
-  a.ldq = r->d;
-  a.nq = np;
-  a.d = r->d;
-  a.r2 = r->r2;
-  a.mode = SCAN_MASK;
+  const BatchPlan p = plan_batch(r->filter, r, BATCH_TSPACE, np, r->r2);
+  if (p.filter)
+    return filter_run({r->filter, p, region_live(r), d_t, (long long)r->d, 1, np, nullptr, d_mask, nullptr, s, nullptr, nullptr});
+  ScanArgs a = scan_args(region_live(r), d_t, r->d, 0, np, SCAN_MASK);
   a.out_mask = d_mask;
   CK(launch_scan(r->dp, a, s));
   return 0;
@@ -2632,10 +2653,7 @@ int region_untransform(mlf_region *r, const double *t, long long n, double *w, u
 // test behind its band where the region has it (what a region without a neighbour scan runs), else the binary64 kernel
 int region_ellipsoid_gate(mlf_region *r, const double *d_pts, size_t np, uint8_t *gate, hipStream_t s) {
   if (np == 0) return 0;
-  FilterCtx &f = r->filter;
-  const bool bounded = r->layer_kind == 0 && opt(f, OPT_FUSED_PREP) && opt(f, OPT_PREP_BOUNDED) && prep3_usable(r->d) && r->chol_ready &&
-                       r->p4_ready && !r->has_wrap && np < (size_t)0x7fffffff && (reinterpret_cast<uintptr_t>(d_pts) & 15) == 0;
-  if (!bounded) {
+  if (plan_batch(r->filter, r, BATCH_GATE, (long long)np, r->r2, false, false, d_pts).stage != STAGE_PREP4) {
     PrepArgs pa{};
     pa.pts = d_pts;
     pa.np = (long long)np;
@@ -2648,45 +2666,10 @@ int region_ellipsoid_gate(mlf_region *r, const double *d_pts, size_t np, uint8_t
     CK(launch_prep(r->dp, pa, s));
     return 0;
   }
-  if (int rc = misc_reserve(f)) return rc;
-  CK(f.ell_list.reserve(np * sizeof(int)));
-  Prep4Args pa{};
-  pa.pts = d_pts;
-  pa.np = (long long)np;
-  pa.d = r->d;
-  pa.dp = r->dp;
-  pa.LtF = r->p4_LtF.p;
-  pa.y0 = r->p4_y0.as<float>();
-  pa.TtF = r->p4_TtF.p;
-  pa.lay_ctr = r->use_scan ? r->lay_ctr.as<double>() : r->ell_ctr.as<double>();   // the centre the chain's start values belong to
-  pa.c = r->p4c;
-  pa.c.enl_lo = f32_dn(r->enlarge);
-  pa.c.enl_hi = f32_up(r->enlarge);
-  pa.gate = gate;
-  pa.do_tr = 0;
-  pa.ell_count = f.misc.as<unsigned>();
-  pa.ell_list = f.ell_list.as<int>();
-  pa.ell_cap = (unsigned)np;
+  Prep4Args pa;
+  if (int rc = region_prep4_args(r, d_pts, (long long)np, gate, false, &pa)) return rc;
   CK(launch_prep4(pa, s));
-  EllExactArgs ea{};
-  ea.count = f.misc.as<unsigned>();
-  ea.done = f.misc.as<unsigned>() + 1;
-  ea.last = f.misc.as<unsigned>() + 4;
-  ea.list = f.ell_list.as<int>();
-  ea.cap = (unsigned)np;
-  ea.pts = d_pts;
-  ea.d = r->d;
-  ea.dp = r->dp;
-  ea.ell_ctr = r->ell_ctr.as<double>();
-  ea.ell_Lt = r->ell_Lt.as<double>();
-  ea.ell_L = r->ell_L.as<double>();
-  ea.ell_A = r->ell_A.as<double>();
-  ea.eps_scale = r->ell_eps_scale;
-  ea.enlarge = r->enlarge;
-  ea.chol_ok = r->chol_ok ? 1 : 0;
-  ea.gate = gate;
-  ea.route = nullptr;
-  launch_ell_exact(ea, s);
+  launch_ell_exact(region_ell_args(r, d_pts, (long long)np, gate, nullptr), s);
   CK(hipGetLastError());
   return 0;
 }
@@ -2741,17 +2724,8 @@ int region_sample_tspace(mlf_region *r, int method, long long n, uint64_t seed, 
     launch_scatter(t, r->s_gate.as<uint8_t>(), n, d, r->blk.as<unsigned>(), r->s_tc.as<double>(), k0, s);
     launch_scatter(wall, r->s_gate.as<uint8_t>(), n, d, r->blk.as<unsigned>(), r->s_wc.as<double>(), k0, s);
     launch_scatter(r->s_thin.as<double>(), r->s_gate.as<uint8_t>(), n, 1, r->blk.as<unsigned>(), r->s_thc.as<double>(), k0, s);
-    ScanArgs a{};   // multiplicity: how many balls contain the proposal (no early exit, reference :1087-1088)
-    a.refT = r->refT.as<double>();
-    a.n = r->n;
-    a.npad = r->npad;
-    a.ntiles = r->npad / kWave;
-    a.q = r->s_tc.as<double>();
-    a.ldq = d;
-    a.nq = k0;
-    a.d = d;
-    a.r2 = r->r2;
-    a.mode = SCAN_COUNT;
+    // multiplicity: how many balls contain the proposal (no early exit, reference :1087-1088)
+    ScanArgs a = scan_args(region_live(r), r->s_tc.as<double>(), d, 0, k0, SCAN_COUNT);
     a.out_idx = r->s_count.as<long long>();
     CK(launch_scan(r->dp, a, s));
     launch_thin_by_multiplicity(r->s_count.as<long long>(), r->s_thc.as<double>(), k0, mask, s);
@@ -3059,7 +3033,7 @@ int mlf_region_timing_filter_launch_ms(mlf_region *r, double *ms, int cap, int *
 
 int mlf_region_filter_info(mlf_region *r, size_t np, int *active, int *kdim, int *ntiles32) {
   if (!r || !active || !kdim || !ntiles32) return fail_arg(MLF_E_BADARG, "null pointer");
-  *active = (r->ready && r->use_scan && filter_applies(r->filter, (long long)np, r->r2)) ? 1 : 0;
+  *active = (r->ready && r->use_scan && plan_batch(r->filter, r, BATCH_INSIDE, (long long)np, r->r2).filter) ? 1 : 0;
   *kdim = r->filter.ks * 16;
   *ntiles32 = r->filter.ntiles32;
   return 0;
@@ -3093,7 +3067,7 @@ int mlf_region_debug_stats(mlf_region *r, unsigned long long *out, int cap) {
     out[0] = m[4];
   }
   if (f.segcnt.p && f.segcnt.cap >= sizeof(unsigned)) {
-    const size_t n = f.last_nsegs;
+    const size_t n = (size_t)f.last.nsegs;
     std::vector<unsigned> c(n);
     if (n) CK(hipMemcpy(c.data(), f.segcnt.p, n * sizeof(unsigned), hipMemcpyDeviceToHost));
     unsigned long long sum = 0, mx = 0;
@@ -3113,16 +3087,17 @@ int mlf_region_debug_stats(mlf_region *r, unsigned long long *out, int cap) {
     if (cap > 7) out[7] = g[5];   // three ranges: groups that entered the third
   }
   if (cap > 17) {
-    out[16] = (unsigned long long)f.last_cut[0];
-    out[17] = (unsigned long long)f.last_cut[1];
+    out[16] = (unsigned long long)f.last_min.cut[0];
+    out[17] = (unsigned long long)f.last_min.cut[1];
   }
-  if (cap > 18) out[18] = f.last_same_form ? 1ull : 0ull;   // the last fused launch took the ellipsoid form from the whitening chain
+  // the fused first launch took the ellipsoid form from the whitening chain
+  if (cap > 18) out[18] = (f.last_min.defer && (f.last_min.fused_variant & 2u)) ? 1ull : 0ull;
   {
-    if (cap >= 16 && f.mid_last && f.segcnt.p) {   // k_inside_mid, workgroup (0, 0): stage boundaries
+    if (cap >= 16 && f.last.mid && f.last.time_launches && f.segcnt.p) {   // k_inside_mid, workgroup (0, 0): stage boundaries
       unsigned st[8];
       CK(hipMemcpy(st, f.segcnt.p, sizeof st, hipMemcpyDeviceToHost));
       for (int i = 0; i < 8; ++i) out[8 + i] = st[i];
-    } else if (cap >= 16 && f.last_nsegs == (size_t)uncertain_blocks() && f.segcnt.cap >= (f.last_nsegs + 8) * sizeof(unsigned)) {
+    } else if (cap >= 16 && f.last.nsegs == uncertain_blocks() && f.segcnt.cap >= (size_t)(f.last.nsegs + 8) * sizeof(unsigned)) {
       unsigned st[8];   // shader-clock stamps of k_uncertain's workgroup 0 (stage boundaries of its first set)
       CK(hipMemcpy(st, f.segcnt.as<unsigned>() + uncertain_stamp_base(), sizeof st, hipMemcpyDeviceToHost));
       for (int i = 0; i < 8; ++i) out[8 + i] = st[i];
