@@ -443,6 +443,46 @@ int mlf_host_draw_selection(uint32_t *key, int32_t *pos, size_t npoints, size_t 
 int mlf_region_first_index_dev(mlf_region *r, const double *d_pts, size_t np, int64_t *d_idx,
                                void *stream);
 
+/* ---- user models: a likelihood (and prior transform) written as HIP device functions --------------------------
+ * The GPU counterpart of the reference's compiled-language likelihoods (languages/c/mylib.c: (params, d, n, like)).  The
+ * user's source defines
+ *   __device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux);           (required)
+ *   __device__ void mlf_user_transform(const double *u, double *p, int d, const double *aux, long long naux); (optional)
+ * and is compiled at run time by hiprtc (loaded with dlopen; where it is missing, compiling fails with MLF_E_COMPILE and
+ * every other entry point works as before) for gfx950 with -O3 -std=c++17 -ffp-contract=off, followed by
+ * `#include "mlf_user_rows.hpp"` (csrc/), which defines the one kernel the library launches (mlf_user_rows).  The user
+ * code runs on a shared GPU: it reads aux only within naux, writes nothing but the p row it is handed, and uses no inline
+ * assembly.  nparams == d (derived parameters are not covered).
+ *   compile  include_dir: the directory of mlf_user_rows.hpp.  code_out == NULL: size query (*code_size); a buffer of
+ *            code_cap < the size returns MLF_E_BADARG with *code_size set.  On MLF_E_COMPILE the hiprtc log (or why hiprtc
+ *            could not be loaded) is written to `log` (NUL-terminated, truncated to log_cap).  Needs no GPU.
+ *   create   loads the code object on the library's device, uploads aux (naux doubles, may be 0 / NULL) once.
+ *   destroy  waits for the library's stream before it unloads the model.
+ *   eval     host arrays: u (n, d); p_out (n, d) or NULL; L_out (n) or NULL (not both NULL).  p_out != NULL:
+ *            p = transform(u) (a copy of u without a transform) and L = loglike(p); p_out == NULL: the rows are taken as
+ *            parameters, L = loglike(u).  Synchronous.
+ *   eval_dev the same on DEVICE pointers, enqueued on `stream`; d_member (n bytes, may be NULL): rows with 0 are not
+ *            evaluated, their L is -inf and their p row is left as it was.
+ * mlf_region_refill_user / mlf_walkers_finish_user / mlf_walkers_step_user are mlf_region_refill / mlf_walkers_finish_dev /
+ * mlf_walkers_step_dev with the transform + likelihood pair replaced by one launch of the model's kernel (draws, counts,
+ * compaction, offsets and records are those of the built-in route); the walkers evaluate only the acceptable proposals. */
+#define MLF_E_COMPILE 5     /* the user model did not compile (or hiprtc is not available)   */
+typedef struct mlf_usermodel mlf_usermodel;
+int mlf_usermodel_compile(const char *source, const char *include_dir, int has_transform, void *code_out,
+                          size_t code_cap, size_t *code_size, char *log, size_t log_cap);
+int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_transform, const double *aux,
+                         size_t naux, mlf_usermodel **out);
+int mlf_usermodel_destroy(mlf_usermodel *model);
+int mlf_usermodel_eval(mlf_usermodel *model, const double *u, size_t n, double *p_out, double *L_out);
+int mlf_usermodel_eval_dev(mlf_usermodel *model, const double *d_u, size_t n, const uint8_t *d_member, double *d_p,
+                           double *d_L, void *stream);
+int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
+                           mlf_usermodel *model, double *out_u, double *out_p, double *out_L, size_t capacity,
+                           size_t *nevaluated, size_t *nkept, uint64_t *next_offset);
+int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, int64_t ringindex, double *rec);
+int mlf_walkers_step_user(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
+                          uint64_t offset, mlf_usermodel *model, double *rec, uint64_t *next_offset);
+
 /* ---- bench / profiling helpers ---------------------------------------------------------- */
 /* Runs the neighbour-scan kernel `reps` times on device data and returns the mean kernel time
  * in milliseconds measured with hipEvents on `stream`. */

@@ -125,6 +125,14 @@ SIGNATURES = {
     "mlf_comm_init": [_int],
     "mlf_allreduce_max": [_vp, _sz],
     "mlf_comm_destroy": [],
+    "mlf_usermodel_compile": [ctypes.c_char_p, ctypes.c_char_p, _int, _vp, _sz, _vp, _vp, _sz],
+    "mlf_usermodel_create": [_vp, _sz, _sz, _int, _vp, _sz, _vp],
+    "mlf_usermodel_destroy": [_vp],
+    "mlf_usermodel_eval": [_vp, _vp, _sz, _vp, _vp],
+    "mlf_usermodel_eval_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _vp],
+    "mlf_region_refill_user": [_vp, _int, _sz, ctypes.c_uint64, ctypes.c_uint64, _dbl, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp],
+    "mlf_walkers_finish_user": [_vp, _dbl, _vp, ctypes.c_int64, _vp],
+    "mlf_walkers_step_user": [_vp, _dbl, _dbl, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp],
 }
 
 _lib = None

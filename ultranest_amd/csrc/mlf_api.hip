@@ -2876,13 +2876,12 @@ static int region_sample_impl(mlf_region *r, int method, size_t nsamples, uint64
   return 0;
 }
 
-int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin, int tkind,
-                      double ta, double tb, int lkind, const double *aux, double sigma, double *out_u, double *out_p,
-                      double *out_L, size_t capacity, size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
-  if (!r || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
-    return fail_arg(MLF_E_BADARG, "null pointer");
-  if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
-  if (lkind == 0 && !aux) return fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
+// the body of mlf_region_refill / mlf_region_refill_user: `evaluate(rows, member, n, p_buf, L_buf, s, &prow)` enqueues the prior
+// transform and the likelihood of the n rows (p into p_buf, or *prow = rows for the identity; L into L_buf)
+extern "C++" template <class Evaluate>
+static int region_refill_impl(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
+                              Evaluate evaluate, double *out_u, double *out_p, double *out_L, size_t capacity,
+                              size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
   *nevaluated = 0;
   *nkept = 0;
   size_t nacc = 0;
@@ -2906,16 +2905,10 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
   CK(r->rf_out.reserve(capacity * (2 * (size_t)d + 1) * sizeof(double)));
   CK(r->rf_keep.reserve((size_t)n));
   CK(r->blk.reserve(((size_t)nblk + 1) * sizeof(unsigned)));
-  if (aux)
-    if (int rc = upload(r->rf_aux, aux, (size_t)d * sizeof(double), s)) return rc;
   // prior transform + likelihood on the accepted proposals, where they are (reference _refill_samples,
   // integrator.py:1789-1804); only the points above the threshold travel to the host
   const double *prow = rows;   // identity transform: the parameters ARE the cube coordinates, no copy
-  if (tkind != 0) {
-    launch_elementwise_affine(rows, n * d, tkind, ta, tb, r->rf_p.as<double>(), s);
-    prow = r->rf_p.as<double>();
-  }
-  launch_loglike(lkind, prow, d, n, r->rf_aux.as<double>(), sigma, r->rf_L.as<double>(), s);
+  if (int rc = evaluate(rows, member, n, r->rf_p.as<double>(), r->rf_L.as<double>(), s, &prow)) return rc;
   uint8_t *keep = r->rf_keep.as<uint8_t>();
   launch_mask_greater(r->rf_L.as<double>(), n, Lmin, keep, s, member);
   const unsigned cap = capacity > 0xffffffffu ? 0xffffffffu : (unsigned)capacity;
@@ -2937,6 +2930,47 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
   }
   *nkept = take;
   return 0;
+}
+
+int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin, int tkind,
+                      double ta, double tb, int lkind, const double *aux, double sigma, double *out_u, double *out_p,
+                      double *out_L, size_t capacity, size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
+  if (!r || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
+    return fail_arg(MLF_E_BADARG, "null pointer");
+  if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
+  if (lkind == 0 && !aux) return fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
+  auto evaluate = [&](const double *rows, const uint8_t *, long long n, double *pbuf, double *Lbuf, hipStream_t s,
+                      const double **prow) -> int {
+    const int d = r->d;
+    if (aux)
+      if (int rc = upload(r->rf_aux, aux, (size_t)d * sizeof(double), s)) return rc;
+    if (tkind != 0) {
+      launch_elementwise_affine(rows, n * d, tkind, ta, tb, pbuf, s);
+      *prow = pbuf;
+    }
+    launch_loglike(lkind, *prow, d, n, r->rf_aux.as<double>(), sigma, Lbuf, s);
+    return 0;
+  };
+  return region_refill_impl(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated,
+                            nkept, next_offset);
+}
+
+int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
+                           mlf_usermodel *model, double *out_u, double *out_p, double *out_L, size_t capacity,
+                           size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
+  if (!r || !model || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
+    return fail_arg(MLF_E_BADARG, "null pointer");
+  if (r->ready && usermodel_dim(model) != r->d) return fail_arg(MLF_E_BADARG, "user model and region differ in dimensionality");
+  // one mlf_user_rows launch for transform + likelihood; rows outside the membership mask are not evaluated (L = -inf: the
+  // threshold cut that follows drops them either way)
+  auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
+                      const double **prow) -> int {
+    double *p = usermodel_has_transform(model) ? pbuf : nullptr;
+    if (p) *prow = p;
+    return usermodel_rows(model, rows, n, member, p, Lbuf, s);
+  };
+  return region_refill_impl(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated,
+                            nkept, next_offset);
 }
 
 int mlf_debug_philox(uint64_t seed, unsigned stream, size_t nblocks, uint32_t *out) {

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
+
+struct mlf_usermodel;   // include/mlfriends_hip.h
 
 namespace mlf {
 
@@ -41,5 +44,12 @@ int ctx_ensure();                    // 0 or MLF_E_NODEVICE (message set)
 hipStream_t ctx_stream();
 int ctx_fail_hip(hipError_t e, const char *what, const char *file, int line);   // returns -(int)e
 int ctx_fail_arg(int code, const char *msg);                                    // returns code
+
+// defined in mlf_user.hip: a user model's dimensionality / transform flag, and one launch of its mlf_user_rows kernel on `s`
+// (argument meaning as in mlf_user_rows.hpp)
+int usermodel_dim(const mlf_usermodel *m);
+bool usermodel_has_transform(const mlf_usermodel *m);
+int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
+                   hipStream_t s);
 
 }  // namespace mlf

@@ -1,0 +1,262 @@
+// mlf_user.hip -- user models (include/mlfriends_hip.h, section "user models"): a likelihood and prior transform written
+// as HIP device functions, compiled at run time by hiprtc around mlf_user_rows.hpp, loaded as a module on the library's
+// device and launched on the library's stream (ordered with the kernels around it: the refill and walker routes of
+// mlf_api.hip / mlf_walk_api.hip call usermodel_rows between their own launches).
+//
+// hiprtc is loaded with dlopen, not linked: where it is missing the library loads and every other entry point works;
+// mlf_usermodel_compile then fails with MLF_E_COMPILE and says why.
+#include <hip/hip_runtime.h>
+#include <hip/hiprtc.h>   // types and prototypes only: the functions are looked up in the dlopen'ed library
+
+#include <dlfcn.h>
+
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/mlfriends_hip.h"
+#include "mlf_ctx.hpp"
+#define MLF_USER_ROWS_HOST
+#include "mlf_user_rows.hpp"
+
+using namespace mlf;
+
+#define CK(x)                                                                  \
+  do {                                                                         \
+    hipError_t e_ = (x);                                                       \
+    if (e_ != hipSuccess) return ctx_fail_hip(e_, #x, "mlf_user.hip", __LINE__); \
+  } while (0)
+
+struct mlf_usermodel {
+  hipModule_t module = nullptr;
+  hipFunction_t fn = nullptr;
+  int d = 0;
+  bool has_transform = false;
+  long long naux = 0;
+  DevBuf aux;
+  DevBuf hu, hp, hL;   // staging of mlf_usermodel_eval (host arrays)
+};
+
+namespace {
+
+struct Rtc {
+  bool tried = false;
+  void *handle = nullptr;
+  std::string why;
+  decltype(&hiprtcCreateProgram) create = nullptr;
+  decltype(&hiprtcCompileProgram) compile = nullptr;
+  decltype(&hiprtcDestroyProgram) destroy = nullptr;
+  decltype(&hiprtcGetCodeSize) code_size = nullptr;
+  decltype(&hiprtcGetCode) code = nullptr;
+  decltype(&hiprtcGetProgramLogSize) log_size = nullptr;
+  decltype(&hiprtcGetProgramLog) log = nullptr;
+  decltype(&hiprtcGetErrorString) error_string = nullptr;
+};
+Rtc g_rtc;
+std::mutex g_rtc_mutex;   // one hiprtc compile at a time
+
+template <class F>
+bool rtc_sym(void *h, const char *name, F &f) {
+  f = reinterpret_cast<F>(dlsym(h, name));
+  return f != nullptr;
+}
+
+// under g_rtc_mutex
+bool rtc_load() {
+  Rtc &r = g_rtc;
+  if (r.tried) return r.handle != nullptr;
+  r.tried = true;
+  std::vector<std::string> names = {"libhiprtc.so", "libhiprtc.so.7"};
+  const char *rocm = getenv("ROCM_PATH");
+  names.push_back(std::string(rocm && *rocm ? rocm : "/opt/rocm") + "/lib/libhiprtc.so");
+  std::string errors;
+  for (const std::string &n : names) {
+    r.handle = dlopen(n.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (r.handle) break;
+    const char *e = dlerror();
+    errors += "\n  " + n + ": " + (e ? e : "not found");
+  }
+  if (!r.handle) {
+    r.why = "libhiprtc.so (the HIP run-time compiler, part of ROCm) could not be loaded:" + errors;
+    return false;
+  }
+  if (!rtc_sym(r.handle, "hiprtcCreateProgram", r.create) || !rtc_sym(r.handle, "hiprtcCompileProgram", r.compile) ||
+      !rtc_sym(r.handle, "hiprtcDestroyProgram", r.destroy) || !rtc_sym(r.handle, "hiprtcGetCodeSize", r.code_size) ||
+      !rtc_sym(r.handle, "hiprtcGetCode", r.code) || !rtc_sym(r.handle, "hiprtcGetProgramLogSize", r.log_size) ||
+      !rtc_sym(r.handle, "hiprtcGetProgramLog", r.log) || !rtc_sym(r.handle, "hiprtcGetErrorString", r.error_string)) {
+    r.why = "libhiprtc.so lacks an expected hiprtc entry point";
+    dlclose(r.handle);
+    r.handle = nullptr;
+    return false;
+  }
+  return true;
+}
+
+void put_log(char *log, size_t cap, const std::string &text) {
+  if (!log || cap == 0) return;
+  const size_t k = text.size() < cap - 1 ? text.size() : cap - 1;
+  memcpy(log, text.data(), k);
+  log[k] = '\0';
+}
+
+}  // namespace
+
+namespace mlf {
+
+int usermodel_dim(const mlf_usermodel *m) { return m->d; }
+bool usermodel_has_transform(const mlf_usermodel *m) { return m->has_transform; }
+
+int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
+                   hipStream_t s) {
+  if (n <= 0) return 0;
+  const long long blocks = (n + 63) / 64;
+  if (blocks > 0x7fffffffLL) return ctx_fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
+  const unsigned lds = mlf_user_rows_lds_bytes(m->d, p != nullptr && m->has_transform);
+  // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
+  const double *a_u = u;
+  long long a_n = n;
+  int a_d = m->d;
+  const unsigned char *a_member = member;
+  const double *a_aux = m->aux.as<double>();
+  long long a_naux = m->naux;
+  double *a_p = p, *a_L = L;
+  void *args[] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
+  CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
+  return 0;
+}
+
+}  // namespace mlf
+
+extern "C" {
+
+int mlf_usermodel_compile(const char *source, const char *include_dir, int has_transform, void *code_out, size_t code_cap,
+                          size_t *code_size, char *log, size_t log_cap) {
+  if (!source || !include_dir || !code_size) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  *code_size = 0;
+  put_log(log, log_cap, "");
+  std::lock_guard<std::mutex> lock(g_rtc_mutex);
+  if (!rtc_load()) {
+    put_log(log, log_cap, g_rtc.why);
+    return ctx_fail_arg(MLF_E_COMPILE, g_rtc.why.c_str());
+  }
+  const Rtc &r = g_rtc;
+  const std::string src = std::string(source) + "\n#include \"mlf_user_rows.hpp\"\n";
+  const std::string inc = std::string("-I") + include_dir;
+  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
+                        has_transform ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0"};
+  hiprtcProgram prog = nullptr;
+  hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
+  if (res != HIPRTC_SUCCESS) {
+    const std::string msg = std::string("hiprtcCreateProgram: ") + r.error_string(res);
+    put_log(log, log_cap, msg);
+    return ctx_fail_arg(MLF_E_COMPILE, msg.c_str());
+  }
+  res = r.compile(prog, (int)(sizeof opts / sizeof opts[0]), opts);
+  if (res != HIPRTC_SUCCESS) {
+    std::string text = std::string("hiprtcCompileProgram: ") + r.error_string(res);
+    size_t nlog = 0;
+    if (r.log_size(prog, &nlog) == HIPRTC_SUCCESS && nlog > 1) {
+      std::vector<char> buf(nlog + 1, '\0');
+      if (r.log(prog, buf.data()) == HIPRTC_SUCCESS) text += "\n" + std::string(buf.data());
+    }
+    r.destroy(&prog);
+    put_log(log, log_cap, text);
+    return ctx_fail_arg(MLF_E_COMPILE, "the user model did not compile (hiprtc log in the caller's buffer)");
+  }
+  size_t size = 0;
+  res = r.code_size(prog, &size);
+  if (res != HIPRTC_SUCCESS || size == 0) {
+    r.destroy(&prog);
+    return ctx_fail_arg(MLF_E_COMPILE, "hiprtc returned no code object");
+  }
+  *code_size = size;
+  int rc = 0;
+  if (code_out) {
+    if (code_cap < size) {
+      rc = ctx_fail_arg(MLF_E_BADARG, "code buffer smaller than the code object (size in *code_size)");
+    } else if (r.code(prog, static_cast<char *>(code_out)) != HIPRTC_SUCCESS) {
+      rc = ctx_fail_arg(MLF_E_COMPILE, "hiprtcGetCode failed");
+    }
+  }
+  r.destroy(&prog);
+  return rc;
+}
+
+int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_transform, const double *aux, size_t naux,
+                         mlf_usermodel **out) {
+  if (!out || !code || (naux && !aux)) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  *out = nullptr;
+  if (d == 0) return ctx_fail_arg(MLF_E_BADARG, "dimensionality must be positive");
+  if (d > MLF_MAX_DIM) return ctx_fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
+  if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return ctx_fail_arg(MLF_E_BADARG, "not a code object (ELF)");
+  if (int rc = ctx_ensure()) return rc;
+  hipStream_t s = ctx_stream();
+  mlf_usermodel *m = new mlf_usermodel();
+  m->d = (int)d;
+  m->has_transform = has_transform != 0;
+  m->naux = (long long)naux;
+  hipError_t e = hipModuleLoadData(&m->module, code);
+  if (e == hipSuccess) e = hipModuleGetFunction(&m->fn, m->module, "mlf_user_rows");
+  if (e == hipSuccess) e = m->aux.reserve(naux ? naux * sizeof(double) : sizeof(double));
+  if (e == hipSuccess && naux) e = hipMemcpyAsync(m->aux.p, aux, naux * sizeof(double), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    if (m->module) (void)hipModuleUnload(m->module);
+    m->aux.release();
+    delete m;
+    return ctx_fail_hip(e, "mlf_usermodel_create", "mlf_user.hip", __LINE__);
+  }
+  *out = m;
+  return 0;
+}
+
+int mlf_usermodel_destroy(mlf_usermodel *m) {
+  if (!m) return 0;
+  // the model's last launches may still be queued (the library's stream, or a caller's stream of eval_dev)
+  hipError_t e = hipDeviceSynchronize();
+  if (m->module) {
+    const hipError_t e2 = hipModuleUnload(m->module);
+    if (e == hipSuccess) e = e2;
+  }
+  m->aux.release();
+  m->hu.release();
+  m->hp.release();
+  m->hL.release();
+  delete m;
+  if (e != hipSuccess) return ctx_fail_hip(e, "mlf_usermodel_destroy", "mlf_user.hip", __LINE__);
+  return 0;
+}
+
+int mlf_usermodel_eval(mlf_usermodel *m, const double *u, size_t n, double *p_out, double *L_out) {
+  if (!m || !u || (!p_out && !L_out)) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (n == 0) return 0;
+  if (n > 0x7fffffffffffull / (size_t)m->d) return ctx_fail_arg(MLF_E_BADARG, "batch too large");
+  hipStream_t s = ctx_stream();
+  const size_t rows = n * (size_t)m->d * sizeof(double);
+  CK(m->hu.reserve(rows));
+  if (p_out) CK(m->hp.reserve(rows));
+  if (L_out) CK(m->hL.reserve(n * sizeof(double)));
+  CK(hipMemcpyAsync(m->hu.p, u, rows, hipMemcpyHostToDevice, s));
+  if (int rc = usermodel_rows(m, m->hu.as<double>(), (long long)n, nullptr, p_out ? m->hp.as<double>() : nullptr,
+                              L_out ? m->hL.as<double>() : nullptr, s))
+    return rc;
+  CK(hipGetLastError());
+  if (p_out) CK(hipMemcpyAsync(p_out, m->hp.p, rows, hipMemcpyDeviceToHost, s));
+  if (L_out) CK(hipMemcpyAsync(L_out, m->hL.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  CK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mlf_usermodel_eval_dev(mlf_usermodel *m, const double *d_u, size_t n, const uint8_t *d_member, double *d_p, double *d_L,
+                           void *stream) {
+  if (!m) return ctx_fail_arg(MLF_E_BADARG, "null model");
+  if (n == 0) return 0;
+  if (!d_u || (!d_p && !d_L)) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (int rc = usermodel_rows(m, d_u, (long long)n, d_member, d_p, d_L, (hipStream_t)stream)) return rc;
+  CK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

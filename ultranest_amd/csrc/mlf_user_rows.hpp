@@ -1,0 +1,151 @@
+// mlf_user_rows.hpp -- the one kernel the library launches around a user model (ultranest_amd/devicemodel.py,
+// mlf_user.hip).  hiprtc compiles this header with the user's source in front of it; that source defines
+//
+//   __device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux);          // required
+//   __device__ void mlf_user_transform(const double *u, double *p, int d, const double *aux, long long naux);  // optional
+//
+// (the transform is compiled in when MLF_USER_HAS_TRANSFORM is 1; otherwise p = u).  The library itself includes the
+// header with MLF_USER_ROWS_HOST defined to share the choice of form and its LDS size (mlf_user_rows_lds_bytes).
+//
+// mlf_user_rows(u, n, d, member, aux, naux, p, L): rows are d doubles, row-major, one thread per row.
+//   member (nullable)  only rows with member[i] != 0 are evaluated; the others get L[i] = -inf and their p row is not written
+//   p      (nullable)  NULL: the rows ARE the parameters (no transform; the likelihood reads u)
+//                      else: p = transform(u) (a copy of u without a transform), the likelihood reads p
+//   L      (nullable)  NULL: transform only
+// u and p must not overlap.
+//
+// Two forms, chosen from d alone:
+//   staged  one wave per workgroup copies its 64 rows (one contiguous block of the batch) into LDS with coalesced loads, at
+//           a row pitch of d + 1 doubles (lane = row reads are then conflict-free), runs transform and likelihood from LDS
+//           and writes p back through LDS with coalesced stores (the k_loglike scheme of mlf_misc.hip, with a second buffer
+//           for p).  LDS per wave: nbuf * 64 * (d + 1) * 8 bytes, nbuf = 2 with a transform writing p, else 1.
+//   direct  one thread per row straight from global memory (k_loglike_wide), where the staging would exceed
+//           kUserRowsLdsBudget = 64 KiB per wave: d >= 64 with a transform, d >= 128 without.  64 KiB still lets two
+//           such waves share a CU's 160 KiB of LDS; above it one wave per CU would be left, with nothing to hide its
+//           load latency behind.
+#pragma once
+
+#define MLF_USER_ROWS_LDS_BUDGET 65536
+
+// bytes of dynamic LDS the launch needs (0: the direct form).  has_p_buffer: a transform writes p (second buffer).
+__host__ __device__ inline unsigned mlf_user_rows_lds_bytes(int d, bool has_p_buffer) {
+  const unsigned long long bytes = (unsigned long long)(has_p_buffer ? 2 : 1) * 64ull * (unsigned long long)(d + 1) * 8ull;
+  return bytes <= MLF_USER_ROWS_LDS_BUDGET ? (unsigned)bytes : 0u;
+}
+
+#ifndef MLF_USER_ROWS_HOST
+
+#ifndef MLF_USER_HAS_TRANSFORM
+#define MLF_USER_HAS_TRANSFORM 0
+#endif
+
+namespace mlf_user_detail {
+
+// loads in flight per lane while staging (32 VGPRs)
+constexpr int kLoads = 16;
+
+__device__ inline double neg_inf() { return -__builtin_inf(); }
+
+// rows of one wave: global block [0, total) -> LDS rows of pitch d + 1.  Element e = row * d + col; (row, col) of the lane's
+// next element is stepped by 64 elements at a time (no integer division per element).
+__device__ inline void stage_in(const double *src, int total, int d, double *lds, int lane) {
+  const int ds = d + 1;
+  const int qstep = 64 / d, rstep = 64 % d;
+  int row = lane / d, col = lane % d;
+  for (int e0 = 0; e0 < total; e0 += 64 * kLoads) {
+    double v[kLoads];
+#pragma unroll
+    for (int i = 0; i < kLoads; ++i) {
+      const int e = e0 + 64 * i + lane;
+      v[i] = e < total ? src[e] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < kLoads; ++i) {
+      const int e = e0 + 64 * i + lane;
+      if (e < total) lds[row * ds + col] = v[i];
+      row += qstep;
+      col += rstep;
+      if (col >= d) {
+        col -= d;
+        row += 1;
+      }
+    }
+  }
+}
+
+// LDS rows of pitch d + 1 -> global block [0, total); only the rows whose bit is set in `rows` are written
+__device__ inline void stage_out(double *dst, int total, int d, const double *lds, unsigned long long rows, int lane) {
+  const int ds = d + 1;
+  const int qstep = 64 / d, rstep = 64 % d;
+  int row = lane / d, col = lane % d;
+  for (int e = lane; e < total; e += 64) {
+    if ((rows >> row) & 1ull) dst[e] = lds[row * ds + col];
+    row += qstep;
+    col += rstep;
+    if (col >= d) {
+      col -= d;
+      row += 1;
+    }
+  }
+}
+
+__device__ inline void transform_row(const double *x, double *y, int d, const double *aux, long long naux) {
+#if MLF_USER_HAS_TRANSFORM
+  mlf_user_transform(x, y, d, aux, naux);
+#else
+  (void)aux;
+  (void)naux;
+  for (int k = 0; k < d; ++k) y[k] = x[k];
+#endif
+}
+
+}  // namespace mlf_user_detail
+
+extern "C" __global__ __launch_bounds__(64) void mlf_user_rows(const double *u, long long n, int d, const unsigned char *member,
+                                                                const double *aux, long long naux, double *p, double *L) {
+  using namespace mlf_user_detail;
+  const int lane = threadIdx.x;
+  const long long j0 = (long long)blockIdx.x * 64;
+  if (j0 >= n) return;
+  const long long left = n - j0;
+  const int nrows = left >= 64 ? 64 : (int)left;
+  const long long i = j0 + lane;
+  const bool mine = lane < nrows && (member == nullptr || member[i] != 0);
+  const unsigned long long live = __ballot(mine);
+  if (live == 0) {   // no member row in this block: nothing is read
+    if (L != nullptr && lane < nrows) L[i] = neg_inf();
+    return;
+  }
+  double like = neg_inf();
+  const bool p_buffer = p != nullptr && MLF_USER_HAS_TRANSFORM;
+  if (mlf_user_rows_lds_bytes(d, p_buffer) != 0) {
+    extern __shared__ __attribute__((aligned(16))) double mlf_user_lds[];
+    const int ds = d + 1;
+    double *a = mlf_user_lds;                       // 64 rows of u
+    double *b = p_buffer ? a + 64 * ds : a;         // 64 rows of p (the u rows themselves without a transform)
+    stage_in(u + j0 * d, nrows * d, d, a, lane);
+    __syncthreads();
+    if (mine) {
+      const double *x = a + lane * ds;
+      if (p_buffer) {
+        double *y = b + lane * ds;
+        transform_row(x, y, d, aux, naux);
+        x = y;
+      }
+      if (L != nullptr) like = mlf_user_loglike(x, d, aux, naux);
+    }
+    __syncthreads();
+    if (p != nullptr) stage_out(p + j0 * d, nrows * d, d, b, live, lane);
+  } else if (mine) {
+    const double *x = u + i * d;
+    if (p != nullptr) {
+      double *y = p + i * d;
+      transform_row(x, y, d, aux, naux);
+      x = y;
+    }
+    if (L != nullptr) like = mlf_user_loglike(x, d, aux, naux);
+  }
+  if (L != nullptr && lane < nrows) L[i] = like;
+}
+
+#endif  // MLF_USER_ROWS_HOST

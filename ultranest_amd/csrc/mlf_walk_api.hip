@@ -496,6 +496,66 @@ int mlf_walkers_step_dev(mlf_walkers *w, double Lmin, double scale, int dirkind,
   return 0;
 }
 
+// user model (mlf_user.hip): the proposals of the acceptable walkers go through ONE mlf_user_rows launch that writes pnew and
+// Lnew (dw_update reads Lnew only where acceptable, and pnew only after a success, which needs acceptable: the rows of the
+// other walkers are not evaluated); without a transform the kernel copies unew into pnew
+int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, int64_t ringindex, double *rec) {
+  if (!w || !rec || !model) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w->proposed) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_finish_user without a preceding mlf_walkers_propose");
+  if (usermodel_dim(model) != w->d) return ctx_fail_arg(MLF_E_BADARG, "user model and walkers differ in dimensionality");
+  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
+  hipStream_t s = ctx_stream();
+  const WalkState st = state_of(w);
+  if (int rc = usermodel_rows(model, st.unew, w->P, st.acceptable, st.pnew, st.Lnew, s)) return rc;
+  CK(hipGetLastError());
+  return finish_common(w, Lmin, ringindex, rec);
+}
+
+int mlf_walkers_step_user(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
+                          uint64_t offset, mlf_usermodel *model, double *rec, uint64_t *next_offset) {
+  if (!w || !rec || !next_offset || !model) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w->have_liveL) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
+  if (dirkind < 0 || dirkind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
+  if (usermodel_dim(model) != w->d) return ctx_fail_arg(MLF_E_BADARG, "user model and walkers differ in dimensionality");
+  const bool need_axes = dirkind == DIR_REGION_ORIENTED || dirkind == DIR_REGION_RANDOM || dirkind == DIR_MIXTURE;
+  if ((need_axes && !w->have_axes) || (dirkind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
+    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
+  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
+  hipStream_t s = ctx_stream();
+  if (!w->ring.p) {
+    CK(w->ring.reserve(8));
+    CK(hipMemsetAsync(w->ring.p, 0, 8, s));
+  }
+  const size_t nrec = 10 + 2 * (size_t)w->d;
+  CK(w->rec.reserve(nrec * sizeof(double)));
+  const WalkState st = state_of(w);
+  WalkDirData dd{};
+  dd.axes = w->axes.as<double>();
+  dd.live = w->live.as<double>();
+  dd.nlive = w->nlive;
+  dd.std = w->std.as<double>();
+  StepParams p{};
+  p.Lmin = Lmin;
+  p.scale = scale;
+  p.dirscale = dirscale;
+  p.r2 = w->r2;
+  p.seed = seed;
+  p.offset = offset;
+  // the sequence of mlf_walkers_step_dev; the prologue proposes without a transform (tkind -1)
+  launch_walk_prologue(st, w->live.as<double>(), w->liveL.as<double>(), w->nlive, dirkind, dd, -1, 0.0, 0.0,
+                       w->flags.as<uint8_t>(), p, nullptr, s);
+  if (int rc = usermodel_rows(model, st.unew, w->P, st.acceptable, st.pnew, st.Lnew, s)) return rc;
+  launch_walk_update(st, Lmin, layer_of(w), s);
+  launch_walk_harvest(st, 0, w->ring.as<long long>(), w->r2, w->rec.as<double>(), w->partials.as<double>(), s, nullptr,
+                      w->flags.as<uint8_t>());
+  CK(hipGetLastError());
+  if (int rc = download(rec, w->rec, nrec * sizeof(double), s)) return rc;
+  CK(hipStreamSynchronize(s));
+  const uint64_t per = (uint64_t)((w->d + 1) / 2 + 2);
+  *next_offset = offset + (uint64_t)w->P * (per > 64 ? per : 64);
+  return 0;
+}
+
 int mlf_walkers_step_graph(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                            uint64_t offset, int tkind, double ta, double tb, int lkind, const double *aux, double sigma,
                            double *rec, uint64_t *next_offset) {

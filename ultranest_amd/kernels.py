@@ -395,6 +395,19 @@ class DeviceRegion(object):
         k = nkept.value
         return u[:k], p[:k], L[:k], nev.value, nxt.value
 
+    def refill_user(self, method, nsamples, seed, offset, Lmin, model, capacity=None):
+        """`refill` with a user model (``mlf_usermodel *`` of ultranest_amd.devicemodel) in place of the built-in
+        transform / likelihood kinds."""
+        d = self._d
+        cap = int(nsamples if capacity is None else capacity)
+        u, p, L = np.empty((cap, d)), np.empty((cap, d)), np.empty(cap)
+        nev, nkept, nxt = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
+        check(_lib.lib().mlf_region_refill_user(self._h, int(method), int(nsamples), ctypes.c_uint64(int(seed)),
+                                                ctypes.c_uint64(int(offset)), float(Lmin), model, ptr(u), ptr(p), ptr(L), cap,
+                                                ctypes.byref(nev), ctypes.byref(nkept), ctypes.byref(nxt)))
+        k = nkept.value
+        return u[:k], p[:k], L[:k], nev.value, nxt.value
+
     def first_index_dev(self, d_pts, npts, d_idx, stream=0):
         check(_lib.lib().mlf_region_first_index_dev(self._h, ctypes.c_void_p(d_pts), npts,
                                                     ctypes.c_void_p(d_idx), ctypes.c_void_p(stream)))

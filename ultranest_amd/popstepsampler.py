@@ -18,13 +18,15 @@ Two random sources:
 
 Likelihood: any ``loglike(p) -> L`` / ``transform(u) -> p`` numpy callbacks (the accepted
 proposals then make one round trip), or the device likelihoods of ``ultranest_amd.likelihoods``
-(objects with ``device_spec``), which are evaluated in place on the device.
+(objects with ``device_spec``), which are evaluated in place on the device, or a user model's callbacks
+(``ultranest_amd.devicemodel.DeviceModel``: HIP device functions compiled at run time), which run per step on the
+device (no graph replay, no multi-round kernel).
 """
 import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, devicemodel
 from ._lib import check, f64, ptr
 from .regions import DeviceRNG
 from .stepfuncs import (evolve, generate_cube_oriented_direction,  # noqa: F401
@@ -364,6 +366,27 @@ class _Walkers(object):
                                                 int(ringindex), ptr(rec)))
         return self._record(rec, self.ndim)
 
+    def finish_user(self, Lmin, model, with_transform, ringindex):
+        """`finish_dev` with a user model (ultranest_amd.devicemodel): its kernel evaluates the acceptable proposals."""
+        self.nparams = self.ndim
+        rec = np.empty(9 + 2 * self.ndim)
+        check(_lib.lib().mlf_walkers_finish_user(self._h, float(Lmin), model.handle(with_transform), int(ringindex),
+                                                 ptr(rec)))
+        return self._record(rec, self.ndim)
+
+    def step_user(self, Lmin, scale, kind, dirscale, rng, model, with_transform):
+        """`step_dev` (graph=False) with a user model."""
+        self.nparams = self.ndim
+        rec = np.empty(10 + 2 * self.ndim)
+        nxt = ctypes.c_uint64(0)
+        check(_lib.lib().mlf_walkers_step_user(self._h, float(Lmin), float(scale), int(kind), float(dirscale),
+                                               ctypes.c_uint64(rng.seed), ctypes.c_uint64(rng.offset),
+                                               model.handle(with_transform), ptr(rec), ctypes.byref(nxt)))
+        rng.offset = nxt.value
+        out = self._record(rec, self.ndim)
+        out["ring"] = int(rec[9 + 2 * self.ndim])
+        return out
+
     def set_live(self, us, Ls):
         us, Ls = f64(us), f64(Ls)
         check(_lib.lib().mlf_walkers_set_live(self._h, ptr(us), ptr(Ls), len(Ls)))
@@ -523,11 +546,15 @@ class PopulationSliceSampler(GenericPopulationSampler):
             self._walkers = _Walkers(self.popsize, self.nsteps, ndim)
         w = self._walkers
         tspec, lspec = getattr(transform, "device_spec", None), getattr(loglike, "device_spec", None)
+        user = devicemodel.device_route(transform, loglike)     # (model, with_transform) of a user model, or None
+        if user is not None or devicemodel.is_user_spec(tspec) or devicemodel.is_user_spec(lspec):
+            tspec = lspec = None   # never unpacked as (kind, a, b); a user model paired with another callback: host callbacks
         device_kind = getattr(self.generate_direction, "device_kind", None)
-        whole_step = self.device_rng is not None and device_kind is not None and tspec is not None and lspec is not None
+        whole_step = self.device_rng is not None and device_kind is not None and (
+            user is not None or (tspec is not None and lspec is not None))
         self._sync_region(region, skip_live=whole_step)
         if whole_step:
-            return self._next_on_device(region, Lmin, us, Ls, device_kind, tspec, lspec)
+            return self._next_on_device(region, Lmin, us, Ls, device_kind, tspec, lspec, user)
 
         # step_back on the device; the host learns which walkers need what
         generation, flags = w.begin(Lmin)
@@ -564,7 +591,10 @@ class PopulationSliceSampler(GenericPopulationSampler):
         else:
             unif, rng = np.zeros(self.popsize), None
             unif[bisecting] = np.random.random_sample(int(bisecting.sum()))
-        if resident_likelihood:
+        if user is not None:
+            w.propose(unif, rng, fetch=False)
+            rec = w.finish_user(Lmin, user[0], user[1], self.ringindex)
+        elif resident_likelihood:
             w.propose(unif, rng, fetch=False)
             rec = w.finish_dev(Lmin, tspec, lspec, self.ringindex)
         else:
@@ -578,10 +608,11 @@ class PopulationSliceSampler(GenericPopulationSampler):
         self._generation, self._flags = generation, flags
         return self._finish_call(rec, region)
 
-    def _next_on_device(self, region, Lmin, us, Ls, device_kind, tspec, lspec):
+    def _next_on_device(self, region, Lmin, us, Ls, device_kind, tspec, lspec, user=None):
         """Philox stream + resident likelihood: the whole step is one sequence of kernels
         (``mlf_walkers_step_dev``): restarts draw from a device copy of the live points and the ring
-        index lives on the device; one record comes back."""
+        index lives on the device; one record comes back.  A user model (`user` = (model, with_transform))
+        takes ``mlf_walkers_step_user``, one step per call, without graph replay (ultranest_amd.devicemodel)."""
         w, seen = self._walkers, self._seen
         # the device copy of (us, Ls) follows the host arrays ROW BY ROW: the driver replaces one live point per iteration
         # (integrator.py:2753-2754), so the rows whose likelihood or first coordinate changed since the last call are
@@ -603,7 +634,9 @@ class PopulationSliceSampler(GenericPopulationSampler):
                 mirror[0][changed] = Ls[changed]
                 mirror[1][changed] = us[changed, 0]
         seen["live_age"] += 1
-        if abs(self.max_rounds) > 1:      # (negative: the same rounds through the general, memory-resident form -- tests)
+        if user is not None:
+            rec = w.step_user(Lmin, self.scale, device_kind, 1.0, self.device_rng, user[0], user[1])
+        elif abs(self.max_rounds) > 1:      # (negative: the same rounds through the general, memory-resident form -- tests)
             rec, rows = w.rounds_dev(Lmin, self.scale, device_kind, 1.0, self.device_rng, tspec, lspec, self.max_rounds)
             have_diag = region.maxradiussq is not None
             nc = int(rows[:, 0].sum())

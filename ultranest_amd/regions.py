@@ -20,7 +20,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib, kernels
+from . import _lib, devicemodel, kernels
 from .layers import host_worker, int_dtype, single_blas_thread
 
 # When True, ``MLFriends.inside`` transforms ellipsoid-passing points on the host with the same
@@ -391,6 +391,14 @@ class _DeviceState(object):
         handle = self._prepare_sampling(region, use_scan, method)
         rng = region.device_rng
         u, p, L, nev, rng.offset = handle.refill(method, nsamples, rng.seed, rng.offset, Lmin, tspec, lspec)
+        return u, p, L, nev
+
+    def refill_user(self, region, use_scan, method, nsamples, Lmin, model, with_transform):
+        """The same batch with a user model (ultranest_amd.devicemodel): transform + likelihood in one fused launch."""
+        handle = self._prepare_sampling(region, use_scan, method)
+        rng = region.device_rng
+        u, p, L, nev, rng.offset = handle.refill_user(method, nsamples, rng.seed, rng.offset, Lmin,
+                                                      model.handle(with_transform))
         return u, p, L, nev
 
     def sample(self, region, use_scan, method, nsamples):
@@ -799,15 +807,25 @@ class MLFriends(_LivePoints):
         """One proposal batch of the driver's ``_refill_samples`` (reference integrator.py:1773-1837)
         without leaving the device: draw with the current sampling method, region test, prior
         transform, likelihood, and only the points with L > Lmin come back as ``(u, p, L, nc)``.
-        Needs ``device_rng`` and ``device_spec`` on both callbacks (ultranest_amd.likelihoods);
-        returns None if that does not hold (the caller then uses sample() + callbacks)."""
+        Needs ``device_rng`` and ``device_spec`` on both callbacks (ultranest_amd.likelihoods), or a user model's
+        callbacks (ultranest_amd.devicemodel.device_route); returns None if that does not hold (the caller then uses
+        sample() + callbacks)."""
         tspec, lspec = getattr(transform, "device_spec", None), getattr(loglike, "device_spec", None)
         method = self._DEVICE_METHOD.get(getattr(self.current_sampling_method, "__name__", ""), None)
-        if self.device_rng is None or tspec is None or lspec is None or method is None:
+        user = devicemodel.device_route(transform, loglike)
+        if user is None and (devicemodel.is_user_spec(tspec) or devicemodel.is_user_spec(lspec)):
+            return None     # a user model paired with another callback: host callbacks
+        if user is not None:
+            if self.device_rng is None or method is None:
+                return None
+        elif self.device_rng is None or tspec is None or lspec is None or method is None:
             return None
         if method >= 2 and not self._device_tspace():
             return None
-        u, p, L, nc = self._dev.refill(self, self._uses_scan(), method, nsamples, Lmin, tspec, lspec)
+        if user is not None:
+            u, p, L, nc = self._dev.refill_user(self, self._uses_scan(), method, nsamples, Lmin, *user)
+        else:
+            u, p, L, nc = self._dev.refill(self, self._uses_scan(), method, nsamples, Lmin, tspec, lspec)
         if nc == 0:   # the region accepted nothing: re-roll the method like sample() does (:1180-1183)
             self.current_sampling_method = self.sampling_methods[np.random.randint(len(self.sampling_methods))]
         return u, p, L, nc
