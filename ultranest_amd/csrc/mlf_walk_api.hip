@@ -36,17 +36,26 @@ struct mlf_walkers {
   unsigned nblk = 0;
   bool proposed = false, compacted = false;
   std::vector<uint8_t> host_snap;
+  // one captured launch sequence (replay): the executable graph and everything its captured arguments depend on
+  struct GraphCache {
+    hipGraphExec_t exec = nullptr;
+    std::vector<unsigned long long> key;
+    hipError_t release() {
+      hipGraphExec_t e = exec;
+      exec = nullptr;
+      key.clear();
+      return e ? hipGraphExecDestroy(e) : hipSuccess;
+    }
+  };
   // whole-step hipGraph: one launch replays the ~12 kernels + the record copy; the values that change per
   // call travel through a pinned StepParams block
-  hipGraphExec_t gexec = nullptr;
+  GraphCache step_graph;
   StepParams *h_sp = nullptr;      // pinned
   double *h_rec = nullptr;         // pinned
   DevBuf d_sp;
-  std::vector<unsigned long long> gkey;
   // several rounds per call (mlf_walkers_rounds_dev)
   DevBuf r_ctl, r_flags, r_dist2, r_out, r_sp, r_last, r_parts, live_stage;
-  hipGraphExec_t rgexec = nullptr; // the launch sequence of mlf_walkers_rounds_dev (parameter copy, four kernels, record copy) as ONE graph launch
-  std::vector<unsigned long long> rgkey;
+  GraphCache rounds_graph;         // the launch sequence of mlf_walkers_rounds_dev (parameter copy, four kernels, record copy) as ONE graph launch
   double *h_live = nullptr;        // pinned staging of mlf_walkers_update_live
   size_t h_live_bytes = 0;
   StepParams *h_rsp = nullptr;     // pinned
@@ -125,8 +134,48 @@ int ensure_params(mlf_walkers *w, size_t nparams) {
   return 0;
 }
 
-int finish_common(mlf_walkers *w, double Lmin, int64_t ringindex, double *rec) {
+// What evaluates the proposals: the built-in pair (prior transform tkind, ta, tb; likelihood lkind, aux, sigma) or a user
+// model (mlf_user.hip), whose kernel writes pnew itself and evaluates only the acceptable proposals (dw_update reads Lnew only
+// where acceptable, and pnew only after a success, which needs acceptable); with it, tkind -1: a step's prologue proposes
+// without a transform.
+struct StepEval {
+  mlf_usermodel *model = nullptr;
+  int tkind = -1;
+  double ta = 0.0, tb = 0.0;
+  int lkind = 0;
+  const double *aux = nullptr;
+  double sigma = 0.0;
+
+  int check(const mlf_walkers *w) const {
+    if (model) {
+      if (usermodel_dim(model) != w->d) return ctx_fail_arg(MLF_E_BADARG, "user model and walkers differ in dimensionality");
+      return 0;
+    }
+    if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return ctx_fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
+    if (lkind == 0 && !aux) return ctx_fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
+    return 0;
+  }
+  // pnew and Lnew on s; transform: the built-in transform has not run yet (a step's prologue runs it)
+  int enqueue(mlf_walkers *w, bool transform, hipStream_t s) const {
+    const WalkState st = state_of(w);
+    if (model) return usermodel_rows(model, st.unew, w->P, st.acceptable, st.pnew, st.Lnew, s);
+    if (transform) launch_walk_transform(st, tkind, ta, tb, s);
+    launch_loglike(lkind, st.pnew, w->d, w->P, w->aux.as<double>(), sigma, st.Lnew, s);
+    return 0;
+  }
+};
+
+// update + harvest of walker ringindex; ev (mlf_walkers_finish_dev / _finish_user): the device evaluates the proposals first
+int finish_common(mlf_walkers *w, double Lmin, const StepEval *ev, int64_t ringindex, double *rec) {
   hipStream_t s = ctx_stream();
+  if (ev) {
+    if (int rc = ev->check(w)) return rc;
+    if (int rc = ensure_params(w, (size_t)w->d)) return rc;
+    if (ev->aux)
+      if (int rc = upload(w->aux, ev->aux, (size_t)w->d * 8, s)) return rc;
+    if (int rc = ev->enqueue(w, true, s)) return rc;
+    CK(hipGetLastError());
+  }
   if (ringindex < 0 || ringindex >= w->P) return ctx_fail_arg(MLF_E_BADARG, "ringindex out of range");
   const size_t nrec = 9 + (size_t)w->d + (size_t)w->nparams;
   CK(w->rec.reserve(nrec * sizeof(double)));
@@ -137,6 +186,127 @@ int finish_common(mlf_walkers *w, double Lmin, int64_t ringindex, double *rec) {
   if (int rc = download(rec, w->rec, nrec * sizeof(double), s)) return rc;
   CK(hipStreamSynchronize(s));
   w->proposed = false;
+  return 0;
+}
+
+WalkDirData dir_data(const mlf_walkers *w) {
+  WalkDirData dd{};
+  dd.axes = w->axes.as<double>();
+  dd.live = w->live.as<double>();
+  dd.nlive = w->nlive;
+  dd.std = w->std.as<double>();
+  return dd;
+}
+
+int check_direction_data(const mlf_walkers *w, int kind) {
+  const bool need_axes = kind == DIR_REGION_ORIENTED || kind == DIR_REGION_RANDOM || kind == DIR_MIXTURE;
+  const bool need_live = kind == DIR_DIFFERENTIAL || kind == DIR_MIXTURE;
+  if ((need_axes && !w->have_axes) || (need_live && !w->have_live) || (kind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
+    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
+  return 0;
+}
+
+// the record of a whole step: that of finish (nparams = d), then the ring index after the step
+size_t step_nrec(const mlf_walkers *w) { return 10 + 2 * (size_t)w->d; }
+
+// Philox counters one whole step (one round) consumes
+uint64_t philox_per_call(const mlf_walkers *w) {
+  const uint64_t per = (uint64_t)((w->d + 1) / 2 + 2);
+  return (uint64_t)w->P * (per > 64 ? per : 64);
+}
+
+// the checks of every whole-step route, in this order; max_rounds: that of mlf_walkers_rounds_dev, test-hook sign removed
+int check_step(const mlf_walkers *w, int dirkind, const StepEval &ev, int max_rounds = 1) {
+  if (!w->have_liveL) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
+  if (dirkind < 0 || dirkind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
+  if (int rc = ev.check(w)) return rc;
+  if (max_rounds < 1) return ctx_fail_arg(MLF_E_BADARG, "max_rounds must not be 0");
+  return check_direction_data(w, dirkind);
+}
+
+int prepare_step(mlf_walkers *w, const StepEval &ev, hipStream_t s) {
+  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
+  if (!w->ring.p) {
+    CK(w->ring.reserve(8));
+    CK(hipMemsetAsync(w->ring.p, 0, 8, s));
+  }
+  CK(w->rec.reserve(step_nrec(w) * sizeof(double)));
+  CK(w->aux.reserve((size_t)w->d * 8));
+  if (ev.aux)
+    if (int rc = upload(w->aux, ev.aux, (size_t)w->d * 8, s)) return rc;
+  return 0;
+}
+
+// One whole step on s: the prologue (step_back, restarts, new slices, proposal, built-in transform), the likelihood, update
+// and harvest into w->rec.  The kernels take the per-call scalars from p, or, with dev_params (a graph capture), from there.
+int enqueue_step(mlf_walkers *w, int dirkind, const StepEval &ev, const StepParams &p, const StepParams *dev_params,
+                 hipStream_t s) {
+  const WalkState st = state_of(w);
+  launch_walk_prologue(st, w->live.as<double>(), w->liveL.as<double>(), w->nlive, dirkind, dir_data(w), ev.tkind, ev.ta, ev.tb,
+                       w->flags.as<uint8_t>(), p, dev_params, s);
+  if (int rc = ev.enqueue(w, false, s)) return rc;
+  launch_walk_update(st, p.Lmin, layer_of(w), s, dev_params);
+  launch_walk_harvest(st, 0, w->ring.as<long long>(), p.r2, w->rec.as<double>(), w->partials.as<double>(), s, dev_params,
+                      w->flags.as<uint8_t>());
+  return 0;
+}
+
+// mlf_walkers_step_dev / _step_user: the kernels of one step launched one by one, one record back
+int run_step(mlf_walkers *w, int dirkind, const StepEval &ev, const StepParams &p, double *rec, uint64_t *next_offset) {
+  if (int rc = check_step(w, dirkind, ev)) return rc;
+  hipStream_t s = ctx_stream();
+  if (int rc = prepare_step(w, ev, s)) return rc;
+  if (int rc = enqueue_step(w, dirkind, ev, p, nullptr, s)) return rc;
+  CK(hipGetLastError());
+  if (int rc = download(rec, w->rec, step_nrec(w) * sizeof(double), s)) return rc;
+  CK(hipStreamSynchronize(s));
+  *next_offset = p.offset + philox_per_call(w);
+  return 0;
+}
+
+unsigned long long bits(double v) {
+  unsigned long long u;
+  memcpy(&u, &v, sizeof u);
+  return u;
+}
+unsigned long long addr(const void *p) { return (unsigned long long)(uintptr_t)p; }
+
+// what the captured arguments of a whole step depend on, on both graph routes
+std::vector<unsigned long long> step_key(const mlf_walkers *w, int dirkind, const StepEval &ev) {
+  return {(unsigned long long)dirkind, (unsigned long long)ev.tkind, bits(ev.ta), bits(ev.tb), (unsigned long long)ev.lkind,
+          bits(ev.sigma), (unsigned long long)(w->layer_kind + 1), (unsigned long long)w->layer_wrap, (unsigned long long)w->nlive,
+          addr(w->live.p), addr(w->liveL.p), addr(w->axes.p), addr(w->std.p), addr(w->lay_ctr.p), addr(w->lay_mat.p),
+          addr(w->lay_wrap.p), addr(w->aux.p), addr(w->pnew.p), addr(w->currentp.p)};
+}
+
+// Launch c's graph on s and wait for it.  Without a graph for `key`, the old one goes and capture(s) is captured anew: every
+// call in it is checked and the capture is always ended.  A capture that fails leaves no graph (exec null, key empty) and
+// returns the first error.
+template <class Capture>
+int replay(mlf_walkers::GraphCache &c, std::vector<unsigned long long> key, hipStream_t s, Capture &&capture) {
+  if (!c.exec || key != c.key) {
+    CK(c.release());
+    CK(hipStreamSynchronize(s));
+    CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = capture(s);
+    hipError_t e = hipGetLastError();
+    if (!rc && e != hipSuccess) rc = ctx_fail_hip(e, "a launch during the graph capture", "mlf_walk_api.hip", __LINE__);
+    hipGraph_t graph = nullptr;
+    e = hipStreamEndCapture(s, &graph);
+    if (!rc && e != hipSuccess) rc = ctx_fail_hip(e, "hipStreamEndCapture", "mlf_walk_api.hip", __LINE__);
+    if (!rc) {
+      e = hipGraphInstantiate(&c.exec, graph, nullptr, nullptr, 0);
+      if (e != hipSuccess) {
+        c.exec = nullptr;
+        rc = ctx_fail_hip(e, "hipGraphInstantiate", "mlf_walk_api.hip", __LINE__);
+      }
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc) return rc;
+    c.key = std::move(key);
+  }
+  CK(hipGraphLaunch(c.exec, s));
+  CK(hipStreamSynchronize(s));
   return 0;
 }
 
@@ -193,10 +363,10 @@ int mlf_walkers_destroy(mlf_walkers *w) {
   w->d_sp.release();
   for (DevBuf *b : {&w->r_ctl, &w->r_flags, &w->r_dist2, &w->r_out, &w->r_sp, &w->r_last, &w->r_parts, &w->live_stage}) b->release();
   if (w->h_live) (void)hipHostFree(w->h_live);
-  if (w->rgexec) (void)hipGraphExecDestroy(w->rgexec);
+  (void)w->rounds_graph.release();
   if (w->h_rsp) (void)hipHostFree(w->h_rsp);
   if (w->h_rout) (void)hipHostFree(w->h_rout);
-  if (w->gexec) (void)hipGraphExecDestroy(w->gexec);
+  (void)w->step_graph.release();
   if (w->h_sp) (void)hipHostFree(w->h_sp);
   if (w->h_rec) (void)hipHostFree(w->h_rec);
   delete w;
@@ -300,17 +470,8 @@ int mlf_walkers_brackets_philox(mlf_walkers *w, double scale, int kind, double d
                                 uint64_t offset, uint64_t *next_offset) {
   if (!w || !next_offset) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
   if (kind < 0 || kind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
-  const bool need_axes = kind == DIR_REGION_ORIENTED || kind == DIR_REGION_RANDOM || kind == DIR_MIXTURE;
-  const bool need_live = kind == DIR_DIFFERENTIAL || kind == DIR_MIXTURE;
-  if ((need_axes && !w->have_axes) || (need_live && !w->have_live) ||
-      (kind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
-    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
-  WalkDirData dd{};
-  dd.axes = w->axes.as<double>();
-  dd.live = w->live.as<double>();
-  dd.nlive = w->nlive;
-  dd.std = w->std.as<double>();
-  launch_walk_brackets_philox(state_of(w), scale, kind, dirscale, dd, seed, offset, ctx_stream());
+  if (int rc = check_direction_data(w, kind)) return rc;
+  launch_walk_brackets_philox(state_of(w), scale, kind, dirscale, dir_data(w), seed, offset, ctx_stream());
   CK(hipGetLastError());
   *next_offset = offset + (uint64_t)w->P * (uint64_t)((w->d + 1) / 2 + 2);
   return 0;
@@ -383,24 +544,22 @@ int mlf_walkers_finish(mlf_walkers *w, double Lmin, const double *pnew, const do
     launch_walk_expand(state_of(w), w->blk.as<unsigned>(), w->pc.as<double>(), w->Lc.as<double>(), s);
     CK(hipGetLastError());
   }
-  return finish_common(w, Lmin, ringindex, rec);
+  return finish_common(w, Lmin, nullptr, ringindex, rec);
 }
 
 int mlf_walkers_finish_dev(mlf_walkers *w, double Lmin, int tkind, double ta, double tb, int lkind,
                            const double *aux, double sigma, int64_t ringindex, double *rec) {
   if (!w || !rec) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
   if (!w->proposed) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_finish_dev without a preceding mlf_walkers_propose");
-  if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return ctx_fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
-  if (lkind == 0 && !aux) return ctx_fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
-  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
-  hipStream_t s = ctx_stream();
-  const WalkState st = state_of(w);
-  if (aux)
-    if (int rc = upload(w->aux, aux, (size_t)w->d * 8, s)) return rc;
-  launch_walk_transform(st, tkind, ta, tb, s);
-  launch_loglike(lkind, st.pnew, w->d, w->P, w->aux.as<double>(), sigma, st.Lnew, s);
-  CK(hipGetLastError());
-  return finish_common(w, Lmin, ringindex, rec);
+  const StepEval ev{nullptr, tkind, ta, tb, lkind, aux, sigma};
+  return finish_common(w, Lmin, &ev, ringindex, rec);
+}
+
+int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, int64_t ringindex, double *rec) {
+  if (!w || !rec || !model) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w->proposed) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_finish_user without a preceding mlf_walkers_propose");
+  const StepEval ev{model};
+  return finish_common(w, Lmin, &ev, ringindex, rec);
 }
 
 int mlf_walkers_set_live(mlf_walkers *w, const double *us, const double *Ls, size_t nlive) {
@@ -451,190 +610,42 @@ int mlf_walkers_step_dev(mlf_walkers *w, double Lmin, double scale, int dirkind,
                          uint64_t offset, int tkind, double ta, double tb, int lkind, const double *aux, double sigma,
                          double *rec, uint64_t *next_offset) {
   if (!w || !rec || !next_offset) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (!w->have_liveL) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
-  if (dirkind < 0 || dirkind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
-  if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return ctx_fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
-  if (lkind == 0 && !aux) return ctx_fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
-  const bool need_axes = dirkind == DIR_REGION_ORIENTED || dirkind == DIR_REGION_RANDOM || dirkind == DIR_MIXTURE;
-  if ((need_axes && !w->have_axes) || (dirkind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
-    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
-  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
-  hipStream_t s = ctx_stream();
-  if (!w->ring.p) {
-    CK(w->ring.reserve(8));
-    CK(hipMemsetAsync(w->ring.p, 0, 8, s));
-  }
-  const size_t nrec = 10 + 2 * (size_t)w->d;
-  CK(w->rec.reserve(nrec * sizeof(double)));
-  if (aux)
-    if (int rc = upload(w->aux, aux, (size_t)w->d * 8, s)) return rc;
-  const WalkState st = state_of(w);
-  WalkDirData dd{};
-  dd.axes = w->axes.as<double>();
-  dd.live = w->live.as<double>();
-  dd.nlive = w->nlive;
-  dd.std = w->std.as<double>();
-  // one stream of kernels, one record back: step_back, restarts, new slices, proposal, likelihood, update, harvest
-  StepParams p{};
-  p.Lmin = Lmin;
-  p.scale = scale;
-  p.dirscale = dirscale;
-  p.r2 = w->r2;
-  p.seed = seed;
-  p.offset = offset;
-  launch_walk_prologue(st, w->live.as<double>(), w->liveL.as<double>(), w->nlive, dirkind, dd, tkind, ta, tb,
-                       w->flags.as<uint8_t>(), p, nullptr, s);
-  launch_loglike(lkind, st.pnew, w->d, w->P, w->aux.as<double>(), sigma, st.Lnew, s);
-  launch_walk_update(st, Lmin, layer_of(w), s);
-  launch_walk_harvest(st, 0, w->ring.as<long long>(), w->r2, w->rec.as<double>(), w->partials.as<double>(), s, nullptr,
-                      w->flags.as<uint8_t>());
-  CK(hipGetLastError());
-  if (int rc = download(rec, w->rec, nrec * sizeof(double), s)) return rc;
-  CK(hipStreamSynchronize(s));
-  const uint64_t per = (uint64_t)((w->d + 1) / 2 + 2);
-  *next_offset = offset + (uint64_t)w->P * (per > 64 ? per : 64);
-  return 0;
-}
-
-// user model (mlf_user.hip): the proposals of the acceptable walkers go through ONE mlf_user_rows launch that writes pnew and
-// Lnew (dw_update reads Lnew only where acceptable, and pnew only after a success, which needs acceptable: the rows of the
-// other walkers are not evaluated); without a transform the kernel copies unew into pnew
-int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, int64_t ringindex, double *rec) {
-  if (!w || !rec || !model) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (!w->proposed) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_finish_user without a preceding mlf_walkers_propose");
-  if (usermodel_dim(model) != w->d) return ctx_fail_arg(MLF_E_BADARG, "user model and walkers differ in dimensionality");
-  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
-  hipStream_t s = ctx_stream();
-  const WalkState st = state_of(w);
-  if (int rc = usermodel_rows(model, st.unew, w->P, st.acceptable, st.pnew, st.Lnew, s)) return rc;
-  CK(hipGetLastError());
-  return finish_common(w, Lmin, ringindex, rec);
+  return run_step(w, dirkind, StepEval{nullptr, tkind, ta, tb, lkind, aux, sigma}, StepParams{Lmin, scale, dirscale, w->r2, seed, offset},
+                  rec, next_offset);
 }
 
 int mlf_walkers_step_user(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                           uint64_t offset, mlf_usermodel *model, double *rec, uint64_t *next_offset) {
   if (!w || !rec || !next_offset || !model) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (!w->have_liveL) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
-  if (dirkind < 0 || dirkind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
-  if (usermodel_dim(model) != w->d) return ctx_fail_arg(MLF_E_BADARG, "user model and walkers differ in dimensionality");
-  const bool need_axes = dirkind == DIR_REGION_ORIENTED || dirkind == DIR_REGION_RANDOM || dirkind == DIR_MIXTURE;
-  if ((need_axes && !w->have_axes) || (dirkind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
-    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
-  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
-  hipStream_t s = ctx_stream();
-  if (!w->ring.p) {
-    CK(w->ring.reserve(8));
-    CK(hipMemsetAsync(w->ring.p, 0, 8, s));
-  }
-  const size_t nrec = 10 + 2 * (size_t)w->d;
-  CK(w->rec.reserve(nrec * sizeof(double)));
-  const WalkState st = state_of(w);
-  WalkDirData dd{};
-  dd.axes = w->axes.as<double>();
-  dd.live = w->live.as<double>();
-  dd.nlive = w->nlive;
-  dd.std = w->std.as<double>();
-  StepParams p{};
-  p.Lmin = Lmin;
-  p.scale = scale;
-  p.dirscale = dirscale;
-  p.r2 = w->r2;
-  p.seed = seed;
-  p.offset = offset;
-  // the sequence of mlf_walkers_step_dev; the prologue proposes without a transform (tkind -1)
-  launch_walk_prologue(st, w->live.as<double>(), w->liveL.as<double>(), w->nlive, dirkind, dd, -1, 0.0, 0.0,
-                       w->flags.as<uint8_t>(), p, nullptr, s);
-  if (int rc = usermodel_rows(model, st.unew, w->P, st.acceptable, st.pnew, st.Lnew, s)) return rc;
-  launch_walk_update(st, Lmin, layer_of(w), s);
-  launch_walk_harvest(st, 0, w->ring.as<long long>(), w->r2, w->rec.as<double>(), w->partials.as<double>(), s, nullptr,
-                      w->flags.as<uint8_t>());
-  CK(hipGetLastError());
-  if (int rc = download(rec, w->rec, nrec * sizeof(double), s)) return rc;
-  CK(hipStreamSynchronize(s));
-  const uint64_t per = (uint64_t)((w->d + 1) / 2 + 2);
-  *next_offset = offset + (uint64_t)w->P * (per > 64 ? per : 64);
-  return 0;
+  return run_step(w, dirkind, StepEval{model}, StepParams{Lmin, scale, dirscale, w->r2, seed, offset}, rec, next_offset);
 }
 
 int mlf_walkers_step_graph(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                            uint64_t offset, int tkind, double ta, double tb, int lkind, const double *aux, double sigma,
                            double *rec, uint64_t *next_offset) {
   if (!w || !rec || !next_offset) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (!w->have_liveL) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
-  if (dirkind < 0 || dirkind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
-  if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return ctx_fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
-  if (lkind == 0 && !aux) return ctx_fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
-  const bool need_axes = dirkind == DIR_REGION_ORIENTED || dirkind == DIR_REGION_RANDOM || dirkind == DIR_MIXTURE;
-  if ((need_axes && !w->have_axes) || (dirkind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
-    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
-  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
+  const StepEval ev{nullptr, tkind, ta, tb, lkind, aux, sigma};
+  if (int rc = check_step(w, dirkind, ev)) return rc;
   hipStream_t s = ctx_stream();
-  const size_t nrec = 10 + 2 * (size_t)w->d;
-  if (!w->ring.p) {
-    CK(w->ring.reserve(8));
-    CK(hipMemsetAsync(w->ring.p, 0, 8, s));
-  }
+  if (int rc = prepare_step(w, ev, s)) return rc;
+  const size_t nrec = step_nrec(w);
   if (!w->h_sp) {
     CK(hipHostMalloc(reinterpret_cast<void **>(&w->h_sp), sizeof(StepParams), hipHostMallocDefault));
     CK(hipHostMalloc(reinterpret_cast<void **>(&w->h_rec), nrec * sizeof(double), hipHostMallocDefault));
     CK(w->d_sp.reserve(sizeof(StepParams)));
   }
-  CK(w->rec.reserve(nrec * sizeof(double)));
-  CK(w->aux.reserve((size_t)w->d * 8));
-  if (aux)
-    if (int rc = upload(w->aux, aux, (size_t)w->d * 8, s)) return rc;
-  // everything a captured kernel argument depends on: a change means a new capture
-  auto bits = [](double v) {
-    unsigned long long u;
-    memcpy(&u, &v, sizeof u);
-    return u;
-  };
-  auto addr = [](const void *p) { return (unsigned long long)(uintptr_t)p; };
-  std::vector<unsigned long long> key = {
-      (unsigned long long)dirkind, (unsigned long long)tkind, bits(ta), bits(tb), (unsigned long long)lkind, bits(sigma),
-      (unsigned long long)(w->layer_kind + 1), (unsigned long long)w->layer_wrap, (unsigned long long)w->nlive,
-      addr(w->live.p), addr(w->liveL.p), addr(w->axes.p), addr(w->std.p), addr(w->lay_ctr.p), addr(w->lay_mat.p),
-      addr(w->lay_wrap.p), addr(w->aux.p), addr(w->rec.p), addr(w->pnew.p), addr(w->currentp.p)};
-  if (!w->gexec || key != w->gkey) {
-    if (w->gexec) {
-      CK(hipGraphExecDestroy(w->gexec));
-      w->gexec = nullptr;
-    }
-    const WalkState st = state_of(w);
-    WalkDirData dd{};
-    dd.axes = w->axes.as<double>();
-    dd.live = w->live.as<double>();
-    dd.nlive = w->nlive;
-    dd.std = w->std.as<double>();
-    const StepParams *sp = w->d_sp.as<StepParams>();
-    CK(hipStreamSynchronize(s));
-    CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    (void)hipMemcpyAsync(w->d_sp.p, w->h_sp, sizeof(StepParams), hipMemcpyHostToDevice, s);
-    launch_walk_prologue(st, w->live.as<double>(), w->liveL.as<double>(), w->nlive, dirkind, dd, tkind, ta, tb,
-                         w->flags.as<uint8_t>(), StepParams{}, sp, s);
-    launch_loglike(lkind, st.pnew, w->d, w->P, w->aux.as<double>(), sigma, st.Lnew, s);
-    launch_walk_update(st, 0.0, layer_of(w), s, sp);
-    launch_walk_harvest(st, 0, w->ring.as<long long>(), 0.0, w->rec.as<double>(), w->partials.as<double>(), s, sp,
-                        w->flags.as<uint8_t>());
-    (void)hipMemcpyAsync(w->h_rec, w->rec.p, nrec * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipGraph_t graph = nullptr;
-    CK(hipStreamEndCapture(s, &graph));
-    hipError_t e = hipGraphInstantiate(&w->gexec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return ctx_fail_hip(e, "hipGraphInstantiate", "mlf_walk_api.hip", __LINE__);
-    w->gkey = key;
-  }
-  w->h_sp->Lmin = Lmin;
-  w->h_sp->scale = scale;
-  w->h_sp->dirscale = dirscale;
-  w->h_sp->r2 = w->r2;
-  w->h_sp->seed = seed;
-  w->h_sp->offset = offset;
-  CK(hipGraphLaunch(w->gexec, s));
-  CK(hipStreamSynchronize(s));
+  std::vector<unsigned long long> key = step_key(w, dirkind, ev);
+  key.push_back(addr(w->rec.p));
+  *w->h_sp = StepParams{Lmin, scale, dirscale, w->r2, seed, offset};
+  if (int rc = replay(w->step_graph, std::move(key), s, [&](hipStream_t s) -> int {
+        CK(hipMemcpyAsync(w->d_sp.p, w->h_sp, sizeof(StepParams), hipMemcpyHostToDevice, s));
+        if (int rc = enqueue_step(w, dirkind, ev, StepParams{}, w->d_sp.as<StepParams>(), s)) return rc;
+        CK(hipMemcpyAsync(w->h_rec, w->rec.p, nrec * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+      }))
+    return rc;
   memcpy(rec, w->h_rec, nrec * sizeof(double));
-  const uint64_t per = (uint64_t)((w->d + 1) / 2 + 2);
-  *next_offset = offset + (uint64_t)w->P * (per > 64 ? per : 64);
+  *next_offset = offset + philox_per_call(w);
   return 0;
 }
 
@@ -642,28 +653,18 @@ int mlf_walkers_rounds_dev(mlf_walkers *w, double Lmin, double scale, int dirkin
                            uint64_t offset, int tkind, double ta, double tb, int lkind, const double *aux, double sigma,
                            int max_rounds, double *rec, double *round_rows, int *rounds, uint64_t *next_offset) {
   if (!w || !rec || !round_rows || !rounds || !next_offset) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (!w->have_liveL) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
-  if (dirkind < 0 || dirkind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
-  if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return ctx_fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
-  if (lkind == 0 && !aux) return ctx_fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
   const int force_memory_form = max_rounds < 0;   // test hook: every round through global memory (the first form of this path)
   if (force_memory_form) max_rounds = -max_rounds;
-  if (max_rounds < 1) return ctx_fail_arg(MLF_E_BADARG, "max_rounds must not be 0");
-  const bool need_axes = dirkind == DIR_REGION_ORIENTED || dirkind == DIR_REGION_RANDOM || dirkind == DIR_MIXTURE;
-  if ((need_axes && !w->have_axes) || (dirkind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
-    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
-  if (int rc = ensure_params(w, (size_t)w->d)) return rc;
+  const StepEval ev{nullptr, tkind, ta, tb, lkind, aux, sigma};
+  if (int rc = check_step(w, dirkind, ev, max_rounds)) return rc;
+  hipStream_t s = ctx_stream();
+  if (int rc = prepare_step(w, ev, s)) return rc;
   // the per-round flag / distance arrays are [max_rounds][P]: keep them within 64 MiB
   const size_t per_round = (size_t)w->P * 9;
   const size_t cap = ((size_t)64 << 20) / per_round;
   if ((size_t)max_rounds > cap) max_rounds = cap < 1 ? 1 : (int)cap;
   if (max_rounds > 4096) max_rounds = 4096;
-  hipStream_t s = ctx_stream();
-  if (!w->ring.p) {
-    CK(w->ring.reserve(8));
-    CK(hipMemsetAsync(w->ring.p, 0, 8, s));
-  }
-  const size_t nrec = 10 + 2 * (size_t)w->d;
+  const size_t nrec = step_nrec(w);
   const size_t nout = nrec + 5 * (size_t)max_rounds;
   if (!w->h_rsp) CK(hipHostMalloc(reinterpret_cast<void **>(&w->h_rsp), sizeof(StepParams), hipHostMallocDefault));
   if (w->h_rout_doubles < nout) {
@@ -680,26 +681,14 @@ int mlf_walkers_rounds_dev(mlf_walkers *w, double Lmin, double scale, int dirkin
   CK(w->r_last.reserve((size_t)w->P * sizeof(int)));
   const size_t nchunks = ((size_t)w->P + 1023) / 1024;
   if (nchunks > 1) CK(w->r_parts.reserve((size_t)max_rounds * nchunks * 5 * sizeof(double)));
-  CK(w->aux.reserve((size_t)w->d * 8));
-  if (aux)
-    if (int rc = upload(w->aux, aux, (size_t)w->d * 8, s)) return rc;
-  w->h_rsp->Lmin = Lmin;
-  w->h_rsp->scale = scale;
-  w->h_rsp->dirscale = dirscale;
-  w->h_rsp->r2 = w->r2;
-  w->h_rsp->seed = seed;
-  w->h_rsp->offset = offset;
-  const uint64_t per = (uint64_t)((w->d + 1) / 2 + 2);
+  *w->h_rsp = StepParams{Lmin, scale, dirscale, w->r2, seed, offset};
   RoundsArgs a{};
   a.w = state_of(w);
   a.live = w->live.as<double>();
   a.Ls = w->liveL.as<double>();
   a.nlive = w->nlive;
   a.dirkind = dirkind;
-  a.dd.axes = w->axes.as<double>();
-  a.dd.live = w->live.as<double>();
-  a.dd.nlive = w->nlive;
-  a.dd.std = w->std.as<double>();
+  a.dd = dir_data(w);
   a.tkind = tkind;
   a.ta = ta;
   a.tb = tb;
@@ -719,42 +708,20 @@ int mlf_walkers_rounds_dev(mlf_walkers *w, double Lmin, double scale, int dirkin
   a.rec = w->r_out.as<double>();
   a.rows = w->r_out.as<double>() + nrec;
   a.max_rounds = max_rounds;
-  a.per_call = (unsigned long long)w->P * (per > 64 ? per : 64);
-  // Everything a captured argument depends on; the values that change from call to call (threshold, scale, radius, seed,
-  // offset) travel through the pinned parameter block.  A change (new region: layer buffers, radius-independent) means a new capture
-  auto bits = [](double v) {
-    unsigned long long u;
-    memcpy(&u, &v, sizeof u);
-    return u;
-  };
-  auto addr = [](const void *p) { return (unsigned long long)(uintptr_t)p; };
-  std::vector<unsigned long long> key = {
-      (unsigned long long)dirkind, (unsigned long long)tkind, bits(ta), bits(tb), (unsigned long long)lkind, bits(sigma),
-      (unsigned long long)(w->layer_kind + 1), (unsigned long long)w->layer_wrap, (unsigned long long)w->nlive,
-      (unsigned long long)max_rounds, (unsigned long long)force_memory_form, (unsigned long long)nout, bits(w->r2),
-      addr(w->live.p), addr(w->liveL.p), addr(w->axes.p), addr(w->std.p), addr(w->lay_ctr.p), addr(w->lay_mat.p),
-      addr(w->lay_wrap.p), addr(w->aux.p), addr(w->r_out.p), addr(w->pnew.p), addr(w->currentp.p), addr(w->r_flags.p),
-      addr(w->r_dist2.p), addr(w->r_last.p), addr(w->r_parts.p), addr(w->r_ctl.p), addr(w->r_sp.p), addr(w->h_rout), addr(w->h_rsp), addr(w->flags.p),
-      addr(w->ring.p)};
-  if (!w->rgexec || key != w->rgkey) {
-    if (w->rgexec) {
-      CK(hipGraphExecDestroy(w->rgexec));
-      w->rgexec = nullptr;
-    }
-    CK(hipStreamSynchronize(s));
-    CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    (void)hipMemcpyAsync(w->r_sp.p, w->h_rsp, sizeof(StepParams), hipMemcpyHostToDevice, s);
-    launch_walk_rounds(a, s);
-    (void)hipMemcpyAsync(w->h_rout, w->r_out.p, nout * sizeof(double), hipMemcpyDeviceToHost, s);
-    hipGraph_t graph = nullptr;
-    CK(hipStreamEndCapture(s, &graph));
-    hipError_t e = hipGraphInstantiate(&w->rgexec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return ctx_fail_hip(e, "hipGraphInstantiate", "mlf_walk_api.hip", __LINE__);
-    w->rgkey = key;
-  }
-  CK(hipGraphLaunch(w->rgexec, s));
-  CK(hipStreamSynchronize(s));
+  a.per_call = philox_per_call(w);
+  // the values that change from call to call (threshold, scale, seed, offset) travel through the pinned parameter block
+  std::vector<unsigned long long> key = step_key(w, dirkind, ev);
+  key.insert(key.end(), {(unsigned long long)max_rounds, (unsigned long long)force_memory_form, (unsigned long long)nout,
+                         bits(w->r2), addr(w->r_out.p), addr(w->r_flags.p), addr(w->r_dist2.p), addr(w->r_last.p),
+                         addr(w->r_parts.p), addr(w->r_ctl.p), addr(w->r_sp.p), addr(w->h_rout), addr(w->h_rsp),
+                         addr(w->flags.p), addr(w->ring.p)});
+  if (int rc = replay(w->rounds_graph, std::move(key), s, [&](hipStream_t s) -> int {
+        CK(hipMemcpyAsync(w->r_sp.p, w->h_rsp, sizeof(StepParams), hipMemcpyHostToDevice, s));
+        launch_walk_rounds(a, s);
+        CK(hipMemcpyAsync(w->h_rout, w->r_out.p, nout * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+      }))
+    return rc;
   const int R = (int)w->h_rout[4];
   if (w->h_rout[5] != 0.0) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_rounds_dev: a walker gave up waiting for the ring walker's rounds");
   if (R < 1 || R > max_rounds) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_rounds_dev: the device reported an impossible round count");

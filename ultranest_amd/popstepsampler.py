@@ -337,10 +337,13 @@ class _Walkers(object):
         return out[:nacc.value]
 
     def _record(self, rec, nparams):
+        """The record of a finish call, or of a whole step on the device: one double more, the ring index after the step."""
         d = self.ndim
-        return dict(found=rec[0] == 1.0, L=rec[1], left=rec[2], right=rec[3], nc=int(rec[4]), nmovable=int(rec[5]),
-                    nsuccess=int(rec[6]), nfar=rec[7], sumlog=rec[8], u=rec[9:9 + d].copy(),
-                    p=rec[9 + d:9 + d + nparams].copy())
+        out = dict(found=rec[0] == 1.0, L=rec[1], left=rec[2], right=rec[3], nc=int(rec[4]), nmovable=int(rec[5]),
+                   nsuccess=int(rec[6]), nfar=rec[7], sumlog=rec[8], u=rec[9:9 + d].copy(), p=rec[9 + d:9 + d + nparams].copy())
+        if len(rec) > 9 + d + nparams:
+            out["ring"] = int(rec[9 + d + nparams])
+        return out
 
     def finish(self, Lmin, pnew, Lnew, ringindex):
         pnew, Lnew = f64(pnew), f64(Lnew)
@@ -376,16 +379,9 @@ class _Walkers(object):
 
     def step_user(self, Lmin, scale, kind, dirscale, rng, model, with_transform):
         """`step_dev` (graph=False) with a user model."""
-        self.nparams = self.ndim
-        rec = np.empty(10 + 2 * self.ndim)
-        nxt = ctypes.c_uint64(0)
-        check(_lib.lib().mlf_walkers_step_user(self._h, float(Lmin), float(scale), int(kind), float(dirscale),
-                                               ctypes.c_uint64(rng.seed), ctypes.c_uint64(rng.offset),
-                                               model.handle(with_transform), ptr(rec), ctypes.byref(nxt)))
-        rng.offset = nxt.value
-        out = self._record(rec, self.ndim)
-        out["ring"] = int(rec[9 + 2 * self.ndim])
-        return out
+        rec = self._whole_step(_lib.lib().mlf_walkers_step_user, Lmin, scale, kind, dirscale, rng,
+                               (model.handle(with_transform),))
+        return self._record(rec, self.ndim)
 
     def set_live(self, us, Ls):
         us, Ls = f64(us), f64(Ls)
@@ -395,46 +391,43 @@ class _Walkers(object):
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         check(_lib.lib().mlf_walkers_update_live(self._h, ptr(rows), len(rows), ptr(f64(us_rows)), ptr(f64(Ls_rows))))
 
+    def _whole_step(self, fn, Lmin, scale, kind, dirscale, rng, args, outs=()):
+        """One call of a whole-step entry point, fn(handle, Lmin, scale, kind, dirscale, seed, offset, *args, rec, *outs,
+        next_offset): advances rng.offset and returns the 10 + 2 d record (the ring index after the step last)."""
+        self.nparams = self.ndim
+        rec = np.empty(10 + 2 * self.ndim)
+        nxt = ctypes.c_uint64(0)
+        check(fn(self._h, float(Lmin), float(scale), int(kind), float(dirscale), ctypes.c_uint64(rng.seed),
+                 ctypes.c_uint64(rng.offset), *args, ptr(rec), *outs, ctypes.byref(nxt)))
+        rng.offset = nxt.value
+        return rec
+
+    @staticmethod
+    def _builtin_args(tspec, lspec):
+        (tkind, ta, tb), (lkind, aux, sigma) = tspec, lspec
+        return int(tkind), float(ta), float(tb), int(lkind), ptr(None if aux is None else f64(aux)), float(sigma)
+
     def step_dev(self, Lmin, scale, kind, dirscale, rng, tspec, lspec, graph=True):
         """Whole sampler step on the device (graph: replayed as one hipGraph launch); returns the record
         (with the ring index after the step)."""
-        self.nparams = self.ndim
-        tkind, ta, tb = tspec
-        lkind, aux, sigma = lspec
-        rec = np.empty(10 + 2 * self.ndim)
-        nxt = ctypes.c_uint64(0)
         fn = _lib.lib().mlf_walkers_step_graph if graph else _lib.lib().mlf_walkers_step_dev
-        check(fn(self._h, float(Lmin), float(scale), int(kind), float(dirscale), ctypes.c_uint64(rng.seed),
-                 ctypes.c_uint64(rng.offset), int(tkind), float(ta), float(tb), int(lkind),
-                 ptr(None if aux is None else f64(aux)), float(sigma), ptr(rec), ctypes.byref(nxt)))
-        rng.offset = nxt.value
-        out = self._record(rec, self.ndim)
-        out["ring"] = int(rec[9 + 2 * self.ndim])
-        return out
+        rec = self._whole_step(fn, Lmin, scale, kind, dirscale, rng, self._builtin_args(tspec, lspec))
+        return self._record(rec, self.ndim)
 
     def rounds_dev(self, Lmin, scale, kind, dirscale, rng, tspec, lspec, max_rounds):
         """Whole sampler steps on the device until the walker under the ring index has finished (or `max_rounds`):
         ``mlf_walkers_rounds_dev``.  Returns the record of the LAST round (with "ring" and "rounds") and the per-round
         statistics rows (rounds, 5): what `rounds` consecutive `step_dev` calls would have returned, one host round trip."""
-        self.nparams = self.ndim
-        tkind, ta, tb = tspec
-        lkind, aux, sigma = lspec
-        rec = np.empty(10 + 2 * self.ndim)
         if getattr(self, "_round_rows", None) is None or len(self._round_rows) < abs(max_rounds):
             self._round_rows = np.empty((abs(int(max_rounds)), 5))
-        nxt = ctypes.c_uint64(0)
         nrounds = ctypes.c_int(0)
-        check(_lib.lib().mlf_walkers_rounds_dev(
-            self._h, float(Lmin), float(scale), int(kind), float(dirscale), ctypes.c_uint64(rng.seed), ctypes.c_uint64(rng.offset),
-            int(tkind), float(ta), float(tb), int(lkind), ptr(None if aux is None else f64(aux)), float(sigma), int(max_rounds),
-            ptr(rec), ptr(self._round_rows), ctypes.byref(nrounds), ctypes.byref(nxt)))
-        rng.offset = nxt.value
-        R = nrounds.value
-        rows = self._round_rows[:R]
-        d = self.ndim
-        out = dict(found=rec[0] == 1.0, L=rec[1], left=rec[2], right=rec[3], u=rec[9:9 + d].copy(), p=rec[9 + d:9 + 2 * d].copy(),
-                   ring=int(rec[9 + 2 * d]), rounds=R)
-        return out, rows
+        rec = self._whole_step(_lib.lib().mlf_walkers_rounds_dev, Lmin, scale, kind, dirscale, rng,
+                               self._builtin_args(tspec, lspec) + (int(max_rounds),),
+                               (ptr(self._round_rows), ctypes.byref(nrounds)))
+        rec[4:9] = 0        # [4] holds the number of rounds, [5 ...] nothing: the statistics come per round, in the rows
+        out = self._record(rec, self.ndim)
+        out["rounds"] = R = nrounds.value
+        return out, self._round_rows[:R]
 
     def export(self):
         """Host copies of the resident state (tests, debugging)."""
