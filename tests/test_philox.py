@@ -45,11 +45,15 @@ def test_restatement_ball_is_uniform():
 
 
 def _region(kind, n, d, seed):
-    import ultranest_amd.mlfriends as m
-    from ultranest_amd.regions import DeviceRNG
     rng = np.random.RandomState(seed)
     u = 0.5 + 0.08 * rng.normal(size=(n, d)) * np.linspace(0.5, 1.5, d)
     u = u[np.logical_and(u > 0, u < 1).all(axis=1)]
+    return _region_of(kind, u, rng)
+
+
+def _region_of(kind, u, rng):
+    import ultranest_amd.mlfriends as m
+    from ultranest_amd.regions import DeviceRNG
     layer = m.AffineLayer()
     layer.optimize(u, u)
     region = getattr(m, kind)(u, layer)
@@ -223,8 +227,23 @@ def test_sampling_from_points_matches_restatement_and_is_uniform(d):
 def test_device_refill_equals_sample_then_callbacks(method_name):
     """mlf_region_refill = the same draw as region.sample() followed by the prior transform, the
     likelihood and the L > Lmin cut, with only the survivors copied back."""
+    _check_refill_equals_sample(*_region("MLFriends", 400, 4, 77), method_name)
+
+
+@pytest.mark.gpu
+def test_device_refill_compacts_a_thin_ellipsoid_batch():
+    """the same with method 1 for live points along a closed curve: the wrapping ellipsoid is mostly empty, under a quarter of
+    its draws are accepted, and the refill compacts them before the evaluation (a denser batch is evaluated where it was drawn)"""
+    rng = np.random.RandomState(78)
+    t = rng.uniform(0, 2 * np.pi, 400)
+    u = 0.5 + 0.2 * np.stack([np.cos(t), np.sin(t), np.cos(2 * t), np.sin(2 * t)], axis=1) + 0.02 * rng.normal(size=(400, 4))
+    nc = _check_refill_equals_sample(*_region_of("MLFriends", u, rng), "sample_from_wrapping_ellipsoid")
+    assert 0 < 4 * nc < 30000
+
+
+def _check_refill_equals_sample(region, DeviceRNG, method_name):
+    """returns the number of likelihood evaluations of the refill (= accepted draws of its batch of 30000)"""
     from ultranest_amd import likelihoods
-    region, DeviceRNG = _region("MLFriends", 400, 4, 77)
     region.current_sampling_method = getattr(region, method_name)
     loglike = likelihoods.GaussLikelihood(0.5, 0.08, 4)
     nsamples = 30000
@@ -246,6 +265,7 @@ def test_device_refill_equals_sample_then_callbacks(method_name):
     assert (L > Lmin).all() and len(u) > 100
     # callbacks without a device form: the caller is told to take the host route
     assert region.refill(100, Lmin, lambda x: x, loglike) is None
+    return nc
 
 
 @pytest.mark.gpu

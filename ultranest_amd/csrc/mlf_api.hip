@@ -2624,6 +2624,8 @@ int mlf_region_set_sampling_data(mlf_region *r, const double *invT, const double
   return 0;
 }
 
+}  // extern "C"
+
 namespace {
 
 // neighbour test of t-space points against the resident live points (MFMA pre-filter when it applies)
@@ -2635,17 +2637,6 @@ int region_scan_mask(mlf_region *r, const double *d_t, long long np, uint8_t *d_
   ScanArgs a = scan_args(region_live(r), d_t, r->d, 0, np, SCAN_MASK);
   a.out_mask = d_mask;
   CK(launch_scan(r->dp, a, s));
-  return 0;
-}
-
-// w = t . invT + ctr (+ unwrap) and the cube flags of `n` rows
-int region_untransform(mlf_region *r, const double *t, long long n, double *w, uint8_t *in_cube, hipStream_t s) {
-  const double *wrap = r->has_wrap ? r->wrap.as<double>() : nullptr;
-  if (r->d <= 128 && r->s_invT_pad.p)
-    CK(launch_rows_affine(t, n, r->d, r->s_invT_pad.as<double>(), r->lay_ctr.as<double>(), wrap, w, in_cube, s));
-  else
-    launch_untransform_rows(t, n, r->d, r->s_invT.as<double>(), r->lay_ctr.as<double>(), wrap, w, in_cube, s);
-  CK(hipGetLastError());
   return 0;
 }
 
@@ -2674,160 +2665,66 @@ int region_ellipsoid_gate(mlf_region *r, const double *d_pts, size_t np, uint8_t
   return 0;
 }
 
-// methods 2 and 3 of MLFriends.sample: proposals are born in t-space
-int region_sample_tspace(mlf_region *r, int method, long long n, uint64_t seed, uint64_t offset, double *out,
-                         size_t capacity, size_t *naccepted, uint64_t *next_offset, bool fetch) {
-  Ctx &c = g_ctx;
-  hipStream_t s = c.stream;
-  const int d = r->d;
-  const int nblk = (int)((n + 255) / 256);
-  CK(r->gen.reserve((size_t)n * d * sizeof(double)));
-  CK(r->gen2.reserve((size_t)n * d * sizeof(double)));
-  CK(r->smask.reserve((size_t)n));
-  CK(r->cube.reserve((size_t)n));
-  CK(r->blk.reserve(((size_t)nblk + 1) * sizeof(unsigned)));
-  double *t = r->gen.as<double>();
-  uint8_t *mask = r->smask.as<uint8_t>();
-  if (method == 2) {
-    launch_generate_tbox(t, n, d, r->s_lo.as<double>(), r->s_hi.as<double>(), std::sqrt(r->r2), seed, offset, s);
-    CK(hipGetLastError());
-    *next_offset = offset + (uint64_t)((n * d + 1) / 2);
-    if (int rc = region_scan_mask(r, t, n, mask, s)) return rc;
-  } else {   // method 3
-    // Reference order (:1072-1094, :1154-1160): multiplicity of every proposal -> thinning -> untransform -> cube and ellipsoid
-    // tests.  Every one of these is a function of the proposal alone (the thinning uniform is drawn with it), so the accepted set
-    // does not depend on their order: the cheap tests run FIRST, on the whole batch (untransform + cube 0.2 ms, ellipsoid 0.15 ms
-    // per 2^20 x 50), and the multiplicity -- the exact count over all live points, 22 ms for the whole batch, the one stage that
-    // cannot stop at the first hit -- is taken of their survivors only (a few per cent at C5).
-    CK(r->s_thin.reserve((size_t)n * sizeof(double)));
-    CK(r->s_gate.reserve((size_t)n));
-    launch_generate_around_points(t, r->s_thin.as<double>(), n, d, r->refR.as<double>(), r->n, r->dp, r->r2, seed,
-                                  offset, s);
-    CK(hipGetLastError());
-    *next_offset = offset + (uint64_t)n * (uint64_t)((d + 1) / 2 + 2);
-    double *wall = r->gen2.as<double>();
-    if (int rc = region_untransform(r, t, n, wall, r->cube.as<uint8_t>(), s)) return rc;
-    if (int rc = region_ellipsoid_gate(r, wall, (size_t)n, r->s_gate.as<uint8_t>(), s)) return rc;
-    launch_mask_and(r->s_gate.as<uint8_t>(), r->cube.as<uint8_t>(), n, s);
-    launch_mask_offsets(r->s_gate.as<uint8_t>(), n, r->blk.as<unsigned>(), s);
-    CK(hipGetLastError());
-    unsigned k0 = 0;
-    CK(hipMemcpyAsync(&k0, r->blk.as<unsigned>() + nblk, sizeof k0, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    *naccepted = 0;
-    if (k0 == 0) return 0;
-    CK(r->s_tc.reserve((size_t)k0 * d * sizeof(double)));
-    CK(r->s_wc.reserve((size_t)k0 * d * sizeof(double)));
-    CK(r->s_thc.reserve((size_t)k0 * sizeof(double)));
-    CK(r->s_count.reserve((size_t)k0 * sizeof(long long)));
-    // (the offsets of this mask are in blk already: launch_mask_offsets above)
-    launch_scatter(t, r->s_gate.as<uint8_t>(), n, d, r->blk.as<unsigned>(), r->s_tc.as<double>(), k0, s);
-    launch_scatter(wall, r->s_gate.as<uint8_t>(), n, d, r->blk.as<unsigned>(), r->s_wc.as<double>(), k0, s);
-    launch_scatter(r->s_thin.as<double>(), r->s_gate.as<uint8_t>(), n, 1, r->blk.as<unsigned>(), r->s_thc.as<double>(), k0, s);
-    // multiplicity: how many balls contain the proposal (no early exit, reference :1087-1088)
-    ScanArgs a = scan_args(region_live(r), r->s_tc.as<double>(), d, 0, k0, SCAN_COUNT);
-    a.out_idx = r->s_count.as<long long>();
-    CK(launch_scan(r->dp, a, s));
-    launch_thin_by_multiplicity(r->s_count.as<long long>(), r->s_thc.as<double>(), k0, mask, s);
-    CK(hipGetLastError());
-    CK(r->sout.reserve(capacity * (size_t)d * sizeof(double)));
-    const unsigned cap3 = capacity > 0xffffffffu ? 0xffffffffu : (unsigned)capacity;
-    launch_compact(r->s_wc.as<double>(), mask, k0, d, r->blk.as<unsigned>(), r->sout.as<double>(), cap3, s);
-    CK(hipGetLastError());
-    unsigned count3 = 0;
-    const int nblk0 = (int)((k0 + 255) / 256);
-    CK(hipMemcpyAsync(&count3, r->blk.as<unsigned>() + nblk0, sizeof count3, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    const size_t take3 = count3 < cap3 ? count3 : cap3;
-    if (take3 && fetch) {
-      CK(hipMemcpyAsync(out, r->sout.p, take3 * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s));
-      CK(hipStreamSynchronize(s));
-    }
-    *naccepted = take3;
-    return 0;
-  }
-  // survivors of the neighbour test, compacted; everything after works on those rows only
-  launch_compact(t, mask, n, d, r->blk.as<unsigned>(), r->gen2.as<double>(), (unsigned)n, s);
+// methods 2 and 3 after the draw: w = t . invT + ctr (+ unwrap) of `n` t-space rows, gate = w inside the unit cube and the
+// wrapping ellipsoid
+int region_cube_gate(mlf_region *r, const double *t, long long n, double *w, uint8_t *gate, hipStream_t s) {
+  uint8_t *in_cube = r->cube.as<uint8_t>();
+  const double *wrap = r->has_wrap ? r->wrap.as<double>() : nullptr;
+  if (r->d <= 128 && r->s_invT_pad.p)
+    CK(launch_rows_affine(t, n, r->d, r->s_invT_pad.as<double>(), r->lay_ctr.as<double>(), wrap, w, in_cube, s));
+  else
+    launch_untransform_rows(t, n, r->d, r->s_invT.as<double>(), r->lay_ctr.as<double>(), wrap, w, in_cube, s);
   CK(hipGetLastError());
-  unsigned k1 = 0;
-  CK(hipMemcpyAsync(&k1, r->blk.as<unsigned>() + nblk, sizeof k1, hipMemcpyDeviceToHost, s));
-  CK(hipStreamSynchronize(s));
-  *naccepted = 0;
-  if (k1 == 0) return 0;
-  double *w = r->gen.as<double>();   // the t-space batch is not needed any more
-  if (int rc = region_untransform(r, r->gen2.as<double>(), k1, w, r->cube.as<uint8_t>(), s)) return rc;
-  if (int rc = region_ellipsoid_gate(r, w, k1, mask, s)) return rc;
-  launch_mask_and(mask, r->cube.as<uint8_t>(), k1, s);
-  CK(r->sout.reserve(capacity * (size_t)d * sizeof(double)));
-  const unsigned cap = capacity > 0xffffffffu ? 0xffffffffu : (unsigned)capacity;
-  launch_compact(w, mask, k1, d, r->blk.as<unsigned>(), r->sout.as<double>(), cap, s);
-  CK(hipGetLastError());
-  unsigned count = 0;
-  const int nblk1 = (int)((k1 + 255) / 256);
-  CK(hipMemcpyAsync(&count, r->blk.as<unsigned>() + nblk1, sizeof count, hipMemcpyDeviceToHost, s));
-  CK(hipStreamSynchronize(s));
-  const size_t take = count < cap ? count : cap;
-  if (take && fetch) {
-    CK(hipMemcpyAsync(out, r->sout.p, take * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-  }
-  *naccepted = take;
+  if (int rc = region_ellipsoid_gate(r, w, (size_t)n, gate, s)) return rc;
+  launch_mask_and(gate, in_cube, n, s);
   return 0;
 }
 
-}  // namespace
+// what region_draw leaves on the device: n rows of d doubles in cube space, accepted where member[i] != 0 (n = 0: none)
+struct Drawn {
+  const double *rows = nullptr;
+  const uint8_t *member = nullptr;
+  long long n = 0;
+};
 
-// fetch = false leaves the accepted rows in r->sout (device) for mlf_region_refill
-// masked_ok (with fetch = false): methods 0 and 1 may leave the batch where it was drawn (r->gen, all `nsamples` rows) with the
-// membership mask in r->smask instead of compacting the accepted rows into r->sout; *masked tells which of the two happened
-static int region_sample_impl(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double *out,
-                              size_t capacity, size_t *naccepted, uint64_t *next_offset, bool fetch, bool masked_ok = false,
-                              bool *masked = nullptr);
-
-int mlf_region_sample(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double *out,
-                      size_t capacity, size_t *naccepted, uint64_t *next_offset) {
-  if (!out) return fail_arg(MLF_E_BADARG, "null pointer");
-  return region_sample_impl(r, method, nsamples, seed, offset, out, capacity, naccepted, next_offset, true);
-}
-
-static int region_sample_impl(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset,
-                      double *out, size_t capacity, size_t *naccepted, uint64_t *next_offset, bool fetch, bool masked_ok,
-                      bool *masked) {
-  if (masked) *masked = false;
-  if (!r || !naccepted || !next_offset) return fail_arg(MLF_E_BADARG, "null pointer");
+// MLFriends.sample on the device: `nsamples` proposals of `method` (0 cube, 1 wrapping ellipsoid, 2 t-space box, 3 around the live
+// points) from Philox counter `offset` on, through the region's tests; *next_offset = the first counter not used.  The batch stays
+// on the device as its last stage left it, not compacted; r->blk holds the offsets of any mask of up to nsamples rows.
+int region_draw(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, Drawn *b, uint64_t *next_offset) {
+  if (!r || !next_offset) return fail_arg(MLF_E_BADARG, "null pointer");
   if (!r->ready) return fail_arg(MLF_E_STATE, "region used before mlf_region_set");
   if (method < 0 || method > 3)
     return fail_arg(MLF_E_BADARG, "method must be 0 (cube), 1 (wrapping ellipsoid), 2 (t-space box) or 3 (live points)");
   if (method == 1 && !r->axes_ready) return fail_arg(MLF_E_STATE, "mlf_region_set_axes not called");
   if (method >= 2 && (!r->use_scan || !r->sampling_ready))
     return fail_arg(MLF_E_STATE, "mlf_region_set_sampling_data not called (or region without live points)");
-  *naccepted = 0;
+  *b = Drawn{};
   *next_offset = offset;
-  if (nsamples == 0 || capacity == 0) return 0;
-  if (method >= 2)
-    return region_sample_tspace(r, method, (long long)nsamples, seed, offset, out, capacity, naccepted, next_offset, fetch);
-  Ctx &c = g_ctx;
-  hipStream_t s = c.stream;
+  if (nsamples == 0) return 0;
+  hipStream_t s = g_ctx.stream;
   const long long n = (long long)nsamples;
   const int d = r->d;
-  const int nblk = (int)((n + 255) / 256);
   CK(r->gen.reserve((size_t)n * d * sizeof(double)));
   CK(r->smask.reserve((size_t)n));
-  CK(r->blk.reserve(((size_t)nblk + 1) * sizeof(unsigned)));
-  CK(r->sout.reserve(capacity * (size_t)d * sizeof(double)));
-  const uint8_t *pregate = nullptr;
+  CK(r->blk.reserve(((size_t)(n + 255) / 256 + 1) * sizeof(unsigned)));
+  double *gen = r->gen.as<double>();
+  uint8_t *mask = r->smask.as<uint8_t>();
   if (method == 0) {
-    launch_generate_cube(r->gen.as<double>(), n * d, seed, offset, s);
+    CK(launch_generate_cube(gen, n * d, seed, offset, s));
     *next_offset = offset + (uint64_t)((n * d + 1) / 2);
-  } else {
-    CK(r->cube.reserve((size_t)n));
+    if (int rc = region_inside_enqueue(r, gen, nsamples, mask, s, nullptr, nullptr, nullptr)) return rc;
+    *b = {gen, mask, n};
+    return 0;
+  }
+  CK(r->cube.reserve((size_t)n));
+  if (method == 1) {
     *next_offset = offset + (uint64_t)n * (uint64_t)((d + 1) / 2 + 1);
     if (d <= 128 && r->ax_pad.p) {   // draws, axes product, centre and cube test in one launch: the batch is written once
-      CK(launch_generate_ellipsoid(r->gen.as<double>(), n, d, r->enlarge, r->ax_pad.as<double>(), r->ell_ctr.as<double>(),
-                                   r->cube.as<uint8_t>(), seed, offset, s));
+      CK(launch_generate_ellipsoid(gen, n, d, r->enlarge, r->ax_pad.as<double>(), r->ell_ctr.as<double>(), r->cube.as<uint8_t>(),
+                                   seed, offset, s));
     } else {
       CK(r->gen2.reserve((size_t)n * d * sizeof(double)));
-      launch_generate_ball(r->gen2.as<double>(), n, d, r->enlarge, seed, offset, s);
+      CK(launch_generate_ball(r->gen2.as<double>(), n, d, r->enlarge, seed, offset, s));
       PrepArgs pa{};
       pa.pts = r->gen2.as<double>();
       pa.np = n;
@@ -2835,93 +2732,110 @@ static int region_sample_impl(mlf_region *r, int method, size_t nsamples, uint64
       pa.do_tr = 1;
       pa.lay_ctr = r->ax_zero.as<double>();
       pa.lay_Tt = r->ax_mat.as<double>();
-      pa.t_out = r->gen.as<double>();
+      pa.t_out = gen;
       pa.ldt = d;
       CK(launch_prep(r->dp, pa, s));
-      launch_center_and_cube(r->gen.as<double>(), n, d, r->ell_ctr.as<double>(), r->cube.as<uint8_t>(), s);
+      launch_center_and_cube(gen, n, d, r->ell_ctr.as<double>(), r->cube.as<uint8_t>(), s);
+      CK(hipGetLastError());
     }
-    pregate = r->cube.as<uint8_t>();
+    if (int rc = region_inside_enqueue(r, gen, nsamples, mask, s, nullptr, nullptr, r->cube.as<uint8_t>())) return rc;
+    *b = {gen, mask, n};
+    return 0;
   }
+  // methods 2 and 3: proposals are born in t-space
+  CK(r->gen2.reserve((size_t)n * d * sizeof(double)));
+  if (method == 2) {
+    CK(launch_generate_tbox(gen, n, d, r->s_lo.as<double>(), r->s_hi.as<double>(), std::sqrt(r->r2), seed, offset, s));
+    *next_offset = offset + (uint64_t)((n * d + 1) / 2);
+    if (int rc = region_scan_mask(r, gen, n, mask, s)) return rc;
+    // survivors of the neighbour test, compacted; everything after works on those rows only
+    const Compaction nearby(mask, n, r->blk.as<unsigned>(), s);
+    nearby.scatter(gen, d, r->gen2.as<double>(), nsamples);
+    size_t k1 = 0;
+    CK(nearby.count(nsamples, &k1));
+    if (k1 == 0) return 0;
+    // the t-space batch is not needed any more: gen takes the cube-space rows
+    if (int rc = region_cube_gate(r, r->gen2.as<double>(), (long long)k1, gen, mask, s)) return rc;
+    *b = {gen, mask, (long long)k1};
+    return 0;
+  }
+  // Method 3.  Reference order (:1072-1094, :1154-1160): multiplicity of every proposal -> thinning -> untransform -> cube and
+  // ellipsoid tests.  Every one of these is a function of the proposal alone (the thinning uniform is drawn with it), so the
+  // accepted set does not depend on their order: the cheap tests run FIRST, on the whole batch (untransform + cube 0.2 ms,
+  // ellipsoid 0.15 ms per 2^20 x 50), and the multiplicity -- the exact count over all live points, 22 ms for the whole batch, the
+  // one stage that cannot stop at the first hit -- is taken of their survivors only (a few per cent at C5).
+  CK(r->s_thin.reserve((size_t)n * sizeof(double)));
+  CK(r->s_gate.reserve((size_t)n));
+  CK(launch_generate_around_points(gen, r->s_thin.as<double>(), n, d, r->refR.as<double>(), r->n, r->dp, r->r2, seed, offset, s));
+  *next_offset = offset + (uint64_t)n * (uint64_t)((d + 1) / 2 + 2);
+  double *wall = r->gen2.as<double>();
+  if (int rc = region_cube_gate(r, gen, n, wall, r->s_gate.as<uint8_t>(), s)) return rc;
+  const Compaction cheap(r->s_gate.as<uint8_t>(), n, r->blk.as<unsigned>(), s);
+  size_t k0 = 0;
+  CK(cheap.count(nsamples, &k0));
+  if (k0 == 0) return 0;
+  CK(r->s_tc.reserve(k0 * d * sizeof(double)));
+  CK(r->s_wc.reserve(k0 * d * sizeof(double)));
+  CK(r->s_thc.reserve(k0 * sizeof(double)));
+  CK(r->s_count.reserve(k0 * sizeof(long long)));
+  cheap.scatter(gen, d, r->s_tc.as<double>(), k0);
+  cheap.scatter(wall, d, r->s_wc.as<double>(), k0);
+  cheap.scatter(r->s_thin.as<double>(), 1, r->s_thc.as<double>(), k0);
+  // multiplicity: how many balls contain the proposal (no early exit, reference :1087-1088)
+  ScanArgs a = scan_args(region_live(r), r->s_tc.as<double>(), d, 0, (long long)k0, SCAN_COUNT);
+  a.out_idx = r->s_count.as<long long>();
+  CK(launch_scan(r->dp, a, s));
+  launch_thin_by_multiplicity(r->s_count.as<long long>(), r->s_thc.as<double>(), (long long)k0, mask, s);
   CK(hipGetLastError());
-  if (int rc = region_inside_enqueue(r, r->gen.as<double>(), nsamples, r->smask.as<uint8_t>(), s, nullptr,
-                                     nullptr, pregate))
-    return rc;
-  const unsigned cap = capacity > 0xffffffffu ? 0xffffffffu : (unsigned)capacity;
-  unsigned count = 0;
-  if (masked_ok && !fetch && capacity >= nsamples) {
-    // the refill works on the batch where it is: count the accepted rows; only a thin batch (under a quarter accepted) is
-    // worth compacting before the prior transform and the likelihood run over it
-    launch_mask_offsets(r->smask.as<uint8_t>(), n, r->blk.as<unsigned>(), s);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&count, r->blk.as<unsigned>() + nblk, sizeof count, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    if ((size_t)count * 4 >= nsamples) {
-      *naccepted = count;
-      *masked = true;
-      return 0;
-    }
-    if (count == 0) return 0;
-  }
-  launch_compact(r->gen.as<double>(), r->smask.as<uint8_t>(), n, d, r->blk.as<unsigned>(), r->sout.as<double>(),
-                 cap, s);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(&count, r->blk.as<unsigned>() + nblk, sizeof count, hipMemcpyDeviceToHost, s));
-  CK(hipStreamSynchronize(s));
-  const size_t take = count < cap ? count : cap;
-  if (take && fetch) {
-    CK(hipMemcpyAsync(out, r->sout.p, take * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-  }
-  *naccepted = take;
+  *b = {r->s_wc.as<double>(), mask, (long long)k0};
   return 0;
 }
 
 // the body of mlf_region_refill / mlf_region_refill_user: `evaluate(rows, member, n, p_buf, L_buf, s, &prow)` enqueues the prior
 // transform and the likelihood of the n rows (p into p_buf, or *prow = rows for the identity; L into L_buf)
-extern "C++" template <class Evaluate>
-static int region_refill_impl(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
-                              Evaluate evaluate, double *out_u, double *out_p, double *out_L, size_t capacity,
-                              size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
+template <class Evaluate>
+int region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin, Evaluate evaluate,
+                  double *out_u, double *out_p, double *out_L, size_t capacity, size_t *nevaluated, size_t *nkept,
+                  uint64_t *next_offset) {
   *nevaluated = 0;
   *nkept = 0;
+  Drawn b;
+  if (int rc = region_draw(r, method, nsamples, seed, offset, &b, next_offset)) return rc;
+  if (b.n == 0) return 0;
+  hipStream_t s = g_ctx.stream;
+  const int d = r->d;
+  // The accepted count first.  A batch drawn in the cube (methods 0 and 1) with at least a quarter of it accepted is evaluated
+  // where it was drawn: the prior transform and the likelihood run over all its rows (a rejected row costs a wasted evaluation,
+  // no copy) and the threshold cut keeps accepted rows only, so rows, order and values are those of the compacted route.  Any
+  // other batch is compacted before the evaluation.
+  const Compaction accepted(b.member, b.n, r->blk.as<unsigned>(), s);
   size_t nacc = 0;
-  bool masked = false;
-  if (int rc = region_sample_impl(r, method, nsamples, seed, offset, nullptr, nsamples, &nacc, next_offset, false, true, &masked))
-    return rc;
+  CK(accepted.count(nsamples, &nacc));
   *nevaluated = nacc;
   if (nacc == 0 || capacity == 0) return 0;
-  Ctx &c = g_ctx;
-  hipStream_t s = c.stream;
-  const int d = r->d;
-  // masked: the whole batch as drawn (r->gen) with its membership mask (r->smask) -- the prior transform and the likelihood run
-  // over all rows (a rejected row costs a wasted evaluation, no copy), the threshold cut keeps accepted rows only, and the
-  // rows that pass it are compacted once; rows, order and values are those of the compacted route (r->sout, dense)
-  const double *rows = masked ? r->gen.as<double>() : r->sout.as<double>();
-  const uint8_t *member = masked ? r->smask.as<uint8_t>() : nullptr;
-  const long long n = masked ? (long long)nsamples : (long long)nacc;
-  const int nblk = (int)((n + 255) / 256);
+  if (method >= 2 || nacc * 4 < nsamples) {
+    CK(r->sout.reserve(nsamples * d * sizeof(double)));
+    accepted.scatter(b.rows, d, r->sout.as<double>(), nacc);
+    b = {r->sout.as<double>(), nullptr, (long long)nacc};
+  }
+  const long long n = b.n;
   CK(r->rf_p.reserve((size_t)n * d * sizeof(double)));
   CK(r->rf_L.reserve((size_t)n * sizeof(double)));
   CK(r->rf_out.reserve(capacity * (2 * (size_t)d + 1) * sizeof(double)));
   CK(r->rf_keep.reserve((size_t)n));
-  CK(r->blk.reserve(((size_t)nblk + 1) * sizeof(unsigned)));
   // prior transform + likelihood on the accepted proposals, where they are (reference _refill_samples,
   // integrator.py:1789-1804); only the points above the threshold travel to the host
-  const double *prow = rows;   // identity transform: the parameters ARE the cube coordinates, no copy
-  if (int rc = evaluate(rows, member, n, r->rf_p.as<double>(), r->rf_L.as<double>(), s, &prow)) return rc;
+  const double *prow = b.rows;   // identity transform: the parameters ARE the cube coordinates, no copy
+  if (int rc = evaluate(b.rows, b.member, n, r->rf_p.as<double>(), r->rf_L.as<double>(), s, &prow)) return rc;
   uint8_t *keep = r->rf_keep.as<uint8_t>();
-  launch_mask_greater(r->rf_L.as<double>(), n, Lmin, keep, s, member);
-  const unsigned cap = capacity > 0xffffffffu ? 0xffffffffu : (unsigned)capacity;
+  launch_mask_greater(r->rf_L.as<double>(), n, Lmin, keep, s, b.member);
   double *ou = r->rf_out.as<double>(), *op = ou + capacity * (size_t)d, *oL = op + capacity * (size_t)d;
-  launch_mask_offsets(keep, n, r->blk.as<unsigned>(), s);   // one count + scan for the three arrays
-  launch_scatter(rows, keep, n, d, r->blk.as<unsigned>(), ou, cap, s);
-  launch_scatter(prow, keep, n, d, r->blk.as<unsigned>(), op, cap, s);
-  launch_scatter(r->rf_L.as<double>(), keep, n, 1, r->blk.as<unsigned>(), oL, cap, s);
-  CK(hipGetLastError());
-  unsigned count = 0;
-  CK(hipMemcpyAsync(&count, r->blk.as<unsigned>() + nblk, sizeof count, hipMemcpyDeviceToHost, s));
-  CK(hipStreamSynchronize(s));
-  const size_t take = count < cap ? count : cap;
+  const Compaction kept(keep, n, r->blk.as<unsigned>(), s);   // one count + scan for the three arrays
+  kept.scatter(b.rows, d, ou, capacity);
+  kept.scatter(prow, d, op, capacity);
+  kept.scatter(r->rf_L.as<double>(), 1, oL, capacity);
+  size_t take = 0;
+  CK(kept.count(capacity, &take));
   if (take) {
     CK(hipMemcpyAsync(out_u, ou, take * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s));
     CK(hipMemcpyAsync(out_p, op, take * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2929,6 +2843,33 @@ static int region_refill_impl(mlf_region *r, int method, size_t nsamples, uint64
     CK(hipStreamSynchronize(s));
   }
   *nkept = take;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mlf_region_sample(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double *out,
+                      size_t capacity, size_t *naccepted, uint64_t *next_offset) {
+  if (!out || !naccepted) return fail_arg(MLF_E_BADARG, "null pointer");
+  *naccepted = 0;
+  Drawn b;
+  // capacity 0 draws nothing: the counter stays at `offset`
+  if (int rc = region_draw(r, method, capacity ? nsamples : 0, seed, offset, &b, next_offset)) return rc;
+  if (b.n == 0) return 0;
+  hipStream_t s = g_ctx.stream;
+  const int d = r->d;
+  CK(r->sout.reserve(capacity * (size_t)d * sizeof(double)));
+  const Compaction accepted(b.member, b.n, r->blk.as<unsigned>(), s);
+  accepted.scatter(b.rows, d, r->sout.as<double>(), capacity);
+  size_t take = 0;
+  CK(accepted.count(capacity, &take));
+  if (take) {
+    CK(hipMemcpyAsync(out, r->sout.p, take * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+  }
+  *naccepted = take;
   return 0;
 }
 
@@ -2951,8 +2892,8 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
     launch_loglike(lkind, *prow, d, n, r->rf_aux.as<double>(), sigma, Lbuf, s);
     return 0;
   };
-  return region_refill_impl(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated,
-                            nkept, next_offset);
+  return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
+                       next_offset);
 }
 
 int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
@@ -2969,8 +2910,8 @@ int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t 
     if (p) *prow = p;
     return usermodel_rows(model, rows, n, member, p, Lbuf, s);
   };
-  return region_refill_impl(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated,
-                            nkept, next_offset);
+  return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
+                       next_offset);
 }
 
 int mlf_debug_philox(uint64_t seed, unsigned stream, size_t nblocks, uint32_t *out) {

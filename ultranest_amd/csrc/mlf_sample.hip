@@ -470,16 +470,18 @@ void launch_philox_words(unsigned long long seed, unsigned stream, long long n, 
   hipLaunchKernelGGL(k_philox_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seed, stream, n, out);
 }
 
-void launch_generate_cube(double *pts, long long nelem, unsigned long long seed, unsigned long long offset,
-                          hipStream_t s) {
+hipError_t launch_generate_cube(double *pts, long long nelem, unsigned long long seed, unsigned long long offset,
+                                hipStream_t s) {
   const long long nb = (nelem + 1) / 2;
   hipLaunchKernelGGL(k_generate_cube, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, pts, nelem, seed, offset);
+  return hipGetLastError();
 }
 
-void launch_generate_ball(double *z, long long n, int d, double enlarge, unsigned long long seed,
-                          unsigned long long offset, hipStream_t s) {
+hipError_t launch_generate_ball(double *z, long long n, int d, double enlarge, unsigned long long seed,
+                                unsigned long long offset, hipStream_t s) {
   hipLaunchKernelGGL(k_generate_ball, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, n, d, enlarge, seed,
                      offset);
+  return hipGetLastError();
 }
 
 int generate_ellipsoid_chunk(int d) {   // outputs per wave: the instantiated size that covers ceil(d / 4)
@@ -553,26 +555,29 @@ void launch_center_and_cube(double *w, long long n, int d, const double *center,
   hipLaunchKernelGGL(k_center_and_cube, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, n, d, center, in_cube);   // 4 waves x 64 rows
 }
 
-void launch_generate_tbox(double *t, long long n, int d, const double *lo, const double *hi, double pad,
-                          unsigned long long seed, unsigned long long offset, hipStream_t s) {
+hipError_t launch_generate_tbox(double *t, long long n, int d, const double *lo, const double *hi, double pad,
+                                unsigned long long seed, unsigned long long offset, hipStream_t s) {
   const long long nb = (n * d + 1) / 2;
   hipLaunchKernelGGL(k_generate_tbox, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, t, n * d, d, lo, hi, pad, seed,
                      offset);
+  return hipGetLastError();
 }
 
-void launch_generate_around_points(double *t, double *thin_u, long long n, int d, const double *refR, int nlive, int dp,
-                                   double r2, unsigned long long seed, unsigned long long offset, hipStream_t s) {
-  if (n <= 0) return;
+hipError_t launch_generate_around_points(double *t, double *thin_u, long long n, int d, const double *refR, int nlive, int dp,
+                                         double r2, unsigned long long seed, unsigned long long offset, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
   const int npairs = (d + 1) / 2;
   const unsigned pmagic = npairs > 1 ? (unsigned)((0x100000000ull + (unsigned)npairs - 1) / (unsigned)npairs) : 0u;
   const unsigned dmagic = d > 1 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u;
   const size_t lds = ((size_t)64 * (d + 1) + 64) * sizeof(double) + 64 * sizeof(unsigned);
   static DeviceGrant grant;
-  (void)grant.ensure([] {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_generate_around_points), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-  });
+  if (hipError_t e = grant.ensure([] {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_generate_around_points), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
+      }))
+    return e;
   hipLaunchKernelGGL(k_generate_around_points, dim3((unsigned)((n + 63) / 64)), dim3(256), lds, s, t, thin_u, n, d, refR,
                      nlive, dp, r2, seed, offset, pmagic, dmagic);
+  return hipGetLastError();
 }
 
 void launch_thin_by_multiplicity(const long long *count, const double *thin_u, long long n, uint8_t *mask, hipStream_t s) {
@@ -613,27 +618,29 @@ void launch_scan_counts(unsigned *blk, int nblk, hipStream_t s) {
 }
 
 // blk[i] = number of set mask bytes before block i (256 entries per block), blk[nblk] = total
-void launch_mask_offsets(const uint8_t *mask, long long n, unsigned *blk, hipStream_t s) {
+Compaction::Compaction(const uint8_t *mask_, long long n_, unsigned *blk_, hipStream_t s_) : mask(mask_), n(n_), blk(blk_), s(s_) {
   const int nblk = (int)((n + 255) / 256);
   hipLaunchKernelGGL(k_count_accepted, dim3(nblk), dim3(256), 0, s, mask, n, blk);
   hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, blk, nblk);
 }
 
-void launch_compact(const double *pts, const uint8_t *mask, long long n, int d, unsigned *blk, double *out,
-                    unsigned capacity, hipStream_t s) {
-  launch_mask_offsets(mask, n, blk, s);
-  launch_scatter(pts, mask, n, d, blk, out, capacity, s);
-}
-
-// the scatter alone: blk holds the offsets of THIS mask (launch_mask_offsets); several arrays compacted by one mask share them
-void launch_scatter(const double *pts, const uint8_t *mask, long long n, int d, const unsigned *blk, double *out,
-                    unsigned capacity, hipStream_t s) {
+void Compaction::scatter(const double *src, int d, double *dst, size_t capacity) const {
   const int nblk = (int)((n + 255) / 256);
+  const unsigned cap = capacity > 0xffffffffu ? 0xffffffffu : (unsigned)capacity;
   const unsigned dmagic = d > 1 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u;
   if (d == 1)
-    hipLaunchKernelGGL(k_scatter_scalars, dim3(nblk), dim3(256), 0, s, pts, mask, n, blk, out, capacity);
+    hipLaunchKernelGGL(k_scatter_scalars, dim3(nblk), dim3(256), 0, s, src, mask, n, blk, dst, cap);
   else
-    hipLaunchKernelGGL(k_scatter_accepted, dim3(nblk), dim3(256), 0, s, pts, mask, n, d, dmagic, blk, out, capacity);
+    hipLaunchKernelGGL(k_scatter_accepted, dim3(nblk), dim3(256), 0, s, src, mask, n, d, dmagic, blk, dst, cap);
+}
+
+hipError_t Compaction::count(size_t capacity, size_t *taken) const {
+  unsigned total = 0;
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(&total, blk + (n + 255) / 256, sizeof total, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  *taken = total < capacity ? total : capacity;
+  return e;
 }
 
 }  // namespace mlf

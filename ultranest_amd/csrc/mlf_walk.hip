@@ -392,7 +392,7 @@ __global__ void k_walk_transform(WalkState w, int tkind, double a, double b) {
   w.pnew[e] = p;
 }
 
-// blk = exclusive per-256 offsets of the acceptable walkers (launch_compact); walker i takes row
+// blk = exclusive per-256 offsets of the acceptable walkers (Compaction in mlf_walkers_propose); walker i takes row
 // rank(i) of the compacted host results
 __global__ __launch_bounds__(256) void k_walk_expand(WalkState w, const unsigned *blk, const double *pc,
                                                      const double *Lc) {

@@ -33,7 +33,6 @@ struct mlf_walkers {
   int layer_kind = -1;
   bool layer_wrap = false;
   double r2 = 1.0;
-  unsigned nblk = 0;
   bool proposed = false, compacted = false;
   std::vector<uint8_t> host_snap;
   // one captured launch sequence (replay): the executable graph and everything its captured arguments depend on
@@ -515,13 +514,10 @@ int mlf_walkers_propose(mlf_walkers *w, const double *unif, uint64_t seed, uint6
   w->compacted = false;
   if (!nacc) return 0;
   // host likelihood: hand back the acceptable rows in walker order
-  launch_compact(st.unew, st.acceptable, w->P, w->d, w->blk.as<unsigned>(), w->compact.as<double>(),
-                 (unsigned)w->P, s);
-  CK(hipGetLastError());
-  w->nblk = (unsigned)((w->P + 255) / 256);
-  unsigned count = 0;
-  CK(hipMemcpyAsync(&count, w->blk.as<unsigned>() + w->nblk, sizeof count, hipMemcpyDeviceToHost, s));
-  CK(hipStreamSynchronize(s));
+  const Compaction acceptable(st.acceptable, w->P, w->blk.as<unsigned>(), s);
+  acceptable.scatter(st.unew, w->d, w->compact.as<double>(), (size_t)w->P);
+  size_t count = 0;
+  CK(acceptable.count((size_t)w->P, &count));
   if (count) {
     if (int rc = download(unew_out, w->compact, (size_t)count * w->d * 8, s)) return rc;
     CK(hipStreamSynchronize(s));

@@ -382,29 +382,25 @@ class DeviceRegion(object):
     def refill(self, method, nsamples, seed, offset, Lmin, tspec, lspec, capacity=None):
         """Device-resident proposal batch: draw + region test + prior transform + likelihood; returns the
         points above `Lmin` as (u, p, L), the number of likelihood evaluations and the next offset."""
-        d = self._d
-        cap = int(nsamples if capacity is None else capacity)
-        u, p, L = np.empty((cap, d)), np.empty((cap, d)), np.empty(cap)
-        nev, nkept, nxt = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
         tkind, ta, tb = tspec
         lkind, aux, sigma = lspec
-        check(_lib.lib().mlf_region_refill(self._h, int(method), int(nsamples), ctypes.c_uint64(int(seed)),
-                                           ctypes.c_uint64(int(offset)), float(Lmin), int(tkind), float(ta), float(tb),
-                                           int(lkind), ptr(None if aux is None else f64(aux)), float(sigma), ptr(u), ptr(p),
-                                           ptr(L), cap, ctypes.byref(nev), ctypes.byref(nkept), ctypes.byref(nxt)))
-        k = nkept.value
-        return u[:k], p[:k], L[:k], nev.value, nxt.value
+        return self._refill(_lib.lib().mlf_region_refill, method, nsamples, seed, offset, Lmin, capacity,
+                            int(tkind), float(ta), float(tb), int(lkind), ptr(None if aux is None else f64(aux)), float(sigma))
 
     def refill_user(self, method, nsamples, seed, offset, Lmin, model, capacity=None):
         """`refill` with a user model (``mlf_usermodel *`` of ultranest_amd.devicemodel) in place of the built-in
         transform / likelihood kinds."""
+        return self._refill(_lib.lib().mlf_region_refill_user, method, nsamples, seed, offset, Lmin, capacity, model)
+
+    def _refill(self, fn, method, nsamples, seed, offset, Lmin, capacity, *evaluation):
+        """The call of `fn` (mlf_region_refill or its user variant) that `evaluation`, its arguments between Lmin and
+        the output arrays, completes."""
         d = self._d
         cap = int(nsamples if capacity is None else capacity)
         u, p, L = np.empty((cap, d)), np.empty((cap, d)), np.empty(cap)
         nev, nkept, nxt = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
-        check(_lib.lib().mlf_region_refill_user(self._h, int(method), int(nsamples), ctypes.c_uint64(int(seed)),
-                                                ctypes.c_uint64(int(offset)), float(Lmin), model, ptr(u), ptr(p), ptr(L), cap,
-                                                ctypes.byref(nev), ctypes.byref(nkept), ctypes.byref(nxt)))
+        check(fn(self._h, int(method), int(nsamples), ctypes.c_uint64(int(seed)), ctypes.c_uint64(int(offset)), float(Lmin),
+                 *evaluation, ptr(u), ptr(p), ptr(L), cap, ctypes.byref(nev), ctypes.byref(nkept), ctypes.byref(nxt)))
         k = nkept.value
         return u[:k], p[:k], L[:k], nev.value, nxt.value
 

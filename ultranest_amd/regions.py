@@ -388,25 +388,23 @@ class _DeviceState(object):
 
     def refill(self, region, use_scan, method, nsamples, Lmin, tspec, lspec):
         """Device-resident proposal batch (draw, region test, prior transform, likelihood, threshold)."""
-        handle = self._prepare_sampling(region, use_scan, method)
-        rng = region.device_rng
-        u, p, L, nev, rng.offset = handle.refill(method, nsamples, rng.seed, rng.offset, Lmin, tspec, lspec)
-        return u, p, L, nev
+        return self._draw(region, use_scan, method, "refill", nsamples, Lmin, tspec, lspec)
 
     def refill_user(self, region, use_scan, method, nsamples, Lmin, model, with_transform):
         """The same batch with a user model (ultranest_amd.devicemodel): transform + likelihood in one fused launch."""
-        handle = self._prepare_sampling(region, use_scan, method)
-        rng = region.device_rng
-        u, p, L, nev, rng.offset = handle.refill_user(method, nsamples, rng.seed, rng.offset, Lmin,
-                                                      model.handle(with_transform))
-        return u, p, L, nev
+        return self._draw(region, use_scan, method, "refill_user", nsamples, Lmin, model.handle(with_transform))
 
     def sample(self, region, use_scan, method, nsamples):
         """Device-side draw + membership + compaction with the region's ``device_rng``."""
+        return self._draw(region, use_scan, method, "sample", nsamples)[0]
+
+    def _draw(self, region, use_scan, method, call, nsamples, *args):
+        """handle.<call>(method, nsamples, seed, offset, *args) at the region's ``device_rng`` position, which moves on to the
+        next offset; returns the call's results without that offset."""
         handle = self._prepare_sampling(region, use_scan, method)
         rng = region.device_rng
-        pts, rng.offset = handle.sample(method, nsamples, rng.seed, rng.offset)
-        return pts
+        *out, rng.offset = getattr(handle, call)(method, nsamples, rng.seed, rng.offset, *args)
+        return tuple(out)
 
     def _prepare_sampling(self, region, use_scan, method):
         handle = self.sync(region, use_scan)
