@@ -99,7 +99,7 @@ def pad16(v, K):
 
 
 class EllSetup:
-    """host constants of region_prep4_setup / region_prep4_centres (csrc/mlf_api.hip) for the ellipsoid chain"""
+    """host constants of region_prep4_setup / region_prep4_centres (csrc/mlf_region.hip) for the ellipsoid chain"""
 
     def __init__(self, L, A, c_ell, c_lay, amax):
         d = L.shape[0]
@@ -335,7 +335,7 @@ def test_whitening_chain_error_model():
 
 
 class SameFormSetup:
-    """host constants of the "same quadratic form" variant (region_prep4_setup, csrc/mlf_api.hip: p4c_same): the ellipsoid
+    """host constants of the "same quadratic form" variant (region_prep4_setup, csrc/mlf_region.hip: p4c_same): the ellipsoid
     test reads delta^T A delta = |T^T delta|^2 + delta^T E delta off the whitening chain; None when the residue is refused"""
 
     def __init__(self, T, A, c, amax):

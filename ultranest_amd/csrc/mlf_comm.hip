@@ -69,7 +69,7 @@ int load_rccl() {
   if (!h)
     for (const char *n : names)
       if ((h = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;
-  if (!h) return ctx_fail_arg(MLF_E_STATE, "librccl.so not found (needed only for mlf_comm_* / mlf_allreduce_max)");
+  if (!h) return fail_arg(MLF_E_STATE, "librccl.so not found (needed only for mlf_comm_* / mlf_allreduce_max)");
   Rccl r;
   r.h = h;
   r.get_unique_id = (fn_get_unique_id)dlsym(h, "ncclGetUniqueId");
@@ -81,7 +81,7 @@ int load_rccl() {
   r.group_end = (fn_group)dlsym(h, "ncclGroupEnd");
   r.errstr = (fn_errstr)dlsym(h, "ncclGetErrorString");
   if (!r.get_unique_id || !r.init_rank || !r.init_all || !r.all_reduce || !r.destroy || !r.group_start || !r.group_end)
-    return ctx_fail_arg(MLF_E_STATE, "librccl.so lacks an expected symbol");
+    return fail_arg(MLF_E_STATE, "librccl.so lacks an expected symbol");
   g_rccl = r;
   return 0;
 }
@@ -89,23 +89,17 @@ int load_rccl() {
 int fail_rccl(int code, const char *what) {
   std::string msg = std::string("RCCL failure in ") + what + ": " +
                     (g_rccl.errstr ? g_rccl.errstr(code) : "error") + " (" + std::to_string(code) + ")";
-  ctx_fail_arg(MLF_E_STATE, msg.c_str());
+  fail_arg(MLF_E_STATE, msg.c_str());
   return -1000 - code;
 }
-
-#define CKH(x)                                                        \
-  do {                                                                \
-    hipError_t e_ = (x);                                              \
-    if (e_ != hipSuccess) return ctx_fail_hip(e_, #x, __FILE__, __LINE__); \
-  } while (0)
 
 int reserve_bufs(size_t count) {
   if (count <= g_comm.buf_count) return 0;
   for (size_t i = 0; i < g_comm.devices.size(); ++i) {
-    CKH(hipSetDevice(g_comm.devices[i]));
-    if (g_comm.bufs[i]) CKH(hipFree(g_comm.bufs[i]));
+    CK(hipSetDevice(g_comm.devices[i]));
+    if (g_comm.bufs[i]) CK(hipFree(g_comm.bufs[i]));
     g_comm.bufs[i] = nullptr;
-    CKH(hipMalloc(reinterpret_cast<void **>(&g_comm.bufs[i]), count * sizeof(double)));
+    CK(hipMalloc(reinterpret_cast<void **>(&g_comm.bufs[i]), count * sizeof(double)));
   }
   g_comm.buf_count = count;
   return 0;
@@ -116,7 +110,7 @@ int reserve_bufs(size_t count) {
 extern "C" {
 
 int mlf_comm_unique_id(char *id_out, size_t len) {
-  if (!id_out || len < 128) return ctx_fail_arg(MLF_E_BADARG, "id buffer must hold 128 bytes");
+  if (!id_out || len < 128) return fail_arg(MLF_E_BADARG, "id buffer must hold 128 bytes");
   if (int rc = load_rccl()) return rc;
   UniqueId id;
   if (int rc = g_rccl.get_unique_id(&id)) return fail_rccl(rc, "ncclGetUniqueId");
@@ -147,20 +141,20 @@ static int adopt(const std::vector<int> &devices, const std::vector<Comm> &comms
   g_comm.bufs.assign(devices.size(), nullptr);
   g_comm.buf_count = 0;
   for (size_t i = 0; i < devices.size(); ++i) {
-    CKH(hipSetDevice(devices[i]));
-    CKH(hipStreamCreate(&g_comm.streams[i]));
+    CK(hipSetDevice(devices[i]));
+    CK(hipStreamCreate(&g_comm.streams[i]));
   }
-  CKH(hipSetDevice(devices[0]));
+  CK(hipSetDevice(devices[0]));
   return reserve_bufs(16);
 }
 
 int mlf_comm_init_rank(const char *id, size_t len, int nranks, int rank) {
-  if (!id || len < 128 || nranks < 1 || rank < 0 || rank >= nranks) return ctx_fail_arg(MLF_E_BADARG, "bad communicator arguments");
-  if (int rc = ctx_ensure()) return rc;
+  if (!id || len < 128 || nranks < 1 || rank < 0 || rank >= nranks) return fail_arg(MLF_E_BADARG, "bad communicator arguments");
+  if (int rc = ensure_ctx()) return rc;
   if (int rc = load_rccl()) return rc;
   mlf_comm_destroy();
   int dev = 0;
-  CKH(hipGetDevice(&dev));   // the device selected with mlf_set_device
+  CK(hipGetDevice(&dev));   // the device selected with mlf_set_device
   UniqueId uid;
   memcpy(uid.bytes, id, 128);
   Comm c = nullptr;
@@ -170,8 +164,8 @@ int mlf_comm_init_rank(const char *id, size_t len, int nranks, int rank) {
 
 int mlf_comm_init(int ndev) {
   int have = 0;
-  CKH(hipGetDeviceCount(&have));
-  if (ndev < 1 || ndev > have) return ctx_fail_arg(MLF_E_BADARG, "mlf_comm_init: ndev must be between 1 and the number of visible devices");
+  CK(hipGetDeviceCount(&have));
+  if (ndev < 1 || ndev > have) return fail_arg(MLF_E_BADARG, "mlf_comm_init: ndev must be between 1 and the number of visible devices");
   if (int rc = load_rccl()) return rc;
   mlf_comm_destroy();
   std::vector<int> devices((size_t)ndev);
@@ -182,13 +176,13 @@ int mlf_comm_init(int ndev) {
 }
 
 int mlf_allreduce_max(double *values, size_t count) {
-  if (!values || count == 0) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (g_comm.comms.empty()) return ctx_fail_arg(MLF_E_STATE, "mlf_allreduce_max before mlf_comm_init / mlf_comm_init_rank");
+  if (!values || count == 0) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (g_comm.comms.empty()) return fail_arg(MLF_E_STATE, "mlf_allreduce_max before mlf_comm_init / mlf_comm_init_rank");
   if (int rc = reserve_bufs(count)) return rc;
   const size_t ndev = g_comm.devices.size();
   for (size_t i = 0; i < ndev; ++i) {
-    CKH(hipSetDevice(g_comm.devices[i]));
-    CKH(hipMemcpyAsync(g_comm.bufs[i], values + i * count, count * sizeof(double), hipMemcpyHostToDevice, g_comm.streams[i]));
+    CK(hipSetDevice(g_comm.devices[i]));
+    CK(hipMemcpyAsync(g_comm.bufs[i], values + i * count, count * sizeof(double), hipMemcpyHostToDevice, g_comm.streams[i]));
   }
   if (int rc = g_rccl.group_start()) return fail_rccl(rc, "ncclGroupStart");
   for (size_t i = 0; i < ndev; ++i)
@@ -196,11 +190,11 @@ int mlf_allreduce_max(double *values, size_t count) {
       return fail_rccl(rc, "ncclAllReduce");
   if (int rc = g_rccl.group_end()) return fail_rccl(rc, "ncclGroupEnd");
   for (size_t i = 0; i < ndev; ++i) {
-    CKH(hipSetDevice(g_comm.devices[i]));
-    CKH(hipMemcpyAsync(values + i * count, g_comm.bufs[i], count * sizeof(double), hipMemcpyDeviceToHost, g_comm.streams[i]));
-    CKH(hipStreamSynchronize(g_comm.streams[i]));
+    CK(hipSetDevice(g_comm.devices[i]));
+    CK(hipMemcpyAsync(values + i * count, g_comm.bufs[i], count * sizeof(double), hipMemcpyDeviceToHost, g_comm.streams[i]));
+    CK(hipStreamSynchronize(g_comm.streams[i]));
   }
-  CKH(hipSetDevice(g_comm.devices[0]));
+  CK(hipSetDevice(g_comm.devices[0]));
   return 0;
 }
 

@@ -1,5 +1,5 @@
-// mlf_ctx.hpp -- what the C-ABI translation units (mlf_api.hip, mlf_walk_api.hip) share: the
-// grow-only device buffer, the library context (one device, one stream) and error reporting.
+// mlf_ctx.hpp -- what every C-ABI translation unit shares: the grow-only device buffer, the library
+// context (one device, one stream) and error reporting.  mlf_host.hpp adds what the membership / region units share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,11 +39,11 @@ struct DevBuf {
   }
 };
 
-// defined in mlf_api.hip
-int ctx_ensure();                    // 0 or MLF_E_NODEVICE (message set)
+// defined in mlf_api.hip; the fail_* set the text that mlf_last_error returns
+int ensure_ctx();                    // 0 or MLF_E_NODEVICE (message set)
 hipStream_t ctx_stream();
-int ctx_fail_hip(hipError_t e, const char *what, const char *file, int line);   // returns -(int)e
-int ctx_fail_arg(int code, const char *msg);                                    // returns code
+int fail_hip(hipError_t e, const char *what, const char *file, int line);   // "HIP error N (text) at FILE:LINE: call"; returns -(int)e
+int fail_arg(int code, const char *msg);                                    // returns code
 
 // defined in mlf_user.hip: a user model's dimensionality / transform flag, and one launch of its mlf_user_rows kernel on `s`
 // (argument meaning as in mlf_user_rows.hpp)
@@ -53,3 +53,10 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
                    hipStream_t s);
 
 }  // namespace mlf
+
+// a failed HIP call ends the calling function with fail_hip's code
+#define CK(x)                                                                    \
+  do {                                                                           \
+    hipError_t e_ = (x);                                                         \
+    if (e_ != hipSuccess) return mlf::fail_hip(e_, #x, __FILE_NAME__, __LINE__); \
+  } while (0)

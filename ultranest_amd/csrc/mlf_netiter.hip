@@ -73,9 +73,9 @@ extern "C" {
 
 int mlf_counter_create(mlf_counter **out, size_t nroots, size_t ncounters, const uint8_t *member, int random,
                        int check_insertion_order) {
-  if (!out || !member) return mlf::ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!out || !member) return mlf::fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
-  if (nroots == 0 || ncounters == 0) return mlf::ctx_fail_arg(MLF_E_BADARG, "nroots and ncounters must be positive");
+  if (nroots == 0 || ncounters == 0) return mlf::fail_arg(MLF_E_BADARG, "nroots and ncounters must be positive");
   mlf_counter *c = new mlf_counter();
   c->nroots = nroots;
   c->ncounters = ncounters;
@@ -101,7 +101,7 @@ int mlf_counter_destroy(mlf_counter *c) {
 }
 
 int mlf_counter_reset(mlf_counter *c) {
-  if (!c) return mlf::ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!c) return mlf::fail_arg(MLF_E_BADARG, "null pointer");
   reset(c);
   return 0;
 }
@@ -110,13 +110,13 @@ int mlf_counter_passing_node(mlf_counter *c, int64_t rootid, double Li, size_t n
                              const int64_t *rootids, const double *parallel_values, size_t nparallel,
                              const double *random_beta, double *logwidth) {
   if (!c || !logwidth || (nparallel && (!rootids || !parallel_values)) || (nchildren && !child_values))
-    return mlf::ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (rootid < 0 || (size_t)rootid >= c->nroots) return mlf::ctx_fail_arg(MLF_E_BADARG, "rootid out of range");
-  if (nparallel == 0) return mlf::ctx_fail_arg(MLF_E_BADARG, "no parallel nodes");
+    return mlf::fail_arg(MLF_E_BADARG, "null pointer");
+  if (rootid < 0 || (size_t)rootid >= c->nroots) return mlf::fail_arg(MLF_E_BADARG, "rootid out of range");
+  if (nparallel == 0) return mlf::fail_arg(MLF_E_BADARG, "no parallel nodes");
   if (c->random && nchildren >= 1 && !random_beta)
-    return mlf::ctx_fail_arg(MLF_E_BADARG, "random volume shrinkage needs the beta draws");
+    return mlf::fail_arg(MLF_E_BADARG, "random volume shrinkage needs the beta draws");
   for (size_t j = 0; j < nparallel; ++j)
-    if (rootids[j] < 0 || (size_t)rootids[j] >= c->nroots) return mlf::ctx_fail_arg(MLF_E_BADARG, "root id out of range");
+    if (rootids[j] < 0 || (size_t)rootids[j] >= c->nroots) return mlf::fail_arg(MLF_E_BADARG, "root id out of range");
   const size_t nb = c->ncounters, nr = c->nroots;
   // in which bootstraps is rootid, and how many live points does each bootstrap have (:743-747)
   {   // one contiguous membership row per parallel node: the inner loop vectorises
@@ -131,7 +131,7 @@ int mlf_counter_passing_node(mlf_counter *c, int64_t rootid, double Li, size_t n
   }
   const long long nlive0 = c->nlive[0];
   auto active = [&](size_t b) { return c->member[b * nr + (size_t)rootid] != 0; };
-  if (!active(0)) return mlf::ctx_fail_arg(MLF_E_STATE, "the main counter must contain every root");
+  if (!active(0)) return mlf::fail_arg(MLF_E_STATE, "the main counter must contain every root");
 
   if (nchildren >= 1) {   // one arc terminates, another is spawned (:749-820)
     for (size_t b = 0; b < nb; ++b) {
@@ -176,7 +176,7 @@ int mlf_counter_passing_node(mlf_counter *c, int64_t rootid, double Li, size_t n
         for (size_t k = 0; k < nchildren; ++k) {
           // rank of the child among the parallel values of the main counter
           const long long order = std::lower_bound(c->sorted.begin(), c->sorted.end(), child_values[k]) - c->sorted.begin();
-          if (order < 0 || order > nlive0) return mlf::ctx_fail_arg(MLF_E_BADARG, "insertion order out of range");
+          if (order < 0 || order > nlive0) return mlf::fail_arg(MLF_E_BADARG, "insertion order out of range");
           c->acc_U += ((double)order + 0.5) / (double)nlive0;
           c->acc_N += 1;
           const double m_U = (double)c->acc_N * 0.5;
@@ -232,7 +232,7 @@ int mlf_counter_passing_node(mlf_counter *c, int64_t rootid, double Li, size_t n
 // row with numpy costs ~0.4 ms at 4000 x 50.  count = number of differing rows (may exceed capacity).
 int mlf_host_changed_rows(const double *a, const double *b, size_t n, size_t d, int64_t *rows, size_t capacity,
                           size_t *count) {
-  if (!a || !b || !count || (capacity && !rows)) return mlf::ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!a || !b || !count || (capacity && !rows)) return mlf::fail_arg(MLF_E_BADARG, "null pointer");
   size_t c = 0;
   const size_t bytes = d * sizeof(double);
   for (size_t i = 0; i < n; ++i)
@@ -264,9 +264,9 @@ inline void mt19937_refill(uint32_t *key) {
 }  // namespace
 
 int mlf_host_draw_selection(uint32_t *key, int32_t *pos, size_t npoints, size_t nrounds, uint8_t *masks) {
-  if (!key || !pos || (npoints && nrounds && !masks)) return mlf::ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!key || !pos || (npoints && nrounds && !masks)) return mlf::fail_arg(MLF_E_BADARG, "null pointer");
   if (npoints == 0 || npoints > 0x80000000ull || *pos < 0 || *pos > 624)
-    return mlf::ctx_fail_arg(MLF_E_BADARG, "npoints or generator position out of range");
+    return mlf::fail_arg(MLF_E_BADARG, "npoints or generator position out of range");
   memset(masks, 0, npoints * nrounds);
   if (npoints == 1) {   // numpy fills the zeros without drawing
     memset(masks, 1, nrounds);
@@ -298,7 +298,7 @@ int mlf_host_draw_selection(uint32_t *key, int32_t *pos, size_t npoints, size_t 
 
 int mlf_counter_state(const mlf_counter *c, double *scalars, double *all_H, double *all_logZ, double *all_logVolremaining,
                       double *all_logZremain, int64_t *runs, size_t runs_capacity, size_t *nruns) {
-  if (!c || !scalars) return mlf::ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!c || !scalars) return mlf::fail_arg(MLF_E_BADARG, "null pointer");
   scalars[0] = c->logZ;
   scalars[1] = c->logZerr;
   scalars[2] = c->logVol;

@@ -1,7 +1,7 @@
 // mlf_user.hip -- user models (include/mlfriends_hip.h, section "user models"): a likelihood and prior transform written
 // as HIP device functions, compiled at run time by hiprtc around mlf_user_rows.hpp, loaded as a module on the library's
 // device and launched on the library's stream (ordered with the kernels around it: the refill and walker routes of
-// mlf_api.hip / mlf_walk_api.hip call usermodel_rows between their own launches).
+// mlf_region_sample.hip / mlf_walk_api.hip call usermodel_rows between their own launches).
 //
 // hiprtc is loaded with dlopen, not linked: where it is missing the library loads and every other entry point works;
 // mlf_usermodel_compile then fails with MLF_E_COMPILE and says why.
@@ -22,12 +22,6 @@
 #include "mlf_user_rows.hpp"
 
 using namespace mlf;
-
-#define CK(x)                                                                  \
-  do {                                                                         \
-    hipError_t e_ = (x);                                                       \
-    if (e_ != hipSuccess) return ctx_fail_hip(e_, #x, "mlf_user.hip", __LINE__); \
-  } while (0)
 
 struct mlf_usermodel {
   hipModule_t module = nullptr;
@@ -112,7 +106,7 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
                    hipStream_t s) {
   if (n <= 0) return 0;
   const long long blocks = (n + 63) / 64;
-  if (blocks > 0x7fffffffLL) return ctx_fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
+  if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
   const unsigned lds = mlf_user_rows_lds_bytes(m->d, p != nullptr && m->has_transform);
   // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
   const double *a_u = u;
@@ -133,13 +127,13 @@ extern "C" {
 
 int mlf_usermodel_compile(const char *source, const char *include_dir, int has_transform, void *code_out, size_t code_cap,
                           size_t *code_size, char *log, size_t log_cap) {
-  if (!source || !include_dir || !code_size) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
   if (!rtc_load()) {
     put_log(log, log_cap, g_rtc.why);
-    return ctx_fail_arg(MLF_E_COMPILE, g_rtc.why.c_str());
+    return fail_arg(MLF_E_COMPILE, g_rtc.why.c_str());
   }
   const Rtc &r = g_rtc;
   const std::string src = std::string(source) + "\n#include \"mlf_user_rows.hpp\"\n";
@@ -151,7 +145,7 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
   if (res != HIPRTC_SUCCESS) {
     const std::string msg = std::string("hiprtcCreateProgram: ") + r.error_string(res);
     put_log(log, log_cap, msg);
-    return ctx_fail_arg(MLF_E_COMPILE, msg.c_str());
+    return fail_arg(MLF_E_COMPILE, msg.c_str());
   }
   res = r.compile(prog, (int)(sizeof opts / sizeof opts[0]), opts);
   if (res != HIPRTC_SUCCESS) {
@@ -163,21 +157,21 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
     }
     r.destroy(&prog);
     put_log(log, log_cap, text);
-    return ctx_fail_arg(MLF_E_COMPILE, "the user model did not compile (hiprtc log in the caller's buffer)");
+    return fail_arg(MLF_E_COMPILE, "the user model did not compile (hiprtc log in the caller's buffer)");
   }
   size_t size = 0;
   res = r.code_size(prog, &size);
   if (res != HIPRTC_SUCCESS || size == 0) {
     r.destroy(&prog);
-    return ctx_fail_arg(MLF_E_COMPILE, "hiprtc returned no code object");
+    return fail_arg(MLF_E_COMPILE, "hiprtc returned no code object");
   }
   *code_size = size;
   int rc = 0;
   if (code_out) {
     if (code_cap < size) {
-      rc = ctx_fail_arg(MLF_E_BADARG, "code buffer smaller than the code object (size in *code_size)");
+      rc = fail_arg(MLF_E_BADARG, "code buffer smaller than the code object (size in *code_size)");
     } else if (r.code(prog, static_cast<char *>(code_out)) != HIPRTC_SUCCESS) {
-      rc = ctx_fail_arg(MLF_E_COMPILE, "hiprtcGetCode failed");
+      rc = fail_arg(MLF_E_COMPILE, "hiprtcGetCode failed");
     }
   }
   r.destroy(&prog);
@@ -186,12 +180,12 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
 
 int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_transform, const double *aux, size_t naux,
                          mlf_usermodel **out) {
-  if (!out || !code || (naux && !aux)) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
-  if (d == 0) return ctx_fail_arg(MLF_E_BADARG, "dimensionality must be positive");
-  if (d > MLF_MAX_DIM) return ctx_fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
-  if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return ctx_fail_arg(MLF_E_BADARG, "not a code object (ELF)");
-  if (int rc = ctx_ensure()) return rc;
+  if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
+  if (d > MLF_MAX_DIM) return fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
+  if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return fail_arg(MLF_E_BADARG, "not a code object (ELF)");
+  if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   mlf_usermodel *m = new mlf_usermodel();
   m->d = (int)d;
@@ -206,7 +200,7 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
     if (m->module) (void)hipModuleUnload(m->module);
     m->aux.release();
     delete m;
-    return ctx_fail_hip(e, "mlf_usermodel_create", "mlf_user.hip", __LINE__);
+    return fail_hip(e, "mlf_usermodel_create", "mlf_user.hip", __LINE__);
   }
   *out = m;
   return 0;
@@ -225,14 +219,14 @@ int mlf_usermodel_destroy(mlf_usermodel *m) {
   m->hp.release();
   m->hL.release();
   delete m;
-  if (e != hipSuccess) return ctx_fail_hip(e, "mlf_usermodel_destroy", "mlf_user.hip", __LINE__);
+  if (e != hipSuccess) return fail_hip(e, "mlf_usermodel_destroy", "mlf_user.hip", __LINE__);
   return 0;
 }
 
 int mlf_usermodel_eval(mlf_usermodel *m, const double *u, size_t n, double *p_out, double *L_out) {
-  if (!m || !u || (!p_out && !L_out)) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!m || !u || (!p_out && !L_out)) return fail_arg(MLF_E_BADARG, "null pointer");
   if (n == 0) return 0;
-  if (n > 0x7fffffffffffull / (size_t)m->d) return ctx_fail_arg(MLF_E_BADARG, "batch too large");
+  if (n > 0x7fffffffffffull / (size_t)m->d) return fail_arg(MLF_E_BADARG, "batch too large");
   hipStream_t s = ctx_stream();
   const size_t rows = n * (size_t)m->d * sizeof(double);
   CK(m->hu.reserve(rows));
@@ -251,9 +245,9 @@ int mlf_usermodel_eval(mlf_usermodel *m, const double *u, size_t n, double *p_ou
 
 int mlf_usermodel_eval_dev(mlf_usermodel *m, const double *d_u, size_t n, const uint8_t *d_member, double *d_p, double *d_L,
                            void *stream) {
-  if (!m) return ctx_fail_arg(MLF_E_BADARG, "null model");
+  if (!m) return fail_arg(MLF_E_BADARG, "null model");
   if (n == 0) return 0;
-  if (!d_u || (!d_p && !d_L)) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!d_u || (!d_p && !d_L)) return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = usermodel_rows(m, d_u, (long long)n, d_member, d_p, d_L, (hipStream_t)stream)) return rc;
   CK(hipGetLastError());
   return 0;

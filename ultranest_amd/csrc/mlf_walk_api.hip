@@ -15,12 +15,6 @@
 
 using namespace mlf;
 
-#define CK(x)                                                                  \
-  do {                                                                         \
-    hipError_t e_ = (x);                                                       \
-    if (e_ != hipSuccess) return ctx_fail_hip(e_, #x, "mlf_walk_api.hip", __LINE__); \
-  } while (0)
-
 struct mlf_walkers {
   int P = 0, nsteps = 0, d = 0, nparams = 0;
   DevBuf allu, allL, generation, currentt, currentv, left, right, sl, sr, currentp;
@@ -81,8 +75,8 @@ int download(void *host, const DevBuf &b, size_t bytes, hipStream_t s) {
 }
 
 int check_nd(size_t n, size_t d) {
-  if (d == 0) return ctx_fail_arg(MLF_E_BADARG, "dimensionality must be positive");
-  if (n > 0x7fffffffull / (d ? d : 1)) return ctx_fail_arg(MLF_E_BADARG, "population too large");
+  if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
+  if (n > 0x7fffffffull / (d ? d : 1)) return fail_arg(MLF_E_BADARG, "population too large");
   return 0;
 }
 
@@ -123,9 +117,9 @@ WalkLayer layer_of(const mlf_walkers *w) {
 }
 
 int ensure_params(mlf_walkers *w, size_t nparams) {
-  if (nparams == 0) return ctx_fail_arg(MLF_E_BADARG, "nparams must be positive");
+  if (nparams == 0) return fail_arg(MLF_E_BADARG, "nparams must be positive");
   if (w->nparams == (int)nparams) return 0;
-  if (w->nparams != 0) return ctx_fail_arg(MLF_E_STATE, "number of transformed parameters changed between calls");
+  if (w->nparams != 0) return fail_arg(MLF_E_STATE, "number of transformed parameters changed between calls");
   w->nparams = (int)nparams;
   CK(w->currentp.reserve((size_t)w->P * nparams * sizeof(double)));
   CK(w->pnew.reserve((size_t)w->P * nparams * sizeof(double)));
@@ -147,11 +141,11 @@ struct StepEval {
 
   int check(const mlf_walkers *w) const {
     if (model) {
-      if (usermodel_dim(model) != w->d) return ctx_fail_arg(MLF_E_BADARG, "user model and walkers differ in dimensionality");
+      if (usermodel_dim(model) != w->d) return fail_arg(MLF_E_BADARG, "user model and walkers differ in dimensionality");
       return 0;
     }
-    if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return ctx_fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
-    if (lkind == 0 && !aux) return ctx_fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
+    if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
+    if (lkind == 0 && !aux) return fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
     return 0;
   }
   // pnew and Lnew on s; transform: the built-in transform has not run yet (a step's prologue runs it)
@@ -175,7 +169,7 @@ int finish_common(mlf_walkers *w, double Lmin, const StepEval *ev, int64_t ringi
     if (int rc = ev->enqueue(w, true, s)) return rc;
     CK(hipGetLastError());
   }
-  if (ringindex < 0 || ringindex >= w->P) return ctx_fail_arg(MLF_E_BADARG, "ringindex out of range");
+  if (ringindex < 0 || ringindex >= w->P) return fail_arg(MLF_E_BADARG, "ringindex out of range");
   const size_t nrec = 9 + (size_t)w->d + (size_t)w->nparams;
   CK(w->rec.reserve(nrec * sizeof(double)));
   const WalkState st = state_of(w);
@@ -201,7 +195,7 @@ int check_direction_data(const mlf_walkers *w, int kind) {
   const bool need_axes = kind == DIR_REGION_ORIENTED || kind == DIR_REGION_RANDOM || kind == DIR_MIXTURE;
   const bool need_live = kind == DIR_DIFFERENTIAL || kind == DIR_MIXTURE;
   if ((need_axes && !w->have_axes) || (need_live && !w->have_live) || (kind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
-    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
+    return fail_arg(MLF_E_STATE, "mlf_walkers_set_direction_data has not provided what this direction kind needs");
   return 0;
 }
 
@@ -216,10 +210,10 @@ uint64_t philox_per_call(const mlf_walkers *w) {
 
 // the checks of every whole-step route, in this order; max_rounds: that of mlf_walkers_rounds_dev, test-hook sign removed
 int check_step(const mlf_walkers *w, int dirkind, const StepEval &ev, int max_rounds = 1) {
-  if (!w->have_liveL) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
-  if (dirkind < 0 || dirkind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
+  if (!w->have_liveL) return fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
+  if (dirkind < 0 || dirkind > DIR_MIXTURE) return fail_arg(MLF_E_BADARG, "unknown direction kind");
   if (int rc = ev.check(w)) return rc;
-  if (max_rounds < 1) return ctx_fail_arg(MLF_E_BADARG, "max_rounds must not be 0");
+  if (max_rounds < 1) return fail_arg(MLF_E_BADARG, "max_rounds must not be 0");
   return check_direction_data(w, dirkind);
 }
 
@@ -289,15 +283,15 @@ int replay(mlf_walkers::GraphCache &c, std::vector<unsigned long long> key, hipS
     CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     int rc = capture(s);
     hipError_t e = hipGetLastError();
-    if (!rc && e != hipSuccess) rc = ctx_fail_hip(e, "a launch during the graph capture", "mlf_walk_api.hip", __LINE__);
+    if (!rc && e != hipSuccess) rc = fail_hip(e, "a launch during the graph capture", "mlf_walk_api.hip", __LINE__);
     hipGraph_t graph = nullptr;
     e = hipStreamEndCapture(s, &graph);
-    if (!rc && e != hipSuccess) rc = ctx_fail_hip(e, "hipStreamEndCapture", "mlf_walk_api.hip", __LINE__);
+    if (!rc && e != hipSuccess) rc = fail_hip(e, "hipStreamEndCapture", "mlf_walk_api.hip", __LINE__);
     if (!rc) {
       e = hipGraphInstantiate(&c.exec, graph, nullptr, nullptr, 0);
       if (e != hipSuccess) {
         c.exec = nullptr;
-        rc = ctx_fail_hip(e, "hipGraphInstantiate", "mlf_walk_api.hip", __LINE__);
+        rc = fail_hip(e, "hipGraphInstantiate", "mlf_walk_api.hip", __LINE__);
       }
     }
     if (graph) (void)hipGraphDestroy(graph);
@@ -314,12 +308,12 @@ int replay(mlf_walkers::GraphCache &c, std::vector<unsigned long long> key, hipS
 extern "C" {
 
 int mlf_walkers_create(mlf_walkers **out, size_t popsize, size_t nsteps, size_t d) {
-  if (!out) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!out) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
   if (popsize == 0 || nsteps == 0 || d == 0 || popsize > (1u << 24) || nsteps > 65535)
-    return ctx_fail_arg(MLF_E_BADARG, "mlf_walkers_create: popsize, nsteps, d must be positive");
-  if (d > 128) return ctx_fail_arg(MLF_E_DIM, "the resident walkers (one wave per walker, lane = coordinate pair) cover up to 128 dimensions");
-  if (int rc = ctx_ensure()) return rc;
+    return fail_arg(MLF_E_BADARG, "mlf_walkers_create: popsize, nsteps, d must be positive");
+  if (d > 128) return fail_arg(MLF_E_DIM, "the resident walkers (one wave per walker, lane = coordinate pair) cover up to 128 dimensions");
+  if (int rc = ensure_ctx()) return rc;
   mlf_walkers *w = new mlf_walkers();
   w->P = (int)popsize;
   w->nsteps = (int)nsteps;
@@ -338,14 +332,14 @@ int mlf_walkers_create(mlf_walkers **out, size_t popsize, size_t nsteps, size_t 
     hipError_t err = e.b->reserve(e.bytes);
     if (err != hipSuccess) {
       mlf_walkers_destroy(w);
-      return ctx_fail_hip(err, "device allocation for the walker population", "mlf_walk_api.hip", __LINE__);
+      return fail_hip(err, "device allocation for the walker population", "mlf_walk_api.hip", __LINE__);
     }
   }
   launch_walk_reset(state_of(w), ctx_stream());
   hipError_t err = hipStreamSynchronize(ctx_stream());
   if (err != hipSuccess) {
     mlf_walkers_destroy(w);
-    return ctx_fail_hip(err, "walker reset", "mlf_walk_api.hip", __LINE__);
+    return fail_hip(err, "walker reset", "mlf_walk_api.hip", __LINE__);
   }
   *out = w;
   return 0;
@@ -373,7 +367,7 @@ int mlf_walkers_destroy(mlf_walkers *w) {
 }
 
 int mlf_walkers_reset(mlf_walkers *w) {
-  if (!w) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
   launch_walk_reset(state_of(w), ctx_stream());
   if (w->nparams) CK(hipMemsetAsync(w->currentp.p, 0xff, (size_t)w->P * w->nparams * sizeof(double), ctx_stream()));
   if (w->ring.p) CK(hipMemsetAsync(w->ring.p, 0, 8, ctx_stream()));
@@ -383,7 +377,7 @@ int mlf_walkers_reset(mlf_walkers *w) {
 }
 
 int mlf_walkers_begin(mlf_walkers *w, double Lmin, int64_t *generation, uint8_t *flags) {
-  if (!w || !generation || !flags) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || !generation || !flags) return fail_arg(MLF_E_BADARG, "null pointer");
   hipStream_t s = ctx_stream();
   const size_t P = (size_t)w->P;
   // snapshot = generation (8 P bytes) followed by the flags (P bytes): one device-to-host copy
@@ -401,10 +395,10 @@ int mlf_walkers_begin(mlf_walkers *w, double Lmin, int64_t *generation, uint8_t 
 }
 
 int mlf_walkers_start(mlf_walkers *w, const int64_t *idx, size_t n, const double *u_rows, const double *L) {
-  if (!w || (n && (!idx || !u_rows || !L))) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || (n && (!idx || !u_rows || !L))) return fail_arg(MLF_E_BADARG, "null pointer");
   if (n == 0) return 0;
   for (size_t j = 0; j < n; ++j)
-    if (idx[j] < 0 || idx[j] >= w->P) return ctx_fail_arg(MLF_E_BADARG, "walker index out of range");
+    if (idx[j] < 0 || idx[j] >= w->P) return fail_arg(MLF_E_BADARG, "walker index out of range");
   hipStream_t s = ctx_stream();
   if (int rc = upload(w->idx, idx, n * 8, s)) return rc;
   if (int rc = upload(w->rows, u_rows, n * (size_t)w->d * 8, s)) return rc;
@@ -415,10 +409,10 @@ int mlf_walkers_start(mlf_walkers *w, const int64_t *idx, size_t n, const double
 }
 
 int mlf_walkers_points(mlf_walkers *w, const int64_t *idx, size_t n, double *out_rows) {
-  if (!w || (n && (!idx || !out_rows))) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || (n && (!idx || !out_rows))) return fail_arg(MLF_E_BADARG, "null pointer");
   if (n == 0) return 0;
   for (size_t j = 0; j < n; ++j)
-    if (idx[j] < 0 || idx[j] >= w->P) return ctx_fail_arg(MLF_E_BADARG, "walker index out of range");
+    if (idx[j] < 0 || idx[j] >= w->P) return fail_arg(MLF_E_BADARG, "walker index out of range");
   hipStream_t s = ctx_stream();
   if (int rc = upload(w->idx, idx, n * 8, s)) return rc;
   CK(w->rows.reserve(n * (size_t)w->d * 8));
@@ -430,10 +424,10 @@ int mlf_walkers_points(mlf_walkers *w, const int64_t *idx, size_t n, double *out
 }
 
 int mlf_walkers_brackets(mlf_walkers *w, const int64_t *idx, size_t n, double scale, const double *v_rows) {
-  if (!w || (n && (!idx || !v_rows))) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || (n && (!idx || !v_rows))) return fail_arg(MLF_E_BADARG, "null pointer");
   if (n == 0) return 0;
   for (size_t j = 0; j < n; ++j)
-    if (idx[j] < 0 || idx[j] >= w->P) return ctx_fail_arg(MLF_E_BADARG, "walker index out of range");
+    if (idx[j] < 0 || idx[j] >= w->P) return fail_arg(MLF_E_BADARG, "walker index out of range");
   hipStream_t s = ctx_stream();
   if (int rc = upload(w->vidx, idx, n * 8, s)) return rc;
   if (int rc = upload(w->vrows, v_rows, n * (size_t)w->d * 8, s)) return rc;
@@ -444,7 +438,7 @@ int mlf_walkers_brackets(mlf_walkers *w, const int64_t *idx, size_t n, double sc
 
 int mlf_walkers_set_direction_data(mlf_walkers *w, const double *axes, const double *live, size_t nlive,
                                    const double *std) {
-  if (!w) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
   hipStream_t s = ctx_stream();
   const size_t d = (size_t)w->d;
   if (axes) {
@@ -452,7 +446,7 @@ int mlf_walkers_set_direction_data(mlf_walkers *w, const double *axes, const dou
     w->have_axes = true;
   }
   if (live) {
-    if (nlive < 2) return ctx_fail_arg(MLF_E_BADARG, "differential directions need at least two live points");
+    if (nlive < 2) return fail_arg(MLF_E_BADARG, "differential directions need at least two live points");
     if (int rc = upload(w->live, live, nlive * d * 8, s)) return rc;
     w->nlive = (int)nlive;
     w->have_live = true;
@@ -467,8 +461,8 @@ int mlf_walkers_set_direction_data(mlf_walkers *w, const double *axes, const dou
 
 int mlf_walkers_brackets_philox(mlf_walkers *w, double scale, int kind, double dirscale, uint64_t seed,
                                 uint64_t offset, uint64_t *next_offset) {
-  if (!w || !next_offset) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (kind < 0 || kind > DIR_MIXTURE) return ctx_fail_arg(MLF_E_BADARG, "unknown direction kind");
+  if (!w || !next_offset) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (kind < 0 || kind > DIR_MIXTURE) return fail_arg(MLF_E_BADARG, "unknown direction kind");
   if (int rc = check_direction_data(w, kind)) return rc;
   launch_walk_brackets_philox(state_of(w), scale, kind, dirscale, dir_data(w), seed, offset, ctx_stream());
   CK(hipGetLastError());
@@ -478,12 +472,12 @@ int mlf_walkers_brackets_philox(mlf_walkers *w, double scale, int kind, double d
 
 int mlf_walkers_set_layer(mlf_walkers *w, int kind, const double *ctr, const double *mat, const double *wrap,
                           double maxradiussq) {
-  if (!w) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
   if (kind < 0) {
     w->layer_kind = -1;
     return 0;
   }
-  if (kind > 1 || !ctr || !mat) return ctx_fail_arg(MLF_E_BADARG, "layer kind must be 0 (affine) or 1 (scaling)");
+  if (kind > 1 || !ctr || !mat) return fail_arg(MLF_E_BADARG, "layer kind must be 0 (affine) or 1 (scaling)");
   hipStream_t s = ctx_stream();
   const size_t d = (size_t)w->d;
   if (int rc = upload(w->lay_ctr, ctr, d * 8, s)) return rc;
@@ -499,8 +493,8 @@ int mlf_walkers_set_layer(mlf_walkers *w, int kind, const double *ctr, const dou
 
 int mlf_walkers_propose(mlf_walkers *w, const double *unif, uint64_t seed, uint64_t offset, double *unew_out,
                         size_t *nacc) {
-  if (!w) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if ((unew_out == nullptr) != (nacc == nullptr)) return ctx_fail_arg(MLF_E_BADARG, "unew_out and nacc go together");
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
+  if ((unew_out == nullptr) != (nacc == nullptr)) return fail_arg(MLF_E_BADARG, "unew_out and nacc go together");
   hipStream_t s = ctx_stream();
   const WalkState st = state_of(w);
   const double *d_unif = nullptr;
@@ -529,9 +523,9 @@ int mlf_walkers_propose(mlf_walkers *w, const double *unif, uint64_t seed, uint6
 
 int mlf_walkers_finish(mlf_walkers *w, double Lmin, const double *pnew, const double *Lnew, size_t nacc,
                        size_t nparams, int64_t ringindex, double *rec) {
-  if (!w || !rec || (nacc && (!pnew || !Lnew))) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || !rec || (nacc && (!pnew || !Lnew))) return fail_arg(MLF_E_BADARG, "null pointer");
   if (!w->proposed || !w->compacted)
-    return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_finish without a preceding mlf_walkers_propose(unew_out != NULL)");
+    return fail_arg(MLF_E_STATE, "mlf_walkers_finish without a preceding mlf_walkers_propose(unew_out != NULL)");
   if (int rc = ensure_params(w, nparams)) return rc;
   hipStream_t s = ctx_stream();
   if (nacc) {
@@ -545,22 +539,22 @@ int mlf_walkers_finish(mlf_walkers *w, double Lmin, const double *pnew, const do
 
 int mlf_walkers_finish_dev(mlf_walkers *w, double Lmin, int tkind, double ta, double tb, int lkind,
                            const double *aux, double sigma, int64_t ringindex, double *rec) {
-  if (!w || !rec) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (!w->proposed) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_finish_dev without a preceding mlf_walkers_propose");
+  if (!w || !rec) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w->proposed) return fail_arg(MLF_E_STATE, "mlf_walkers_finish_dev without a preceding mlf_walkers_propose");
   const StepEval ev{nullptr, tkind, ta, tb, lkind, aux, sigma};
   return finish_common(w, Lmin, &ev, ringindex, rec);
 }
 
 int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, int64_t ringindex, double *rec) {
-  if (!w || !rec || !model) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (!w->proposed) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_finish_user without a preceding mlf_walkers_propose");
+  if (!w || !rec || !model) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w->proposed) return fail_arg(MLF_E_STATE, "mlf_walkers_finish_user without a preceding mlf_walkers_propose");
   const StepEval ev{model};
   return finish_common(w, Lmin, &ev, ringindex, rec);
 }
 
 int mlf_walkers_set_live(mlf_walkers *w, const double *us, const double *Ls, size_t nlive) {
-  if (!w || !us || !Ls) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (nlive < 2) return ctx_fail_arg(MLF_E_BADARG, "at least two live points are needed");
+  if (!w || !us || !Ls) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (nlive < 2) return fail_arg(MLF_E_BADARG, "at least two live points are needed");
   hipStream_t s = ctx_stream();
   if (int rc = upload(w->live, us, nlive * (size_t)w->d * 8, s)) return rc;
   if (int rc = upload(w->liveL, Ls, nlive * 8, s)) return rc;
@@ -571,12 +565,12 @@ int mlf_walkers_set_live(mlf_walkers *w, const double *us, const double *Ls, siz
 }
 
 int mlf_walkers_update_live(mlf_walkers *w, const int64_t *rows, size_t count, const double *us_rows, const double *Ls_rows) {
-  if (!w || (count && (!rows || !us_rows || !Ls_rows))) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
-  if (!w->have_liveL) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
+  if (!w || (count && (!rows || !us_rows || !Ls_rows))) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w->have_liveL) return fail_arg(MLF_E_STATE, "mlf_walkers_set_live not called");
   if (count == 0) return 0;
   const size_t d = (size_t)w->d;
   for (size_t j = 0; j < count; ++j)
-    if (rows[j] < 0 || rows[j] >= w->nlive) return ctx_fail_arg(MLF_E_BADARG, "live point index out of range");
+    if (rows[j] < 0 || rows[j] >= w->nlive) return fail_arg(MLF_E_BADARG, "live point index out of range");
   hipStream_t s = ctx_stream();
   // pinned staging, reused from call to call: every path that reads the device copy ends with a synchronisation of the
   // library's stream, so the copy queued by the previous update has long been made
@@ -605,21 +599,21 @@ int mlf_walkers_update_live(mlf_walkers *w, const int64_t *rows, size_t count, c
 int mlf_walkers_step_dev(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                          uint64_t offset, int tkind, double ta, double tb, int lkind, const double *aux, double sigma,
                          double *rec, uint64_t *next_offset) {
-  if (!w || !rec || !next_offset) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || !rec || !next_offset) return fail_arg(MLF_E_BADARG, "null pointer");
   return run_step(w, dirkind, StepEval{nullptr, tkind, ta, tb, lkind, aux, sigma}, StepParams{Lmin, scale, dirscale, w->r2, seed, offset},
                   rec, next_offset);
 }
 
 int mlf_walkers_step_user(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                           uint64_t offset, mlf_usermodel *model, double *rec, uint64_t *next_offset) {
-  if (!w || !rec || !next_offset || !model) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || !rec || !next_offset || !model) return fail_arg(MLF_E_BADARG, "null pointer");
   return run_step(w, dirkind, StepEval{model}, StepParams{Lmin, scale, dirscale, w->r2, seed, offset}, rec, next_offset);
 }
 
 int mlf_walkers_step_graph(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                            uint64_t offset, int tkind, double ta, double tb, int lkind, const double *aux, double sigma,
                            double *rec, uint64_t *next_offset) {
-  if (!w || !rec || !next_offset) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || !rec || !next_offset) return fail_arg(MLF_E_BADARG, "null pointer");
   const StepEval ev{nullptr, tkind, ta, tb, lkind, aux, sigma};
   if (int rc = check_step(w, dirkind, ev)) return rc;
   hipStream_t s = ctx_stream();
@@ -648,7 +642,7 @@ int mlf_walkers_step_graph(mlf_walkers *w, double Lmin, double scale, int dirkin
 int mlf_walkers_rounds_dev(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                            uint64_t offset, int tkind, double ta, double tb, int lkind, const double *aux, double sigma,
                            int max_rounds, double *rec, double *round_rows, int *rounds, uint64_t *next_offset) {
-  if (!w || !rec || !round_rows || !rounds || !next_offset) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w || !rec || !round_rows || !rounds || !next_offset) return fail_arg(MLF_E_BADARG, "null pointer");
   const int force_memory_form = max_rounds < 0;   // test hook: every round through global memory (the first form of this path)
   if (force_memory_form) max_rounds = -max_rounds;
   const StepEval ev{nullptr, tkind, ta, tb, lkind, aux, sigma};
@@ -719,8 +713,8 @@ int mlf_walkers_rounds_dev(mlf_walkers *w, double Lmin, double scale, int dirkin
       }))
     return rc;
   const int R = (int)w->h_rout[4];
-  if (w->h_rout[5] != 0.0) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_rounds_dev: a walker gave up waiting for the ring walker's rounds");
-  if (R < 1 || R > max_rounds) return ctx_fail_arg(MLF_E_STATE, "mlf_walkers_rounds_dev: the device reported an impossible round count");
+  if (w->h_rout[5] != 0.0) return fail_arg(MLF_E_STATE, "mlf_walkers_rounds_dev: a walker gave up waiting for the ring walker's rounds");
+  if (R < 1 || R > max_rounds) return fail_arg(MLF_E_STATE, "mlf_walkers_rounds_dev: the device reported an impossible round count");
   memcpy(rec, w->h_rout, nrec * sizeof(double));
   memcpy(round_rows, w->h_rout + nrec, (size_t)R * 5 * sizeof(double));
   *rounds = R;
@@ -730,7 +724,7 @@ int mlf_walkers_rounds_dev(mlf_walkers *w, double Lmin, double scale, int dirkin
 
 int mlf_walkers_export(mlf_walkers *w, double *allu, double *allL, int64_t *generation, double *currentt,
                        double *currentv, double *left, double *right, uint8_t *sl, uint8_t *sr) {
-  if (!w) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
   hipStream_t s = ctx_stream();
   const size_t P = (size_t)w->P, G = (size_t)w->nsteps + 1, d = (size_t)w->d;
   if (allu) CK(hipMemcpyAsync(allu, w->allu.p, P * G * d * 8, hipMemcpyDeviceToHost, s));
@@ -749,9 +743,9 @@ int mlf_walkers_export(mlf_walkers *w, double *allu, double *allL, int64_t *gene
 // ------------------------------------------------------------------ stateless forms ------------
 int mlf_within_unit_cube(const double *u, size_t n, size_t d, uint8_t *out) {
   if (n == 0) return 0;
-  if (!u || !out) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!u || !out) return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = check_nd(n, d)) return rc;
-  if (int rc = ctx_ensure()) return rc;
+  if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   if (int rc = upload(g_s.a, u, n * d * 8, s)) return rc;
   CK(g_s.b.reserve(n));
@@ -767,9 +761,9 @@ int mlf_evolve_propose(const double *currentu, const double *currentv, const dou
                        size_t d, double *unew, uint8_t *acceptable) {
   if (n == 0) return 0;
   if (!currentu || !currentv || !left || !right || !sl || !sr || !currentt || !unew || !acceptable)
-    return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+    return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = check_nd(n, d)) return rc;
-  if (int rc = ctx_ensure()) return rc;
+  if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   if (int rc = upload(g_s.a, currentu, n * d * 8, s)) return rc;
   if (int rc = upload(g_s.b, currentv, n * d * 8, s)) return rc;
@@ -801,9 +795,9 @@ int mlf_evolve_update(const uint8_t *acceptable, const double *Lnew_full, double
                       double *right, uint8_t *sl, uint8_t *sr, uint8_t *success, size_t n) {
   if (n == 0) return 0;
   if (!acceptable || !Lnew_full || !currentt || !left || !right || !sl || !sr || !success)
-    return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+    return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = check_nd(n, 1)) return rc;
-  if (int rc = ctx_ensure()) return rc;
+  if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   if (int rc = upload(g_s.a, acceptable, n, s)) return rc;
   if (int rc = upload(g_s.b, Lnew_full, n * 8, s)) return rc;
@@ -828,9 +822,9 @@ int mlf_evolve_update(const uint8_t *acceptable, const double *Lnew_full, double
 
 int mlf_step_back(double Lmin, double *allL, size_t n, size_t ngen, int64_t *generation, double *currentt) {
   if (n == 0) return 0;
-  if (!allL || !generation || !currentt) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!allL || !generation || !currentt) return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = check_nd(n, ngen)) return rc;
-  if (int rc = ctx_ensure()) return rc;
+  if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   if (int rc = upload(g_s.a, allL, n * ngen * 8, s)) return rc;
   if (int rc = upload(g_s.b, generation, n * 8, s)) return rc;
@@ -849,9 +843,9 @@ int mlf_step_back(double Lmin, double *allL, size_t n, size_t ngen, int64_t *gen
 int mlf_unitcube_line_intersection(const double *origin, const double *direction, size_t n, size_t d, double *tleft,
                                    double *tright) {
   if (n == 0) return 0;
-  if (!origin || !direction || !tleft || !tright) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!origin || !direction || !tleft || !tright) return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = check_nd(n, d)) return rc;
-  if (int rc = ctx_ensure()) return rc;
+  if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   if (int rc = upload(g_s.a, origin, n * d * 8, s)) return rc;
   if (int rc = upload(g_s.b, direction, n * d * 8, s)) return rc;
@@ -871,17 +865,17 @@ int mlf_update_vectorised_slice_sampler(const double *t, double *tleft, double *
                                         int64_t *status, double threshold, double shrink_factor, double *allu,
                                         double *allL, double *allp, size_t popsize, size_t d, size_t nparams,
                                         int64_t *discarded) {
-  if (!discarded) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!discarded) return fail_arg(MLF_E_BADARG, "null pointer");
   *discarded = 0;
   if (popsize == 0) return 0;
   if (!t || !tleft || !tright || !proposed_L || !proposed_u || !proposed_p || !worker_running || !status || !allu ||
       !allL || !allp)
-    return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+    return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = check_nd(popsize, d > nparams ? d : nparams)) return rc;
   for (size_t l = 0; l < popsize; ++l)
     if (worker_running[l] < 0 || (size_t)worker_running[l] >= popsize)
-      return ctx_fail_arg(MLF_E_BADARG, "worker_running entry out of range");
-  if (int rc = ctx_ensure()) return rc;
+      return fail_arg(MLF_E_BADARG, "worker_running entry out of range");
+  if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   const size_t P = popsize;
   if (int rc = upload(g_s.a, t, P * 8, s)) return rc;
@@ -915,9 +909,9 @@ int mlf_update_vectorised_slice_sampler(const double *t, double *tleft, double *
 
 int mlf_row_dist2(const double *a, const double *b, size_t n, size_t d, double *out) {
   if (n == 0) return 0;
-  if (!a || !b || !out) return ctx_fail_arg(MLF_E_BADARG, "null pointer");
+  if (!a || !b || !out) return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = check_nd(n, d)) return rc;
-  if (int rc = ctx_ensure()) return rc;
+  if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   if (int rc = upload(g_s.a, a, n * d * 8, s)) return rc;
   if (int rc = upload(g_s.b, b, n * d * 8, s)) return rc;
