@@ -6,6 +6,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+import loglike_reference as LR  # noqa: E402
 from ultranest_amd import likelihoods as lk  # noqa: E402
 from ultranest_amd import usermodels  # noqa: E402
 
@@ -43,8 +44,14 @@ def _funnel_scale(theta, data):
             + np.abs(0.5 * np.log(2 * np.pi * sigma ** 2) * len(data)))
 
 
-@pytest.mark.parametrize("d", [3, 10, 50, 101, 200])
+def _close_to_reference(L, ref, tight_scale):
+    """_close against the high-precision reference of loglike_reference (all rows with a long double, else its mpmath rows)"""
+    return _close(L[ref.rows], ref.ref.astype(np.float64), scale=tight_scale[ref.rows]) and ref.excess(L)[0] <= 1
+
+
+@pytest.mark.parametrize("d", [3, 10, 50, 101, 200, 63, 64, 127, 128])
 def test_funnel_and_gauss_against_numpy(d):
+    """(63 / 64: the staged form ends where a transform needs a second LDS buffer; 127 / 128: where it ends without one)"""
     rs = np.random.RandomState(d)
     F = usermodels.funnel(d)
     G = usermodels.gauss(d)
@@ -59,16 +66,21 @@ def test_funnel_and_gauss_against_numpy(d):
         L = F.loglike(th)
         assert np.array_equal(th, p)
         assert L.shape == (n,) and _close(L, _funnel_np(p, data), scale=_funnel_scale(p, data)), (d, n)
+        assert _close_to_reference(L, LR.Reference("funnel", p, data, with_mpmath=False), _funnel_scale(p, data)), (d, n)
         g = 0.5 + 0.1 * rs.normal(size=(n, d))
         gk = g.copy()
         assert np.array_equal(G.transform(g), g)      # no transform source: identity
-        assert _close(G.loglike(g), _gauss_np(g, centers), scale=_gauss_scale(g, centers)), (d, n)
+        Lg = G.loglike(g)
+        assert _close(Lg, _gauss_np(g, centers), scale=_gauss_scale(g, centers)), (d, n)
+        assert _close_to_reference(Lg, LR.Reference("gauss", g, centers, 0.1, with_mpmath=False), _gauss_scale(g, centers)), (d, n)
         assert np.array_equal(g, gk)
 
 
-@pytest.mark.parametrize("d", [7, 51, 129, 200, 6, 50])
+@pytest.mark.parametrize("d", [7, 51, 129, 200, 6, 50, 63, 64, 127, 128])
 def test_rosenbrock_against_the_builtin_kernels(d):
-    """odd d and d > 128: the built-in route evaluates row by row -- bit for bit; even d <= 128: pair layout, 1e-12"""
+    """odd d and d > 128: the built-in route evaluates row by row -- bit for bit; even d <= 128: pair layout, 1e-12; both
+    within 1e-12 * scale of the high-precision reference (63 / 64, 127 / 128: the ends of the staged form with and without
+    a transform)"""
     R = usermodels.rosenbrock(d)
     rs = np.random.RandomState(100 + d)
     for n in NS:
@@ -80,9 +92,11 @@ def test_rosenbrock_against_the_builtin_kernels(d):
             assert np.array_equal(L, Lb), (d, n, np.abs(L - Lb).max())
         else:
             assert _close(L, Lb), (d, n)
+        ref = LR.Reference("rosenbrock", p, with_mpmath=False)
+        assert ref.excess(L)[0] <= 1 and ref.excess(Lb)[0] <= 1, (d, n, ref.excess(L), ref.excess(Lb))
 
 
-@pytest.mark.parametrize("d", [10, 101])
+@pytest.mark.parametrize("d", [10, 101, 63, 64])
 def test_eval_dev_member_rows_only(d):
     """device pointers (torch tensors): rows outside the mask get L = -inf and keep their p row; the others are the host
     entry's values"""

@@ -232,7 +232,18 @@ def test_graph_replay_equals_kernel_by_kernel_launches(direction):
     ("eggbox", 2, "generate_random_direction", 2, 64),
     ("eggbox", 4, "generate_mixture_random_direction", 64, 1500),   # two chunks of 1024 walkers: statistics per chunk, then added up
     ("gauss", 6, "generate_region_random_direction", 32, 4500),     # above 4096 walkers: the ring walker's launch, then everybody else's
-    ("gauss", 5, "generate_random_direction", 16, 4500)])           # ... in the general form
+    ("gauss", 5, "generate_random_direction", 16, 4500),            # ... in the general form
+    # loglike_pairs / loglike_wave at both ends of every HW class of k_loglike_rows (HW = 8: 10 ... 16, 16: 18 ... 32,
+    # 32: 34 ... 64; HW = 2 and 4 are above)
+    ("rosenbrock", 16, "generate_mixture_random_direction", 24, 64),
+    ("eggbox", 18, "generate_region_random_direction", 24, 64),
+    ("rosenbrock", 32, "generate_differential_direction", 24, 64),
+    ("eggbox", 34, "generate_mixture_random_direction", 24, 64),
+    ("rosenbrock", 62, "generate_region_oriented_direction", 24, 64),
+    ("eggbox", 126, "generate_random_direction", 12, 64),           # HW = 64: the general form, pair layout inside loglike_wave
+    ("rosenbrock", 128, "generate_mixture_random_direction", 12, 64),
+    ("eggbox", 63, "generate_mixture_random_direction", 12, 64),    # odd d: the likelihood row on lane 0
+    ("rosenbrock", 127, "generate_random_direction", 12, 64)])
 def test_rounds_equal_single_steps(problem, d, direction, max_rounds, popsize):
     """mlf_walkers_rounds_dev (every walker's rounds back to back inside its wave, the ring walker deciding how many) against
     one mlf_walkers_step_dev call per round, driven as the reference's driver drives __next__ (integrator.py:1839-1950: call
@@ -242,14 +253,20 @@ def test_rounds_equal_single_steps(problem, d, direction, max_rounds, popsize):
     from ultranest_amd import likelihoods
     from ultranest_amd.regions import DeviceRNG
     rs = np.random.RandomState(100 + d)
+    nlive = 300 if d < 126 else 400      # enough live points for the affine layer at the widest d
     if problem == "gauss":
-        u = 0.5 + 0.08 * rs.normal(size=(300, d))
+        u = 0.5 + 0.08 * rs.normal(size=(nlive, d))
         loglike, transform = likelihoods.GaussLikelihood(0.5, 0.1, d), likelihoods.identity_transform
     elif problem == "eggbox":
         u = rs.uniform(size=(400, d))
+        if d > 10:
+            # the product of d cosines of uniform points is about 2**-d: by d = 52 it vanishes beside the 2 of (2 + prod)**5 and
+            # every live point has L = 32 exactly, a plateau no threshold can rise on.  Points around the peak at z = 4 pi
+            # (u = 0.4) keep the product of order one at every d
+            u = 0.4 + 0.01 * rs.normal(size=(400, d))
         loglike, transform = likelihoods.eggbox_loglike, likelihoods.eggbox_transform
     else:
-        u = 0.5 + 0.04 * rs.normal(size=(300, d))
+        u = 0.5 + 0.04 * rs.normal(size=(nlive, d))
         loglike, transform = likelihoods.rosenbrock_loglike, likelihoods.rosenbrock_transform
     u = np.clip(u, 1e-3, 1 - 1e-3)
     region = _gpu_region(u)
