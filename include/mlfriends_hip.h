@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MLF_ABI_VERSION 1
+#define MLF_ABI_VERSION 2
 
 #define MLF_E_BADARG 1      /* null pointer, zero dimension, inconsistent sizes            */
 #define MLF_E_DIM 2         /* dimensionality above MLF_MAX_DIM                            */
@@ -294,6 +294,23 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
                       double Lmin, int tkind, double ta, double tb, int lkind, const double *aux,
                       double sigma, double *out_u, double *out_p, double *out_L, size_t capacity,
                       size_t *nevaluated, size_t *nkept, uint64_t *next_offset);
+/* The driver's second region: a wrapping ellipsoid around the live points in PARAMETER space (reference WrappingEllipsoid,
+ * mlfriends.pyx:1551-1649), applied to every proposal batch between prior transform and likelihood (integrator.py:1789-1804).
+ * While one is set on the handle, mlf_region_refill and mlf_region_refill_user evaluate gate = inside(p) for the rows the
+ * region accepted, the likelihood counts only for accepted && gate, and *nevaluated = count(accepted && gate) (the
+ * reference's nc += nt); without one, every call, launch and result is what it was.
+ *   q = sum_j sum_k ((p_j - c_j) A_jk) (p_k - c_k) in the order of mlf_inside_ellipsoid (one accumulator, j outer, k inner,
+ *   no FMA); inside = q <= enlarge and p_k == fixed_val[k] wherever fixed_val[k] is not NaN.  A non-finite q is outside.
+ *   set         A: dense d x d, row-major; ctr: d.  A t-region with fixed dimensions (all live points share the value) hands
+ *               over its matrix on the variable dimensions with zeros elsewhere, centre 0 and fixed_val[k] = the shared
+ *               value on the fixed ones (NaN on the variable ones); fixed_val == NULL: none.  Needs mlf_region_set first
+ *               (d is the region's); a later mlf_region_set with another d clears it.
+ *   set_center  the centre alone (the driver re-centres on every live-point replacement, integrator.py:2757-2758).
+ *   clear       back to the ungated refill.
+ * mlf_region_refill_user with a t-region set needs a model created as MLF_USERMODEL_TREGION (else MLF_E_STATE). */
+int mlf_region_set_tregion(mlf_region *r, const double *A, const double *ctr, const double *fixed_val, double enlarge);
+int mlf_region_set_tregion_center(mlf_region *r, const double *ctr);
+int mlf_region_clear_tregion(mlf_region *r);
 /* raw Philox blocks (counter = (i, 0, stream, 0), key = seed) for known-answer tests */
 int mlf_debug_philox(uint64_t seed, unsigned stream, size_t nblocks, uint32_t *out);
 
@@ -472,6 +489,20 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
                           size_t code_cap, size_t *code_size, char *log, size_t log_cap);
 int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_transform, const double *aux,
                          size_t naux, mlf_usermodel **out);
+/* The same pair for a VARIANT of the wrapper kernel, each its own code object (the caller's cache keys it):
+ *   MLF_USERMODEL_DEFAULT  what mlf_usermodel_compile / _create make;
+ *   MLF_USERMODEL_TREGION  the gated form (-DMLF_USER_TREGION=1): the parameter-space wrapping ellipsoid of
+ *                          mlf_region_set_tregion is tested between transform and likelihood inside the one launch.  Such a
+ *                          model runs ONLY in mlf_region_refill_user on a region with a t-region set; every other launch of it
+ *                          (eval, eval_dev, the walkers, a refill without t-region) returns MLF_E_STATE.  Its entry is
+ *                          mlf_user_rows_tregion: create_variant returns MLF_E_BADARG for a code object compiled as the
+ *                          other variant. */
+#define MLF_USERMODEL_DEFAULT 0
+#define MLF_USERMODEL_TREGION 1
+int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant,
+                                  void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap);
+int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int has_transform, int variant,
+                                 const double *aux, size_t naux, mlf_usermodel **out);
 int mlf_usermodel_destroy(mlf_usermodel *model);
 int mlf_usermodel_eval(mlf_usermodel *model, const double *u, size_t n, double *p_out, double *L_out);
 int mlf_usermodel_eval_dev(mlf_usermodel *model, const double *d_u, size_t n, const uint8_t *d_member, double *d_p,

@@ -49,8 +49,16 @@ int fail_arg(int code, const char *msg);                                    // r
 // (argument meaning as in mlf_user_rows.hpp)
 int usermodel_dim(const mlf_usermodel *m);
 bool usermodel_has_transform(const mlf_usermodel *m);
+// the parameter-space wrapping ellipsoid of a gated launch (mlf_tregion_dev.hpp): dense d x d matrix, centre, fixed values (NaN =
+// variable dimension), all on the device; member2[i] = member[i] && inside(p_i) is written for every row
+struct TregionGate {
+  const double *A, *ctr, *fixed_val;
+  double enlarge;
+  uint8_t *member2;
+};
+bool usermodel_gated(const mlf_usermodel *m);   // loaded as the MLF_USERMODEL_TREGION variant: launches with a gate only
 int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
-                   hipStream_t s);
+                   hipStream_t s, const TregionGate *gate = nullptr);
 
 }  // namespace mlf
 

@@ -239,7 +239,8 @@ int mlf_region_destroy(mlf_region *r) {
                     &r->ell_A, &r->tq,  &r->gate,    &r->pts,     &r->mask, &r->row, &r->p4_LtF, &r->p4_TtF, &r->p4_y0, &r->lay_T64, &r->ell_L,
                     &r->gen, &r->gen2, &r->cube, &r->smask, &r->blk, &r->sout, &r->ax_zero, &r->ax_mat,
                     &r->s_invT, &r->s_lo, &r->s_hi, &r->s_thin, &r->s_count, &r->rf_p, &r->rf_L, &r->rf_out, &r->rf_aux,
-                    &r->rf_keep, &r->ax_pad, &r->s_invT_pad, &r->s_tc, &r->s_wc, &r->s_thc, &r->s_gate};
+                    &r->rf_keep, &r->ax_pad, &r->s_invT_pad, &r->s_tc, &r->s_wc, &r->s_thc, &r->s_gate,
+                    &r->tr_A, &r->tr_ctr, &r->tr_fixed, &r->rf_member2};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : r->events) (void)hipEventDestroy(e);
   r->filter.release();
@@ -275,6 +276,7 @@ int mlf_region_set(mlf_region *r, const double *unormed, size_t n, size_t d, int
   } arena_scope(&r->arena);
   r->ready = false;
   r->axes_ready = r->sampling_ready = false;   // a handle may be set again for another region (kernels.DeviceRegion recycles them)
+  if (r->d != (int)d) r->tr_on = false;   // a t-region belongs to its dimensionality
   r->n = (int)n;
   r->d = (int)d;
   r->dp = pick_dp((int)d);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <vector>
 
 #include "../../include/mlfriends_hip.h"
 #include "mlf_host.hpp"
@@ -150,8 +151,15 @@ int region_draw(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint6
   return 0;
 }
 
+// the t-region of the handle as a gated launch reads it
+TregionGate region_tregion(const mlf_region *r) {
+  return {r->tr_A.as<double>(), r->tr_ctr.as<double>(), r->tr_fixed.as<double>(), r->tr_enlarge, r->rf_member2.as<uint8_t>()};
+}
+
 // the body of mlf_region_refill / mlf_region_refill_user: `evaluate(rows, member, n, p_buf, L_buf, s, &prow)` enqueues the prior
-// transform and the likelihood of the n rows (p into p_buf, or *prow = rows for the identity; L into L_buf)
+// transform and the likelihood of the n rows (p into p_buf, or *prow = rows for the identity; L into L_buf).  With a t-region on
+// the handle, evaluate also fills r->rf_member2 = member && inside(p) (region_tregion): that mask replaces the membership
+// mask from there on and its count is *nevaluated; the choice between the two routes keeps using the region's count.
 template <class Evaluate>
 int region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin, Evaluate evaluate,
                   double *out_u, double *out_p, double *out_L, size_t capacity, size_t *nevaluated, size_t *nkept,
@@ -182,12 +190,22 @@ int region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed, uin
   CK(r->rf_L.reserve((size_t)n * sizeof(double)));
   CK(r->rf_out.reserve(capacity * (2 * (size_t)d + 1) * sizeof(double)));
   CK(r->rf_keep.reserve((size_t)n));
+  if (r->tr_on) CK(r->rf_member2.reserve((size_t)n));
   // prior transform + likelihood on the accepted proposals, where they are (reference _refill_samples,
   // integrator.py:1789-1804); only the points above the threshold travel to the host
   const double *prow = b.rows;   // identity transform: the parameters ARE the cube coordinates, no copy
   if (int rc = evaluate(b.rows, b.member, n, r->rf_p.as<double>(), r->rf_L.as<double>(), s, &prow)) return rc;
+  const uint8_t *counted = b.member;
+  if (r->tr_on) {
+    counted = r->rf_member2.as<uint8_t>();
+    const Compaction gated(counted, n, r->blk.as<unsigned>(), s);
+    size_t ngated = 0;
+    CK(gated.count(nsamples, &ngated));
+    *nevaluated = ngated;
+    if (ngated == 0) return 0;
+  }
   uint8_t *keep = r->rf_keep.as<uint8_t>();
-  launch_mask_greater(r->rf_L.as<double>(), n, Lmin, keep, s, b.member);
+  launch_mask_greater(r->rf_L.as<double>(), n, Lmin, keep, s, counted);
   double *ou = r->rf_out.as<double>(), *op = ou + capacity * (size_t)d, *oL = op + capacity * (size_t)d;
   const Compaction kept(keep, n, r->blk.as<unsigned>(), s);   // one count + scan for the three arrays
   kept.scatter(b.rows, d, ou, capacity);
@@ -239,12 +257,19 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
     return fail_arg(MLF_E_BADARG, "null pointer");
   if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
   if (lkind == 0 && !aux) return fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
-  auto evaluate = [&](const double *rows, const uint8_t *, long long n, double *pbuf, double *Lbuf, hipStream_t s,
+  auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
                       const double **prow) -> int {
     const int d = r->d;
     if (aux)
       if (int rc = upload(r->rf_aux, aux, (size_t)d * sizeof(double), s)) return rc;
-    if (tkind != 0) {
+    if (r->tr_on) {   // transform and t-region gate in one pass over the batch
+      // On the in-place route the gate kernel leaves the p rows of the rows the region rejected unwritten.  launch_loglike below
+      // still runs over all n rows of pbuf (allocated for n rows), so it evaluates stale contents there; member2 is 0 for those
+      // rows, and the threshold cut and the count read member2, so none of these values is ever used.
+      const TregionGate g = region_tregion(r);
+      if (tkind != 0) *prow = pbuf;
+      CK(launch_transform_gate({rows, n, d, member, tkind, ta, tb, pbuf, g.A, g.ctr, g.fixed_val, g.enlarge, g.member2}, s));
+    } else if (tkind != 0) {
       launch_elementwise_affine(rows, n * d, tkind, ta, tb, pbuf, s);
       *prow = pbuf;
     }
@@ -255,19 +280,56 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
                        next_offset);
 }
 
+int mlf_region_set_tregion(mlf_region *r, const double *A, const double *ctr, const double *fixed_val, double enlarge) {
+  if (!r || !A || !ctr) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!r->ready) return fail_arg(MLF_E_STATE, "region not set");
+  hipStream_t s = g_ctx.stream;
+  const size_t d = (size_t)r->d;
+  r->tr_on = false;
+  std::vector<double> fixed(d, NAN);
+  if (fixed_val) fixed.assign(fixed_val, fixed_val + d);
+  if (int rc = upload(r->tr_A, A, d * d * sizeof(double), s)) return rc;
+  if (int rc = upload(r->tr_ctr, ctr, d * sizeof(double), s)) return rc;
+  if (int rc = upload(r->tr_fixed, fixed.data(), d * sizeof(double), s)) return rc;
+  CK(hipStreamSynchronize(s));
+  r->tr_enlarge = enlarge;
+  r->tr_on = true;
+  return 0;
+}
+
+int mlf_region_set_tregion_center(mlf_region *r, const double *ctr) {
+  if (!r || !ctr) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!r->ready || !r->tr_on) return fail_arg(MLF_E_STATE, "no t-region set (mlf_region_set_tregion)");
+  hipStream_t s = g_ctx.stream;
+  if (int rc = upload(r->tr_ctr, ctr, (size_t)r->d * sizeof(double), s)) return rc;
+  CK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mlf_region_clear_tregion(mlf_region *r) {
+  if (!r) return fail_arg(MLF_E_BADARG, "null pointer");
+  r->tr_on = false;
+  return 0;
+}
+
 int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
                            mlf_usermodel *model, double *out_u, double *out_p, double *out_L, size_t capacity,
                            size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
   if (!r || !model || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
     return fail_arg(MLF_E_BADARG, "null pointer");
   if (r->ready && usermodel_dim(model) != r->d) return fail_arg(MLF_E_BADARG, "user model and region differ in dimensionality");
+  if (r->tr_on != usermodel_gated(model))
+    return fail_arg(MLF_E_STATE, r->tr_on ? "the region has a t-region: the user model must be loaded as MLF_USERMODEL_TREGION"
+                                          : "user model loaded as MLF_USERMODEL_TREGION, but the region has no t-region");
   // one mlf_user_rows launch for transform + likelihood; rows outside the membership mask are not evaluated (L = -inf: the
   // threshold cut that follows drops them either way)
   auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
                       const double **prow) -> int {
     double *p = usermodel_has_transform(model) ? pbuf : nullptr;
     if (p) *prow = p;
-    return usermodel_rows(model, rows, n, member, p, Lbuf, s);
+    if (!r->tr_on) return usermodel_rows(model, rows, n, member, p, Lbuf, s);
+    const TregionGate g = region_tregion(r);
+    return usermodel_rows(model, rows, n, member, p, Lbuf, s, &g);
   };
   return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
                        next_offset);

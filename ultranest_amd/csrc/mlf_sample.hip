@@ -9,6 +9,7 @@
 // rows travel back.
 #include "mlf_sample.hpp"
 #include "mlf_philox_dev.hpp"
+#include "mlf_tregion_dev.hpp"
 
 #include <math.h>
 
@@ -340,10 +341,7 @@ __global__ void k_untransform_rows(const double *t, long long n, int d, const do
 }
 
 // prior transforms of the benchmark problems, elementwise: 0 identity, 1 x*a + b, 2 (x*a)*b
-__global__ void k_elementwise_affine(const double *x, long long n, int tkind, double a, double b, double *out) {
-  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  const double v = x[e];
+__device__ __forceinline__ double elementwise_affine(double v, int tkind, double a, double b) {
   double p = v;
   if (tkind == 1) {
     const double m = v * a;
@@ -352,7 +350,70 @@ __global__ void k_elementwise_affine(const double *x, long long n, int tkind, do
     const double m = v * a;
     p = m * b;
   }
-  out[e] = p;
+  return p;
+}
+
+__global__ void k_elementwise_affine(const double *x, long long n, int tkind, double a, double b, double *out) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  out[e] = elementwise_affine(x[e], tkind, a, b);
+}
+
+// Prior transform + t-region gate of a refill batch (TransformGateArgs, mlf_sample.hpp).  The mapping of k_prep: one LANE owns
+// one row, its centred parameters p_k - c_k live in registers (DP doubles, zero beyond d), the matrix is staged in LDS as
+// [d][DP] (zero padded) and broadcast; the outer index re-reads u_j (cache) and repeats the transform, bit-identical.
+// Only the rows of `member` get their p row written (k_elementwise_affine transforms every row): the p rows of the others keep
+// what the buffer held, and member2 = 0 tells every later stage not to count them.
+template <int DP>
+__global__ __launch_bounds__(256) void k_transform_gate(TransformGateArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double tg_mat[];   // [d][DP]
+  const int tid = threadIdx.x, d = a.d;
+  const long long i = (long long)blockIdx.x * 256 + tid;
+  const bool mine = i < a.n && (a.member == nullptr || a.member[i] != 0);
+  for (int e = tid; e < d * DP; e += 256) {
+    const int j = e / DP, k = e - j * DP;
+    tg_mat[e] = k < d ? a.A[j * d + k] : 0.0;
+  }
+  __syncthreads();
+  bool ok = mine;
+  if (__any(mine)) {   // a wave without an accepted row skips the d^2 work
+    const double *row = a.u + (mine ? i : 0) * (long long)d;
+    double dl[DP];
+#pragma unroll
+    for (int k = 0; k < DP; ++k) {
+      double v = 0.0;
+      if (k < d) {
+        const double pk = elementwise_affine(row[k], a.tkind, a.ta, a.tb);
+        if (mine && a.tkind != 0) a.p[i * d + k] = pk;
+        ok = ok && mlf_tregion_fixed_ok(pk, a.fixed_val[k]);
+        v = pk - a.ctr[k];
+      }
+      dl[k] = v;
+    }
+    const double q = mlf_tregion_q<DP>(
+        d, [&](int j) { return elementwise_affine(row[j], a.tkind, a.ta, a.tb) - a.ctr[j]; }, [&](int k) { return dl[k]; },
+        [&](int j, int k) { return tg_mat[j * DP + k]; });
+    ok = ok && q <= a.enlarge;
+  }
+  if (i < a.n) a.member2[i] = ok ? 1 : 0;
+}
+
+// the same above 128 dimensions: one thread per row, everything from global memory
+__global__ __launch_bounds__(256) void k_transform_gate_wide(TransformGateArgs a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  bool ok = a.member == nullptr || a.member[i] != 0;
+  if (ok) {
+    const int d = a.d;
+    const double *row = a.u + i * d;
+    if (a.tkind != 0) {
+      double *prow = a.p + i * d;
+      for (int k = 0; k < d; ++k) prow[k] = elementwise_affine(row[k], a.tkind, a.ta, a.tb);
+      row = prow;
+    }
+    ok = mlf_tregion_inside(row, d, a.A, a.ctr, a.fixed_val, a.enlarge);
+  }
+  a.member2[i] = ok ? 1 : 0;
 }
 
 // mask[e] = v[e] > threshold (and also[e], where a mask of the rows that count is given: the others hold no likelihood)
@@ -594,6 +655,35 @@ void launch_untransform_rows(const double *t, long long n, int d, const double *
 void launch_elementwise_affine(const double *x, long long n, int tkind, double a, double b, double *out, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_elementwise_affine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, tkind, a, b, out);
+}
+
+hipError_t launch_transform_gate(const TransformGateArgs &a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.tkind != 0 && a.p == nullptr) return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)((a.n + 255) / 256);
+  const int dp = pick_dp(a.d);
+  if (dp < 0) return hipErrorInvalidValue;
+  if (wide_dims(dp)) {
+    hipLaunchKernelGGL(k_transform_gate_wide, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+  }
+  const size_t lds = (size_t)a.d * dp * sizeof(double);
+  switch (dp) {
+#define X(D)                                                                                    \
+  case D:                                                                                       \
+    if (lds > 48 * 1024) {                                                                      \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_transform_gate<D>),  \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      if (e != hipSuccess) return e;                                                            \
+    }                                                                                           \
+    hipLaunchKernelGGL(k_transform_gate<D>, dim3(grid), dim3(256), lds, s, a);                  \
+    break;
+    MLF_FOR_EACH_DP(X)
+#undef X
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
 
 void launch_mask_greater(const double *v, long long n, double threshold, uint8_t *mask, hipStream_t s, const uint8_t *also) {

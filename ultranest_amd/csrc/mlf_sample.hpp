@@ -27,6 +27,23 @@ void launch_thin_by_multiplicity(const long long *count, const double *thin_u, l
 void launch_untransform_rows(const double *t, long long n, int d, const double *invT, const double *ctr,
                              const double *wrap_shift, double *w, uint8_t *in_cube, hipStream_t s);
 void launch_elementwise_affine(const double *x, long long n, int tkind, double a, double b, double *out, hipStream_t s);
+// The elementwise prior transform of launch_elementwise_affine and the parameter-space wrapping ellipsoid (mlf_tregion_dev.hpp) in
+// one pass over n rows of d doubles: p = transform(u) is written for the rows with member[i] != 0 (member == nullptr: all; nothing
+// for tkind 0, where the rows are the parameters and p may be null) and member2[i] = member[i] && inside(p_i) for every row.
+// A: dense d x d, ctr, fixed_val: d doubles (NaN = variable dimension), all on the device.
+struct TransformGateArgs {
+  const double *u;
+  long long n;
+  int d;
+  const uint8_t *member;
+  int tkind;
+  double ta, tb;
+  double *p;
+  const double *A, *ctr, *fixed_val;
+  double enlarge;
+  uint8_t *member2;
+};
+hipError_t launch_transform_gate(const TransformGateArgs &a, hipStream_t s);
 // mask[e] = v[e] > threshold (&& also[e] where `also` is given)
 void launch_mask_greater(const double *v, long long n, double threshold, uint8_t *mask, hipStream_t s, const uint8_t *also = nullptr);
 void launch_mask_and(uint8_t *mask, const uint8_t *other, long long n, hipStream_t s);

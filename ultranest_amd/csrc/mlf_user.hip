@@ -28,6 +28,7 @@ struct mlf_usermodel {
   hipFunction_t fn = nullptr;
   int d = 0;
   bool has_transform = false;
+  bool gated = false;   // the MLF_USERMODEL_TREGION variant: mlf_user_rows takes the gate's five parameters as well
   long long naux = 0;
   DevBuf aux;
   DevBuf hu, hp, hL;   // staging of mlf_usermodel_eval (host arrays)
@@ -101,9 +102,14 @@ namespace mlf {
 
 int usermodel_dim(const mlf_usermodel *m) { return m->d; }
 bool usermodel_has_transform(const mlf_usermodel *m) { return m->has_transform; }
+bool usermodel_gated(const mlf_usermodel *m) { return m->gated; }
 
 int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
-                   hipStream_t s) {
+                   hipStream_t s, const TregionGate *gate) {
+  // the two variants differ in their parameter lists: never launch one with the other's
+  if (m->gated != (gate != nullptr))
+    return fail_arg(MLF_E_STATE, m->gated ? "user model loaded as the t-region variant: it runs only in a refill with a t-region set"
+                                          : "user model not loaded as the t-region variant (mlf_usermodel_create_variant)");
   if (n <= 0) return 0;
   const long long blocks = (n + 63) / 64;
   if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
@@ -116,6 +122,14 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
   const double *a_aux = m->aux.as<double>();
   long long a_naux = m->naux;
   double *a_p = p, *a_L = L;
+  if (gate) {
+    const double *g_A = gate->A, *g_ctr = gate->ctr, *g_fixed = gate->fixed_val;
+    double g_enlarge = gate->enlarge;
+    unsigned char *g_member2 = gate->member2;
+    void *args[] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L, &g_A, &g_ctr, &g_fixed, &g_enlarge, &g_member2};
+    CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
+    return 0;
+  }
   void *args[] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
   CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
   return 0;
@@ -127,7 +141,15 @@ extern "C" {
 
 int mlf_usermodel_compile(const char *source, const char *include_dir, int has_transform, void *code_out, size_t code_cap,
                           size_t *code_size, char *log, size_t log_cap) {
+  return mlf_usermodel_compile_variant(source, include_dir, has_transform, MLF_USERMODEL_DEFAULT, code_out, code_cap, code_size,
+                                       log, log_cap);
+}
+
+int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant, void *code_out,
+                                  size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
   if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION)
+    return fail_arg(MLF_E_BADARG, "unknown user-model variant");
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
@@ -139,7 +161,8 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
   const std::string src = std::string(source) + "\n#include \"mlf_user_rows.hpp\"\n";
   const std::string inc = std::string("-I") + include_dir;
   const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
-                        has_transform ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0"};
+                        has_transform ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
+                        variant == MLF_USERMODEL_TREGION ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0"};
   hiprtcProgram prog = nullptr;
   hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
   if (res != HIPRTC_SUCCESS) {
@@ -180,8 +203,15 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
 
 int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_transform, const double *aux, size_t naux,
                          mlf_usermodel **out) {
+  return mlf_usermodel_create_variant(code, nbytes, d, has_transform, MLF_USERMODEL_DEFAULT, aux, naux, out);
+}
+
+int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int has_transform, int variant, const double *aux,
+                                 size_t naux, mlf_usermodel **out) {
   if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
+  if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION)
+    return fail_arg(MLF_E_BADARG, "unknown user-model variant");
   if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
   if (d > MLF_MAX_DIM) return fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
   if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return fail_arg(MLF_E_BADARG, "not a code object (ELF)");
@@ -190,9 +220,16 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
   mlf_usermodel *m = new mlf_usermodel();
   m->d = (int)d;
   m->has_transform = has_transform != 0;
+  m->gated = variant == MLF_USERMODEL_TREGION;
   m->naux = (long long)naux;
   hipError_t e = hipModuleLoadData(&m->module, code);
-  if (e == hipSuccess) e = hipModuleGetFunction(&m->fn, m->module, "mlf_user_rows");
+  if (e == hipSuccess && hipModuleGetFunction(&m->fn, m->module, m->gated ? "mlf_user_rows_tregion" : "mlf_user_rows") != hipSuccess) {
+    // the variants' entries differ in name: this code object was compiled as the other one (or is no user model at all)
+    (void)hipGetLastError();
+    (void)hipModuleUnload(m->module);
+    delete m;
+    return fail_arg(MLF_E_BADARG, "the code object has no entry of this variant (compiled as another variant?)");
+  }
   if (e == hipSuccess) e = m->aux.reserve(naux ? naux * sizeof(double) : sizeof(double));
   if (e == hipSuccess && naux) e = hipMemcpyAsync(m->aux.p, aux, naux * sizeof(double), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);

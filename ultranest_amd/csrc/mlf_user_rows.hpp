@@ -23,6 +23,12 @@
 //           kUserRowsLdsBudget = 64 KiB per wave: d >= 64 with a transform, d >= 128 without.  64 KiB still lets two
 //           such waves share a CU's 160 KiB of LDS; above it one wave per CU would be left, with nothing to hide its
 //           load latency behind.
+//
+// Gated form (MLF_USER_TREGION=1, its own code object): the driver's parameter-space wrapping ellipsoid between transform
+// and likelihood (mlf_tregion_dev.hpp; mlf_region_set_tregion).  After transform_row has written the p row the lane
+// tests it, calls the likelihood only if it passes and writes member2[i] = member[i] && inside(p_i); the kernel is named
+// mlf_user_rows_tregion and takes (tr_A, tr_ctr, tr_fixed, tr_enlarge, member2) behind its other parameters.  Matrix, centre and fixed values are read
+// through wave-uniform addresses: no extra LDS, the same choice of form.
 #pragma once
 
 #define MLF_USER_ROWS_LDS_BUDGET 65536
@@ -37,6 +43,17 @@ __host__ __device__ inline unsigned mlf_user_rows_lds_bytes(int d, bool has_p_bu
 
 #ifndef MLF_USER_HAS_TRANSFORM
 #define MLF_USER_HAS_TRANSFORM 0
+#endif
+#ifndef MLF_USER_TREGION
+#define MLF_USER_TREGION 0
+#endif
+#if MLF_USER_TREGION
+#include "mlf_tregion_dev.hpp"
+// the two forms differ in their parameter lists, so they differ in their names: a code object loaded as the other variant has
+// no such entry (mlf_usermodel_create_variant) instead of a launch with the wrong arguments
+#define MLF_USER_ROWS_ENTRY mlf_user_rows_tregion
+#else
+#define MLF_USER_ROWS_ENTRY mlf_user_rows
 #endif
 
 namespace mlf_user_detail {
@@ -101,8 +118,15 @@ __device__ inline void transform_row(const double *x, double *y, int d, const do
 
 }  // namespace mlf_user_detail
 
-extern "C" __global__ __launch_bounds__(64) void mlf_user_rows(const double *u, long long n, int d, const unsigned char *member,
-                                                                const double *aux, long long naux, double *p, double *L) {
+extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const double *u, long long n, int d, const unsigned char *member,
+                                                                const double *aux, long long naux, double *p, double *L
+#if MLF_USER_TREGION
+                                                                ,
+                                                                const double *__restrict__ tr_A, const double *__restrict__ tr_ctr,
+                                                                const double *__restrict__ tr_fixed, double tr_enlarge,
+                                                                unsigned char *member2
+#endif
+) {
   using namespace mlf_user_detail;
   const int lane = threadIdx.x;
   const long long j0 = (long long)blockIdx.x * 64;
@@ -114,9 +138,15 @@ extern "C" __global__ __launch_bounds__(64) void mlf_user_rows(const double *u, 
   const unsigned long long live = __ballot(mine);
   if (live == 0) {   // no member row in this block: nothing is read
     if (L != nullptr && lane < nrows) L[i] = neg_inf();
+#if MLF_USER_TREGION
+    if (lane < nrows) member2[i] = 0;
+#endif
     return;
   }
   double like = neg_inf();
+#if MLF_USER_TREGION
+  bool pass = false;
+#endif
   const bool p_buffer = p != nullptr && MLF_USER_HAS_TRANSFORM;
   if (mlf_user_rows_lds_bytes(d, p_buffer) != 0) {
     extern __shared__ __attribute__((aligned(16))) double mlf_user_lds[];
@@ -132,7 +162,12 @@ extern "C" __global__ __launch_bounds__(64) void mlf_user_rows(const double *u, 
         transform_row(x, y, d, aux, naux);
         x = y;
       }
+#if MLF_USER_TREGION
+      pass = mlf_tregion_inside(x, d, tr_A, tr_ctr, tr_fixed, tr_enlarge);
+      if (L != nullptr && pass) like = mlf_user_loglike(x, d, aux, naux);
+#else
       if (L != nullptr) like = mlf_user_loglike(x, d, aux, naux);
+#endif
     }
     __syncthreads();
     if (p != nullptr) stage_out(p + j0 * d, nrows * d, d, b, live, lane);
@@ -143,8 +178,16 @@ extern "C" __global__ __launch_bounds__(64) void mlf_user_rows(const double *u, 
       transform_row(x, y, d, aux, naux);
       x = y;
     }
+#if MLF_USER_TREGION
+    pass = mlf_tregion_inside(x, d, tr_A, tr_ctr, tr_fixed, tr_enlarge);
+    if (L != nullptr && pass) like = mlf_user_loglike(x, d, aux, naux);
+#else
     if (L != nullptr) like = mlf_user_loglike(x, d, aux, naux);
+#endif
   }
+#if MLF_USER_TREGION
+  if (lane < nrows) member2[i] = pass ? 1 : 0;   // pass implies mine
+#endif
   if (L != nullptr && lane < nrows) L[i] = like;
 }
 

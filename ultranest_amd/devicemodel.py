@@ -24,7 +24,11 @@ them by their ``device_spec`` marker (a ``UserModelSpec``, never one of the ``(k
 
 * ``MLFriends.refill`` (and ``RobustEllipsoidRegion`` / ``SimpleRegion``): draw, region test, transform + likelihood in
   ONE fused launch (``mlf_region_refill_user``), threshold, compaction -- the rows outside the membership mask are not
-  evaluated;
+  evaluated.  With the driver's parameter-space wrapping ellipsoid (``refill(..., tregion=...)``, reference
+  integrator.py:1789-1804) the same launch tests ``tregion.inside(p)`` between transform and likelihood: the model's
+  *gated* variant (``handle(with_transform, gated=True)``: the wrapper compiled with ``-DMLF_USER_TREGION=1``, its own
+  code object, compiled on first gated use) calls the likelihood only for the rows that pass, and the batch never
+  leaves the device;
 * ``PopulationSliceSampler``: host-RNG mode through ``mlf_walkers_finish_user``, Philox mode through
   ``mlf_walkers_step_user``; only the acceptable proposals are evaluated.
 
@@ -53,7 +57,9 @@ from ._lib import check, f64, ptr
 
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 HEADER = os.path.join(INCLUDE_DIR, "mlf_user_rows.hpp")
-# what mlf_usermodel_compile passes to hiprtc besides -I and -DMLF_USER_HAS_TRANSFORM (part of the cache key)
+GATE_HEADER = os.path.join(INCLUDE_DIR, "mlf_tregion_dev.hpp")      # included by the gated variant only
+VARIANT_DEFAULT, VARIANT_TREGION = 0, 1                             # MLF_USERMODEL_* of include/mlfriends_hip.h
+# what mlf_usermodel_compile passes to hiprtc besides -I, -DMLF_USER_HAS_TRANSFORM and -DMLF_USER_TREGION (part of the cache key)
 COMPILE_OPTIONS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off")
 MLF_E_COMPILE = 5
 
@@ -69,19 +75,25 @@ class DeviceModelCompileError(RuntimeError):
         RuntimeError.__init__(self, "the device model did not compile:\n" + log)
 
 
-def _cache_key(source, has_transform):
+def _cache_key(source, has_transform, gated=False):
     h = hashlib.sha256()
     with open(HEADER, "rb") as fh:
         header = fh.read()
-    for part in (source.encode(), b"\0", repr((COMPILE_OPTIONS, bool(has_transform))).encode(), b"\0", header):
+    options = repr((COMPILE_OPTIONS, bool(has_transform)))
+    if gated:
+        options += " tregion"
+        with open(GATE_HEADER, "rb") as fh:
+            header += fh.read()
+    for part in (source.encode(), b"\0", options.encode(), b"\0", header):
         h.update(part)
     return h.hexdigest()
 
 
-def compile_model(source, has_transform):
-    """The gfx950 code object (bytes) of `source` + the wrapper kernel; cached per process."""
+def compile_model(source, has_transform, gated=False):
+    """The gfx950 code object (bytes) of `source` + the wrapper kernel; cached per process.  gated: the variant with the
+    t-region test between transform and likelihood (module docstring), another program under its own key."""
     global compile_calls
-    key = _cache_key(source, has_transform)
+    key = _cache_key(source, has_transform, gated)
     code = _code_cache.get(key)
     if code is not None:
         return code
@@ -92,8 +104,12 @@ def compile_model(source, has_transform):
     for _ in range(2):
         buf = ctypes.create_string_buffer(cap)
         compile_calls += 1
-        rc = L.mlf_usermodel_compile(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), buf, cap,
-                                     ctypes.byref(size), log, len(log))
+        if gated:
+            rc = L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)),
+                                                 VARIANT_TREGION, buf, cap, ctypes.byref(size), log, len(log))
+        else:
+            rc = L.mlf_usermodel_compile(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), buf, cap,
+                                         ctypes.byref(size), log, len(log))
         if rc == MLF_E_COMPILE:
             raise DeviceModelCompileError(log.value.decode(errors="replace"))
         if rc != 0 and size.value > cap:      # code object larger than the buffer: once more with its size
@@ -130,10 +146,14 @@ class _Callback(object):
 class _Handle(object):
     """One loaded model (``mlf_usermodel``) on the library's device."""
 
-    def __init__(self, code, ndim, has_transform, aux):
+    def __init__(self, code, ndim, has_transform, aux, gated=False):
         h = ctypes.c_void_p()
-        check(_lib.lib().mlf_usermodel_create(code, len(code), int(ndim), int(bool(has_transform)), ptr(aux), len(aux),
-                                              ctypes.byref(h)))
+        if gated:
+            check(_lib.lib().mlf_usermodel_create_variant(code, len(code), int(ndim), int(bool(has_transform)),
+                                                          VARIANT_TREGION, ptr(aux), len(aux), ctypes.byref(h)))
+        else:
+            check(_lib.lib().mlf_usermodel_create(code, len(code), int(ndim), int(bool(has_transform)), ptr(aux), len(aux),
+                                                  ctypes.byref(h)))
         self._h = h
         self.has_transform = bool(has_transform)
 
@@ -172,14 +192,19 @@ class DeviceModel(object):
         self.loglike = _Callback(self, "loglike")
         self.transform = _Callback(self, "transform")
 
-    def handle(self, with_transform=True):
+    def handle(self, with_transform=True, gated=False):
         """The loaded model (created on first use: needs the GPU).  with_transform=False: the variant whose prior
-        transform is the identity (a route that pairs this model's likelihood with ``identity_transform``)."""
-        key = bool(with_transform and self.has_transform)
+        transform is the identity (a route that pairs this model's likelihood with ``identity_transform``).  gated=True:
+        the variant with the t-region test (compiled and loaded on first gated use; it runs in a gated refill only)."""
+        tr = bool(with_transform and self.has_transform)
+        key = (tr, True) if gated else tr
         h = self._handles.get(key)
         if h is None:
-            code = self.code if key == self.has_transform else compile_model(self.source, key)
-            h = self._handles[key] = _Handle(code, self.ndim, key, self.aux)
+            if gated:
+                code = compile_model(self.source, tr, gated=True)
+            else:
+                code = self.code if tr == self.has_transform else compile_model(self.source, tr)
+            h = self._handles[key] = _Handle(code, self.ndim, tr, self.aux, gated=gated)
         return h.handle
 
     def close(self):

@@ -188,8 +188,10 @@ def refill_samples(region, tregion, transform, loglike, Lmin, ndraw, pointstore=
     """One proposal batch (reference `_refill_samples`, integrator.py:1773-1837 with
     draw_multiple=True): region.sample -> transform -> tregion.inside -> loglike on the accepted
     rows -> keep logl > Lmin.  Returns (u, v, logl, ncalls)."""
-    if tregion is None and pointstore is None and hasattr(region, "refill"):
-        got = region.refill(ndraw, Lmin, transform, loglike)     # device-resident batch when possible
+    if pointstore is None and hasattr(region, "refill"):         # (a point store logs the rejected evaluations: host route)
+        # device-resident batch when possible, the tregion's test included
+        got = region.refill(ndraw, Lmin, transform, loglike) if tregion is None else \
+            region.refill(ndraw, Lmin, transform, loglike, tregion=tregion)
         if got is not None:
             return got
     u = region.sample(nsamples=ndraw)
@@ -223,7 +225,8 @@ class StaticNestedSampler(object):
 
     def __init__(self, x_dim, loglike, transform=None, num_live_points=400, ndraw=4096,
                  region_class=MLFriends, transform_layer_class=LocalAffineLayer, nbootstraps=30, seed=1,
-                 device_rng=None, stepsampler=None, pointstore=None, log_dir=None, paramnames=None, keep_tree=False):
+                 device_rng=None, stepsampler=None, pointstore=None, log_dir=None, paramnames=None, keep_tree=False,
+                 build_tregion=False):
         self.x_dim = x_dim
         # optional result files in the reference's layout (ultranest_amd.results): the run then keeps the
         # tree of dead and live points (root / pointpile, as the reference's sampler object does) and
@@ -246,8 +249,11 @@ class StaticNestedSampler(object):
         self.nlive = num_live_points
         self.ndraw = ndraw
         self.nbootstraps = nbootstraps
+        # build_tregion: keep the reference driver's second region, a WrappingEllipsoid around the live points in parameter
+        # space (integrator.py:1575, :2135-2157), apply it to every proposal batch and re-centre it on every replacement
+        self.build_tregion = bool(build_tregion)
         self.updater = RegionUpdater(x_dim, region_class=region_class, transform_layer_class=transform_layer_class,
-                                     build_tregion=False)
+                                     build_tregion=self.build_tregion)
         self.seed = seed
         self.ncall = 0
         self.ncall_region = 0
@@ -295,6 +301,8 @@ class StaticNestedSampler(object):
             self.pointpile = PointPile(self.x_dim, v_live.shape[1])
             live_nodes = [self.pointpile.make_node(li, ui, vi) for li, ui, vi in zip(logl, u, v_live)]
             self.root = TreeNode(id=-1, value=-np.inf, children=list(live_nodes))
+        if self.build_tregion:
+            v_live = np.array(v_live, dtype=float)      # own, writable rows: replaced in place below
         ph["initial_points_s"] = tick() - t_run
         logz = -np.inf
         h_terms = []
@@ -307,7 +315,8 @@ class StaticNestedSampler(object):
         while it < max_iters:
             if logvol <= next_update_logvol:
                 t0 = tick()
-                self.updater.update(u, nbootstraps=self.nbootstraps, minvol=np.exp(logvol))
+                self.updater.update(u, nbootstraps=self.nbootstraps, minvol=np.exp(logvol),
+                                    active_p=v_live if self.build_tregion else None)
                 next_update_logvol = logvol + np.log(0.8)
                 if self.stepsampler is not None:
                     self.stepsampler.region_changed(logl, self.updater.region)
@@ -354,7 +363,7 @@ class StaticNestedSampler(object):
                         ip = 0
                         continue
                 t0 = tick()
-                nu, nv, nl, nc = refill_samples(region, None, self.transform, self.loglike, Lmin, self.ndraw,
+                nu, nv, nl, nc = refill_samples(region, self.updater.tregion, self.transform, self.loglike, Lmin, self.ndraw,
                                                 pointstore=self.pointstore, ncall=self.ncall)
                 ph["first_refill_s" if ph["refills"] == 0 else "refill_s"] += tick() - t0
                 ph["refills"] += 1
@@ -369,6 +378,12 @@ class StaticNestedSampler(object):
             region.transformLayer.clusterids[worst] = 0
             u = region.u
             logl[worst] = newl
+            if self.build_tregion:          # the live parameter rows follow; the tregion is re-centred (integrator.py:2757-2758)
+                if newv is None:
+                    newv = np.asarray(self.transform(newu[None, :]))[0]
+                v_live[worst] = newv
+                if self.updater.tregion is not None:
+                    self.updater.tregion.update_center(np.mean(v_live, axis=0))
             if live_nodes is not None:      # the replacement hangs below the point it replaced (integrator.py:2749-2765)
                 if newv is None:
                     newv = np.asarray(self.transform(newu[None, :]))[0]

@@ -281,6 +281,7 @@ class DeviceRegion(object):
         """hand the handle (and its buffers) to the next region"""
         if self._h:
             _lib.lib().mlf_region_set_option(self._h, None, 0, 1)     # the next owner starts from the process defaults
+            _lib.lib().mlf_region_clear_tregion(self._h)              # ... and without this one's t-region
             if len(DeviceRegion._idle) < DeviceRegion._IDLE_MAX:
                 DeviceRegion._idle.append(self._h)
                 self._h = ctypes.c_void_p()
@@ -367,6 +368,25 @@ class DeviceRegion(object):
 
     def set_sampling_data(self, invT, bbox_lo, bbox_hi):
         check(_lib.lib().mlf_region_set_sampling_data(self._h, ptr(f64(invT)), ptr(f64(bbox_lo)), ptr(f64(bbox_hi))))
+
+    def set_tregion(self, A, center, fixed_val, enlarge):
+        """The driver's parameter-space wrapping ellipsoid for the refill calls that follow (mlf_region_set_tregion): dense
+        (d, d) matrix, (d,) centre, (d,) fixed values (NaN = variable dimension) or None."""
+        d = self._d
+        A, center = f64(A), f64(center)
+        fixed_val = None if fixed_val is None else f64(fixed_val)
+        if A.shape != (d, d) or center.shape != (d,) or (fixed_val is not None and fixed_val.shape != (d,)):
+            raise ValueError("t-region arrays do not match the region's %d dimensions" % d)
+        check(_lib.lib().mlf_region_set_tregion(self._h, ptr(A), ptr(center), ptr(fixed_val), float(enlarge)))
+
+    def set_tregion_center(self, center):
+        center = f64(center)
+        if center.shape != (self._d,):
+            raise ValueError("t-region centre does not match the region's %d dimensions" % self._d)
+        check(_lib.lib().mlf_region_set_tregion_center(self._h, ptr(center)))
+
+    def clear_tregion(self):
+        check(_lib.lib().mlf_region_clear_tregion(self._h))
 
     def sample(self, method, nsamples, seed, offset, capacity=None):
         """Device-side draw + membership test + compaction.  Returns (accepted rows (k, d), next offset)."""

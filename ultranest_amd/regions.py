@@ -359,6 +359,7 @@ class _DeviceState(object):
         self.thresholds = None
         self.axes_T = None
         self.sampling_data = None
+        self.tregion = None       # what the handle's t-region was set from: (object, dense matrix, centre, fixed values, enlarge)
         self.fast_key = None      # identities + write counter of everything the device state was built from
 
     @staticmethod
@@ -386,25 +387,51 @@ class _DeviceState(object):
             return False
         return True
 
-    def refill(self, region, use_scan, method, nsamples, Lmin, tspec, lspec):
-        """Device-resident proposal batch (draw, region test, prior transform, likelihood, threshold)."""
-        return self._draw(region, use_scan, method, "refill", nsamples, Lmin, tspec, lspec)
+    def refill(self, region, use_scan, method, nsamples, Lmin, tspec, lspec, tregion=None):
+        """Device-resident proposal batch (draw, region test, prior transform, likelihood, threshold); with `tregion` (one
+        that `tregion_on_device` accepts) its test gates the likelihood on the device."""
+        return self._draw(region, use_scan, method, "refill", nsamples, Lmin, tspec, lspec, tregion=tregion)
 
-    def refill_user(self, region, use_scan, method, nsamples, Lmin, model, with_transform):
-        """The same batch with a user model (ultranest_amd.devicemodel): transform + likelihood in one fused launch."""
-        return self._draw(region, use_scan, method, "refill_user", nsamples, Lmin, model.handle(with_transform))
+    def refill_user(self, region, use_scan, method, nsamples, Lmin, model, with_transform, tregion=None):
+        """The same batch with a user model (ultranest_amd.devicemodel): transform + likelihood in one fused launch (with
+        `tregion`: the model's gated variant, the test inside that launch)."""
+        handle = model.handle(with_transform) if tregion is None else model.handle(with_transform, gated=True)
+        return self._draw(region, use_scan, method, "refill_user", nsamples, Lmin, handle, tregion=tregion)
 
     def sample(self, region, use_scan, method, nsamples):
         """Device-side draw + membership + compaction with the region's ``device_rng``."""
         return self._draw(region, use_scan, method, "sample", nsamples)[0]
 
-    def _draw(self, region, use_scan, method, call, nsamples, *args):
+    def _draw(self, region, use_scan, method, call, nsamples, *args, tregion=None):
         """handle.<call>(method, nsamples, seed, offset, *args) at the region's ``device_rng`` position, which moves on to the
-        next offset; returns the call's results without that offset."""
+        next offset; returns the call's results without that offset.  The refill calls run with the handle's t-region
+        brought to `tregion` (None: none)."""
         handle = self._prepare_sampling(region, use_scan, method)
+        if call != "sample":
+            self.sync_tregion(handle, tregion, region.u.shape[1] if tregion is not None else 0)
         rng = region.device_rng
         *out, rng.offset = getattr(handle, call)(method, nsamples, rng.seed, rng.offset, *args)
         return tuple(out)
+
+    def sync_tregion(self, handle, tregion, ndim):
+        """Keep the handle's copy of the driver's t-region current: nothing for an unchanged one, the centre alone after
+        ``update_center`` (every iteration of the driver), a full set for another object, matrix, enlargement or set of
+        fixed values, a clear for None."""
+        old = self.tregion
+        if tregion is None:
+            if old is not None:
+                handle.clear_tregion()
+                self.tregion = None
+            return
+        A, ctr, fixed, enlarge = tregion_dense(tregion, ndim)
+        if (old is not None and old[0] is tregion and old[4] == enlarge and np.array_equal(old[1], A)
+                and (fixed is None) == (old[3] is None) and (fixed is None or np.array_equal(old[3], fixed, equal_nan=True))):
+            if not np.array_equal(old[2], ctr):
+                handle.set_tregion_center(ctr)
+                self.tregion = old[:2] + (ctr.copy(),) + old[3:]
+            return
+        handle.set_tregion(A, ctr, fixed, enlarge)
+        self.tregion = (tregion, A.copy(), ctr.copy(), fixed, enlarge)
 
     def _prepare_sampling(self, region, use_scan, method):
         handle = self.sync(region, use_scan)
@@ -801,13 +828,18 @@ class MLFriends(_LivePoints):
     _DEVICE_METHOD = dict(sample_from_boundingbox=0, sample_from_wrapping_ellipsoid=1,
                           sample_from_transformed_boundingbox=2, sample_from_points=3)
 
-    def refill(self, nsamples, Lmin, transform, loglike):
+    def refill(self, nsamples, Lmin, transform, loglike, tregion=None):
         """One proposal batch of the driver's ``_refill_samples`` (reference integrator.py:1773-1837)
         without leaving the device: draw with the current sampling method, region test, prior
         transform, likelihood, and only the points with L > Lmin come back as ``(u, p, L, nc)``.
         Needs ``device_rng`` and ``device_spec`` on both callbacks (ultranest_amd.likelihoods), or a user model's
         callbacks (ultranest_amd.devicemodel.device_route); returns None if that does not hold (the caller then uses
-        sample() + callbacks)."""
+        sample() + callbacks).
+
+        `tregion`: the driver's parameter-space ``WrappingEllipsoid`` (integrator.py:1789-1804).  Its ``inside`` test then
+        runs on the device between transform and likelihood, in the arithmetic of the host test; the likelihood counts
+        only for the rows of the region that pass, and ``nc`` is their number.  None is returned for a tregion that cannot
+        go to the device (``tregion_on_device``)."""
         tspec, lspec = getattr(transform, "device_spec", None), getattr(loglike, "device_spec", None)
         method = self._DEVICE_METHOD.get(getattr(self.current_sampling_method, "__name__", ""), None)
         user = devicemodel.device_route(transform, loglike)
@@ -820,11 +852,16 @@ class MLFriends(_LivePoints):
             return None
         if method >= 2 and not self._device_tspace():
             return None
+        gate = {}     # without a tregion the device calls keep their positional form
+        if tregion is not None:
+            if not tregion_on_device(tregion, self.u.shape[1]):
+                return None
+            gate = dict(tregion=tregion)
         if user is not None:
-            u, p, L, nc = self._dev.refill_user(self, self._uses_scan(), method, nsamples, Lmin, *user)
+            u, p, L, nc = self._dev.refill_user(self, self._uses_scan(), method, nsamples, Lmin, *user, **gate)
         else:
-            u, p, L, nc = self._dev.refill(self, self._uses_scan(), method, nsamples, Lmin, tspec, lspec)
-        if nc == 0:   # the region accepted nothing: re-roll the method like sample() does (:1180-1183)
+            u, p, L, nc = self._dev.refill(self, self._uses_scan(), method, nsamples, Lmin, tspec, lspec, **gate)
+        if nc == 0:   # the region (or the tregion) accepted nothing: re-roll the method like sample() does (:1180-1183)
             self.current_sampling_method = self.sampling_methods[np.random.randint(len(self.sampling_methods))]
         return u, p, L, nc
 
@@ -1004,3 +1041,37 @@ class WrappingEllipsoid(object):
             return inside_variable
         inside_fixed = np.all(self.u[0, ~self.variable_dims] == u[:, ~self.variable_dims], axis=1)
         return np.logical_and(inside_fixed, inside_variable)
+
+
+def tregion_on_device(tregion, ndim):
+    """Whether the device refill can apply `tregion` (``MLFriends.refill``): a ``WrappingEllipsoid`` with its own ``inside``,
+    its ellipsoid created and ``enlarge`` set, over `ndim` parameters (derived parameters keep the host route)."""
+    if not isinstance(tregion, WrappingEllipsoid) or type(tregion).inside is not WrappingEllipsoid.inside:
+        return False
+    inv, ctr = getattr(tregion, "ellipsoid_invcov", None), getattr(tregion, "ellipsoid_center", None)
+    if inv is None or ctr is None or tregion.enlarge is None:
+        return False
+    if np.ndim(tregion.u) != 2 or np.shape(tregion.u)[1] != ndim:
+        return False
+    nvar = ndim if tregion.variable_dims is Ellipsis else int(np.count_nonzero(tregion.variable_dims))
+    return np.shape(inv) == (nvar, nvar) and np.shape(ctr) == (nvar,)
+
+
+def tregion_dense(tregion, ndim):
+    """``(A, centre, fixed_val, enlarge)`` of a tregion that ``tregion_on_device`` accepts, as mlf_region_set_tregion takes
+    them: the dense (ndim, ndim) matrix with ``ellipsoid_invcov`` on the variable dimensions and zeros elsewhere (zero
+    terms leave the quadratic form's accumulator as it is), centre 0 on the fixed dimensions, and ``fixed_val`` = the
+    value a fixed dimension must equal (``u[0, k]``), NaN on the variable ones (None without fixed dimensions)."""
+    inv = np.asarray(tregion.ellipsoid_invcov, dtype=float)
+    ctr = np.asarray(tregion.ellipsoid_center, dtype=float)
+    if tregion.variable_dims is Ellipsis:
+        return inv, ctr, None, float(tregion.enlarge)
+    var = np.flatnonzero(tregion.variable_dims)
+    A = np.zeros((ndim, ndim))
+    A[np.ix_(var, var)] = inv
+    c = np.zeros(ndim)
+    c[var] = ctr
+    fixed = np.full(ndim, np.nan)
+    fix = ~np.asarray(tregion.variable_dims)
+    fixed[fix] = np.asarray(tregion.u, dtype=float)[0, fix]
+    return A, c, fixed, float(tregion.enlarge)
