@@ -423,6 +423,46 @@ int mlf_walkers_export(mlf_walkers *w, double *allu, double *allL, int64_t *gene
                        double *currentt, double *currentv, double *left, double *right,
                        uint8_t *searching_left, uint8_t *searching_right);
 
+/* Whole-population random walk = one refill of PopulationRandomWalkSampler (popstepsampler.py:299-353) on the device: popsize
+ * independent walkers, each nsteps moves of direction -> cube-line intersection -> truncated-normal step -> transform ->
+ * likelihood -> accept.  No chain is kept; the handle owns [popsize][d] state and the device copies its setters upload
+ * (set_layer / set_direction_data / set_live: as the mlf_walkers setters of the same names).
+ *   refill_dev   built-in transform (tkind, ta, tb) and likelihood (lkind, aux, sigma), as mlf_walkers_finish_dev.  Walker i
+ *                starts at live row below(word, nlive) with L = Ls[row] (no filter on Ls > Lmin, as the reference); per step
+ *                v = the direction of kind dirkind (0-6) and length dirscale, [tleft, tright] = the line's part inside the unit
+ *                cube, t = a standard normal truncated to it by inverse CDF from one uniform (evaluated on the side of the
+ *                smaller tail), proposal u + v t; accepted iff strictly inside the open cube and L > Lmin (NaN: rejected; a
+ *                proposal rounded onto the boundary counts as a reject).
+ *                Outputs, one row / entry per walker: out_u, out_p (d doubles; p is NaN for a walker that never moved), out_L,
+ *                out_start (live row), out_ever (accepted some move), out_last (accepted the last move), out_tleft / out_tright
+ *                (may be NULL: the cube limits of the last step's line).  counts (6 doubles): rejected moves; walkers with
+ *                out_last; of those, moves farther than the MLFriends radius and the sum of log(distance / radius + 1e-10),
+ *                start row -> final point through the layer (0 without a layer); walkers that never moved; the form that
+ *                ran (0: one launch, 1: three launches per step).
+ *                Philox: every draw is a function of (seed, offset, walker, step) only.  Directions: stream 2, block group
+ *                walker * nsteps + step of (d + 1) / 2 + 2 blocks; stream 7: walker i owns blocks offset + i (nsteps + 1) +
+ *                [0, nsteps] (block 0: start row; block 1 + s: the uniform of step s).  *next_offset = offset + popsize * nsteps
+ *                * ((d + 1) / 2 + 2).
+ *                Two forms, the same results bit for bit: built-in models with even d <= 64 and an affine layer or none run all
+ *                steps in ONE launch with the walker's state in registers; everything else runs three launches per step
+ *                (proposal, evaluation, accept) on HBM state.  form = 1 (test hook) forces the latter; 0 chooses by shape.
+ *   refill_user  the same with a user model's kernel as the evaluation (the cube flag is its member mask; the built-in
+ *                likelihood kernel of the three-launch form has no mask: it evaluates every row, and the accept ignores the
+ *                value of a proposal outside the cube). */
+typedef struct mlf_rwalk mlf_rwalk;
+int mlf_rwalk_create(mlf_rwalk **out, size_t popsize, size_t nsteps, size_t d);
+int mlf_rwalk_destroy(mlf_rwalk *w);
+int mlf_rwalk_set_layer(mlf_rwalk *w, int kind, const double *ctr, const double *mat, const double *wrap,
+                        double maxradiussq);
+int mlf_rwalk_set_direction_data(mlf_rwalk *w, const double *axes, const double *live, size_t nlive,
+                                 const double *std);
+int mlf_rwalk_set_live(mlf_rwalk *w, const double *us, const double *Ls, size_t nlive);
+int mlf_rwalk_refill_dev(mlf_rwalk *w, double Lmin, int dirkind, double dirscale, uint64_t seed, uint64_t offset,
+                         int tkind, double ta, double tb, int lkind, const double *aux, double sigma, int form,
+                         double *out_u, double *out_p, double *out_L, int64_t *out_start, uint8_t *out_ever,
+                         uint8_t *out_last, double *out_tleft, double *out_tright, double *counts,
+                         uint64_t *next_offset);
+
 /* ---- integrator bookkeeping on the host (no GPU involved) -----------------
  * MultiCounter.passing_node of ultranest/netiter.py:721-855 for (nbootstraps + 1) counters, with the
  * insertion-order U test of ultranest/ordertest.py.  member: [ncounters][nroots] uint8, row 0 all
@@ -513,6 +553,10 @@ int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t 
 int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, int64_t ringindex, double *rec);
 int mlf_walkers_step_user(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                           uint64_t offset, mlf_usermodel *model, double *rec, uint64_t *next_offset);
+int mlf_rwalk_refill_user(mlf_rwalk *w, double Lmin, int dirkind, double dirscale, uint64_t seed, uint64_t offset,
+                          mlf_usermodel *model, double *out_u, double *out_p, double *out_L, int64_t *out_start,
+                          uint8_t *out_ever, uint8_t *out_last, double *out_tleft, double *out_tright, double *counts,
+                          uint64_t *next_offset);
 
 /* ---- bench / profiling helpers ---------------------------------------------------------- */
 /* Runs the neighbour-scan kernel `reps` times on device data and returns the mean kernel time

@@ -138,6 +138,15 @@ SIGNATURES = {
     "mlf_usermodel_create_variant": [_vp, _sz, _sz, _int, _int, _vp, _sz, _vp],
     "mlf_walkers_finish_user": [_vp, _dbl, _vp, ctypes.c_int64, _vp],
     "mlf_walkers_step_user": [_vp, _dbl, _dbl, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp],
+    "mlf_rwalk_create": [_vp, _sz, _sz, _sz],
+    "mlf_rwalk_destroy": [_vp],
+    "mlf_rwalk_set_layer": [_vp, _int, _vp, _vp, _vp, _dbl],
+    "mlf_rwalk_set_direction_data": [_vp, _vp, _vp, _sz, _vp],
+    "mlf_rwalk_set_live": [_vp, _vp, _vp, _sz],
+    "mlf_rwalk_refill_dev": [_vp, _dbl, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _int, _dbl, _dbl, _int, _vp, _dbl, _int,
+                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mlf_rwalk_refill_user": [_vp, _dbl, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _vp,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

@@ -13,14 +13,11 @@
 
 #include "mlf_loglike_dev.hpp"
 #include "mlf_philox_dev.hpp"
+#include "mlf_walk_dev.hpp"
 
 namespace mlf {
 
 namespace {
-
-__device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-__device__ __forceinline__ bool inside_open_unit(double x) { return 0.0 < x && x < 1.0; }
 
 // evolve_update for one walker (stepfuncs.pyx:160-183); returns the final success flag
 __device__ __forceinline__ bool update_walker(bool hit, double &t, double &left, double &right, uint8_t &sl,
@@ -73,23 +70,6 @@ __device__ __forceinline__ void step_back_walker(double Lmin, double *L, int G, 
   int nbelow = 0;
   for (long long k = 0; k < width; ++k) nbelow += (L[k] < Lmin) ? 1 : 0;
   step_back_unwind(Lmin, L, width, nbelow, gen, t);
-}
-
-// whitened coordinates of one point (T1: fmod wrap, centre, k-ascending FMA chain like BLAS)
-__device__ __forceinline__ void whiten_point(const WalkLayer &ly, const double *x, int d, int c, double &out) {
-  if (ly.kind == 1) {
-    double v = x[c];
-    if (ly.wrap && !isnan(ly.wrap[c])) v = fmod(v + ly.wrap[c], 1.0);
-    out = (v - ly.ctr[c]) / ly.mat[c];
-    return;
-  }
-  double acc = 0.0;
-  for (int k = 0; k < d; ++k) {
-    double v = x[k];
-    if (ly.wrap && !isnan(ly.wrap[k])) v = fmod(v + ly.wrap[k], 1.0);
-    acc = __builtin_fma(v - ly.ctr[k], ly.mat[(size_t)k * d + c], acc);
-  }
-  out = acc;
 }
 
 }  // namespace
@@ -182,85 +162,7 @@ __global__ void k_walk_brackets(WalkState w, const long long *idx, int n, double
 // 100 walkers.  Here a wave owns one walker: rows are read coalesced, per-walker scalars are computed by all
 // lanes alike (same inputs, same result) and written by lane 0.
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// Direction of a new slice for walker i (stepfuncs.pyx:348-535), drawn on the device: every lane gets ITS coordinates
-// vr[h] = v[lane + 64 h] (0 beyond d).  Philox stream 2, (npairs + 2) blocks per walker: block 0 = integer picks + mixture
-// coin, blocks 1.. = Box-Muller pairs (coordinate k takes the cosine / sine branch of pair k / 2).
-__device__ void dw_direction(const WalkState &w, int i, int lane, int kind, double dirscale, const WalkDirData &dd,
-                             unsigned long long seed, unsigned long long offset, double (&vr)[2]) {
-  const int d = w.d;
-  const int npairs = (d + 1) / 2;
-  const unsigned long long base = offset + (unsigned long long)i * (unsigned long long)(npairs + 2);
-  unsigned pick[4];
-  philox_block(seed, 2u, base, pick);
-  int k = kind;
-  if (k == DIR_MIXTURE) k = (u01(pick[2], pick[3]) < 0.5) ? DIR_DIFFERENTIAL : DIR_REGION_ORIENTED;
-  vr[0] = vr[1] = 0.0;
-  if (k == DIR_CUBE_ORIENTED || k == DIR_CUBE_ORIENTED_SCALED) {
-    const int j = (int)below(pick[0], (unsigned)d);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c = lane + 64 * h;
-      if (c < d) vr[h] = c == j ? ((k == DIR_CUBE_ORIENTED) ? dirscale : dirscale * dd.std[j]) : 0.0;
-    }
-  } else if (k == DIR_REGION_ORIENTED) {
-    const int j = (int)below(pick[0], (unsigned)d);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c = lane + 64 * h;
-      if (c < d) vr[h] = dd.axes[(size_t)j * d + c] * dirscale;
-    }
-  } else if (k == DIR_DIFFERENTIAL) {
-    const unsigned a = below(pick[0], (unsigned)dd.nlive);
-    unsigned b = below(pick[1], (unsigned)(dd.nlive - 1));
-    if (b >= a) ++b;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c = lane + 64 * h;
-      if (c < d) vr[h] = (dd.live[(size_t)a * d + c] - dd.live[(size_t)b * d + c]) * dirscale;
-    }
-  } else {   // DIR_RANDOM, DIR_REGION_RANDOM: isotropic unit vector of length dirscale
-    double g[2] = {0.0, 0.0};
-    double part = 0.0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c = lane + 64 * h;
-      if (c < d) {
-        unsigned r4[4];
-        philox_block(seed, 2u, base + 1 + (c >> 1), r4);
-        const double rad = sqrt(-2.0 * log(u01(r4[0], r4[1])));
-        const double ang = 2.0 * M_PI * u01(r4[2], r4[3]);
-        g[h] = (c & 1) ? rad * sin(ang) : rad * cos(ang);
-        part += g[h] * g[h];
-      }
-    }
-    const double f = dirscale / sqrt(wave_sum(part));
-    g[0] *= f;
-    g[1] *= f;
-    if (k == DIR_RANDOM) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-        if (lane + 64 * h < d) vr[h] = g[h];
-    } else {   // v[r] = sum_c axes[r][c] * v1[c]   (einsum 'ij,kj->ki', stepfuncs.pyx:476)
-      double acc[2] = {0.0, 0.0};
-      for (int c = 0; c < d; ++c) {
-        const double v1c = __shfl(c < 64 ? g[0] : g[1], c & 63, 64);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int r = lane + 64 * h;
-          if (r < d) acc[h] += dd.axes[(size_t)r * d + c] * v1c;
-        }
-      }
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-        if (lane + 64 * h < d) vr[h] = acc[h];
-    }
-  }
-}
+// (wave_sum, dw_direction: mlf_walk_dev.hpp)
 
 // setup_brackets with a device-side direction draw for a walker whose bracket is undefined (popstepsampler.py:483-505).
 // `t`, `left`, `right`, `sl`, `sr` are the wave's copies of the walker state (updated here); vr (optional) receives the
@@ -411,59 +313,11 @@ __global__ __launch_bounds__(256) void k_walk_expand(WalkState w, const unsigned
   for (int k = 0; k < w.nparams; ++k) w.pnew[(size_t)i * w.nparams + k] = pc[(size_t)rank * w.nparams + k];
 }
 
-// diagnose_move_distances for one walker that moved (wave-wide, lane = whitened coordinate; T rows are read
-// coalesced, squared differences summed by a fixed shuffle tree): uo = the point the step started from, un = the
-// accepted point
-// d <= 64, affine layer: lane k holds coordinate k of the two points (vo: where the step started, vn: the accepted point; 0
-// beyond d); returns the squared whitened distance on lane 0.  Both points share every matrix element; the chains read the
-// centred coordinates by lane broadcast (same values and order as whiten_point: results are identical)
-__device__ __forceinline__ double move_distance_regs(const WalkLayer &ly, int d, int lane, double vo, double vn) {
-  if (lane < d) {
-    if (ly.wrap && !isnan(ly.wrap[lane])) {
-      vo = fmod(vo + ly.wrap[lane], 1.0);
-      vn = fmod(vn + ly.wrap[lane], 1.0);
-    }
-    vo -= ly.ctr[lane];
-    vn -= ly.ctr[lane];
-  } else {
-    vo = vn = 0.0;
-  }
-  double ta = 0.0, tb = 0.0;
-  const int c = lane < d ? lane : 0;
-  for (int k = 0; k < d; ++k) {
-    const double m = ly.mat[(size_t)k * d + c];
-    ta = __builtin_fma(__shfl(vo, k, 64), m, ta);
-    tb = __builtin_fma(__shfl(vn, k, 64), m, tb);
-  }
-  double acc = 0.0;
-  if (lane < d) {
-    const double diff = ta - tb;
-    acc = diff * diff;
-  }
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  return acc;
-}
-
+// diagnose_move_distances for one walker that moved (move_distance_rows, mlf_walk_dev.hpp): uo = the point the step started
+// from, un = the accepted point
 __device__ __forceinline__ void dw_move_distance(const WalkState &w, const WalkLayer &ly, int i, int lane, const double *uo,
                                                  const double *un) {
-  double acc = 0.0;
-  if (ly.kind == 0 && w.d <= 64) {
-    double vo = 0.0, vn = 0.0;
-    if (lane < w.d) {
-      vo = uo[lane];
-      vn = un[lane];
-    }
-    acc = move_distance_regs(ly, w.d, lane, vo, vn);
-  } else {
-    for (int c = lane; c < w.d; c += 64) {
-      double ta, tb;
-      whiten_point(ly, uo, w.d, c, ta);
-      whiten_point(ly, un, w.d, c, tb);
-      const double diff = ta - tb;
-      acc += diff * diff;
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  }
+  const double acc = move_distance_rows(ly, w.d, lane, uo, un);
   if (lane == 0) w.dist2[i] = acc;
 }
 
@@ -1198,16 +1052,8 @@ __global__ void k_line_intersection(const double *origin, const double *directio
                                     double *tright) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  double lo = qnan(), hi = qnan();
-  for (int k = 0; k < d; ++k) {
-    const double m = 1.0 / direction[(size_t)i * d + k];
-    const double nn = m * (origin[(size_t)i * d + k] - 0.5);
-    const double kk = fabs(m) * 0.5;
-    const double t1 = -nn - kk;
-    const double t2 = -nn + kk;
-    if (!isnan(t1) && (isnan(lo) || t1 > lo)) lo = t1;
-    if (!isnan(t2) && (isnan(hi) || t2 < hi)) hi = t2;
-  }
+  double lo, hi;
+  line_cube_row(origin + (size_t)i * d, direction + (size_t)i * d, d, lo, hi);
   tleft[i] = lo;
   tright[i] = hi;
 }

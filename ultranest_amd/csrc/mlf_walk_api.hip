@@ -10,23 +10,41 @@
 #include "../../include/mlfriends_hip.h"
 #include "mlf_ctx.hpp"
 #include "mlf_misc.hpp"
+#include "mlf_rwalk.hpp"
 #include "mlf_sample.hpp"
 #include "mlf_walk.hpp"
 
 using namespace mlf;
 
-struct mlf_walkers {
-  int P = 0, nsteps = 0, d = 0, nparams = 0;
-  DevBuf allu, allL, generation, currentt, currentv, left, right, sl, sr, currentp;
-  DevBuf unew, movable, acceptable, success, pnew, Lnew, dist2;
-  DevBuf gmax, flags, snap, idx, rows, vals, vidx, vrows, unif, blk, compact, pc, Lc, rec, aux;
-  DevBuf axes, live, std, lay_ctr, lay_mat, lay_wrap, liveL, ring, partials;
+// Device copies of what the region and the live points contribute, with the state of their setters: shared by the two
+// population handles (mlf_walkers, mlf_rwalk)
+struct RegionCopies {
+  int d = 0;
+  DevBuf axes, live, std, lay_ctr, lay_mat, lay_wrap, liveL;
   bool have_liveL = false;
   int nlive = 0;
   bool have_axes = false, have_live = false, have_std = false;
   int layer_kind = -1;
   bool layer_wrap = false;
   double r2 = 1.0;
+  void release_copies() {
+    for (DevBuf *b : {&axes, &live, &std, &lay_ctr, &lay_mat, &lay_wrap, &liveL}) b->release();
+  }
+};
+
+// PopulationRandomWalkSampler's population (mlf_rwalk.hip): no chain, a walker is its current (u, p, L)
+struct mlf_rwalk : RegionCopies {
+  int P = 0, nsteps = 0;
+  DevBuf u, p, L, start, ever, last, rej, tl, tr, dist2, unew, pnew, Lnew, inside, aux, parts, out;
+  DevBuf *all[17] = {&u, &p, &L, &start, &ever, &last, &rej, &tl, &tr, &dist2, &unew, &pnew, &Lnew, &inside, &aux, &parts, &out};
+};
+
+struct mlf_walkers : RegionCopies {
+  int P = 0, nsteps = 0, nparams = 0;
+  DevBuf allu, allL, generation, currentt, currentv, left, right, sl, sr, currentp;
+  DevBuf unew, movable, acceptable, success, pnew, Lnew, dist2;
+  DevBuf gmax, flags, snap, idx, rows, vals, vidx, vrows, unif, blk, compact, pc, Lc, rec, aux;
+  DevBuf ring, partials;
   bool proposed = false, compacted = false;
   std::vector<uint8_t> host_snap;
   // one captured launch sequence (replay): the executable graph and everything its captured arguments depend on
@@ -106,7 +124,7 @@ WalkState state_of(const mlf_walkers *w) {
   return s;
 }
 
-WalkLayer layer_of(const mlf_walkers *w) {
+WalkLayer layer_of(const RegionCopies *w) {
   WalkLayer l{};
   l.kind = w->layer_kind;
   l.ctr = w->lay_ctr.as<double>();
@@ -139,7 +157,7 @@ struct StepEval {
   const double *aux = nullptr;
   double sigma = 0.0;
 
-  int check(const mlf_walkers *w) const {
+  int check(const RegionCopies *w) const {
     if (model) {
       if (usermodel_dim(model) != w->d) return fail_arg(MLF_E_BADARG, "user model and walkers differ in dimensionality");
       return 0;
@@ -182,7 +200,7 @@ int finish_common(mlf_walkers *w, double Lmin, const StepEval *ev, int64_t ringi
   return 0;
 }
 
-WalkDirData dir_data(const mlf_walkers *w) {
+WalkDirData dir_data(const RegionCopies *w) {
   WalkDirData dd{};
   dd.axes = w->axes.as<double>();
   dd.live = w->live.as<double>();
@@ -191,7 +209,7 @@ WalkDirData dir_data(const mlf_walkers *w) {
   return dd;
 }
 
-int check_direction_data(const mlf_walkers *w, int kind) {
+int check_direction_data(const RegionCopies *w, int kind) {
   const bool need_axes = kind == DIR_REGION_ORIENTED || kind == DIR_REGION_RANDOM || kind == DIR_MIXTURE;
   const bool need_live = kind == DIR_DIFFERENTIAL || kind == DIR_MIXTURE;
   if ((need_axes && !w->have_axes) || (need_live && !w->have_live) || (kind == DIR_CUBE_ORIENTED_SCALED && !w->have_std))
@@ -303,6 +321,149 @@ int replay(mlf_walkers::GraphCache &c, std::vector<unsigned long long> key, hipS
   return 0;
 }
 
+// ---- the setters of the region copies: one body for both handles
+int set_direction_data(RegionCopies *w, const double *axes, const double *live, size_t nlive, const double *std) {
+  hipStream_t s = ctx_stream();
+  const size_t d = (size_t)w->d;
+  if (axes) {
+    if (int rc = upload(w->axes, axes, d * d * 8, s)) return rc;
+    w->have_axes = true;
+  }
+  if (live) {
+    if (nlive < 2) return fail_arg(MLF_E_BADARG, "differential directions need at least two live points");
+    if (int rc = upload(w->live, live, nlive * d * 8, s)) return rc;
+    w->nlive = (int)nlive;
+    w->have_live = true;
+  }
+  if (std) {
+    if (int rc = upload(w->std, std, d * 8, s)) return rc;
+    w->have_std = true;
+  }
+  CK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int set_layer(RegionCopies *w, int kind, const double *ctr, const double *mat, const double *wrap, double maxradiussq) {
+  if (kind < 0) {
+    w->layer_kind = -1;
+    return 0;
+  }
+  if (kind > 1 || !ctr || !mat) return fail_arg(MLF_E_BADARG, "layer kind must be 0 (affine) or 1 (scaling)");
+  hipStream_t s = ctx_stream();
+  const size_t d = (size_t)w->d;
+  if (int rc = upload(w->lay_ctr, ctr, d * 8, s)) return rc;
+  if (int rc = upload(w->lay_mat, mat, (kind == 0 ? d * d : d) * 8, s)) return rc;
+  w->layer_wrap = wrap != nullptr;
+  if (wrap)
+    if (int rc = upload(w->lay_wrap, wrap, d * 8, s)) return rc;
+  CK(hipStreamSynchronize(s));
+  w->layer_kind = kind;
+  w->r2 = maxradiussq;
+  return 0;
+}
+
+int set_live(RegionCopies *w, const double *us, const double *Ls, size_t nlive) {
+  if (nlive < 2) return fail_arg(MLF_E_BADARG, "at least two live points are needed");
+  hipStream_t s = ctx_stream();
+  if (int rc = upload(w->live, us, nlive * (size_t)w->d * 8, s)) return rc;
+  if (int rc = upload(w->liveL, Ls, nlive * 8, s)) return rc;
+  w->nlive = (int)nlive;
+  w->have_live = true;
+  w->have_liveL = true;
+  return 0;
+}
+
+// ---- mlf_rwalk: one refill = start rows, nsteps moves of every walker, diagnostics and counts, one synchronisation
+struct RwalkOut {
+  double *u, *p, *L;
+  int64_t *start;
+  uint8_t *ever, *last;
+  double *tleft, *tright, *counts;
+};
+
+int rwalk_refill(mlf_rwalk *w, double Lmin, int dirkind, double dirscale, uint64_t seed, uint64_t offset, const StepEval &ev,
+                 int form, const RwalkOut &o, uint64_t *next_offset) {
+  if (!w || !o.u || !o.p || !o.L || !o.start || !o.ever || !o.last || !o.counts || !next_offset)
+    return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w->have_liveL) return fail_arg(MLF_E_STATE, "mlf_rwalk_set_live not called");
+  if (dirkind < 0 || dirkind > DIR_MIXTURE) return fail_arg(MLF_E_BADARG, "unknown direction kind");
+  if (form < 0 || form > 1) return fail_arg(MLF_E_BADARG, "form must be 0 (chosen by shape) or 1 (chain form)");
+  if (int rc = ev.check(w)) return rc;
+  if (int rc = check_direction_data(w, dirkind)) return rc;
+  hipStream_t s = ctx_stream();
+  const size_t P = (size_t)w->P, d = (size_t)w->d;
+  if (ev.aux)
+    if (int rc = upload(w->aux, ev.aux, d * 8, s)) return rc;
+  RwalkArgs a{};
+  a.w.P = w->P;
+  a.w.nsteps = w->nsteps;
+  a.w.d = w->d;
+  a.w.u = w->u.as<double>();
+  a.w.p = w->p.as<double>();
+  a.w.L = w->L.as<double>();
+  a.w.start = w->start.as<long long>();
+  a.w.ever = w->ever.as<uint8_t>();
+  a.w.last = w->last.as<uint8_t>();
+  a.w.rej = w->rej.as<int>();
+  a.w.tl = w->tl.as<double>();
+  a.w.tr = w->tr.as<double>();
+  a.w.dist2 = w->dist2.as<double>();
+  a.w.unew = w->unew.as<double>();
+  a.w.pnew = w->pnew.as<double>();
+  a.w.Lnew = w->Lnew.as<double>();
+  a.w.inside = w->inside.as<uint8_t>();
+  a.live = w->live.as<double>();
+  a.Ls = w->liveL.as<double>();
+  a.nlive = w->nlive;
+  a.dirkind = dirkind;
+  a.dirscale = dirscale;
+  a.dd = dir_data(w);
+  a.tkind = ev.tkind;
+  a.ta = ev.ta;
+  a.tb = ev.tb;
+  a.lkind = ev.lkind;
+  a.aux = w->aux.as<double>();
+  a.sigma = ev.sigma;
+  a.ly = layer_of(w);
+  a.Lmin = Lmin;
+  a.seed = seed;
+  a.offset = offset;
+  a.parts = w->parts.as<double>();
+  a.out = w->out.as<double>();
+  const bool fused = !ev.model && form == 0 && rwalk_fused_covers(w->d, w->layer_kind);
+  if (fused) {
+    launch_rwalk_fused(a, s);
+  } else {   // all nsteps triples queued back to back, no synchronisation in between
+    launch_rwalk_start(a, s);
+    for (int step = 0; step < w->nsteps; ++step) {
+      launch_rwalk_propose(a, step, s);
+      if (ev.model) {
+        if (int rc = usermodel_rows(ev.model, a.w.unew, w->P, a.w.inside, a.w.pnew, a.w.Lnew, s)) return rc;
+      } else {
+        launch_loglike(ev.lkind, a.w.pnew, w->d, w->P, a.aux, ev.sigma, a.w.Lnew, s);
+      }
+      launch_rwalk_accept(a, s);
+    }
+  }
+  launch_rwalk_finish(a, s);
+  CK(hipGetLastError());
+  if (int rc = download(o.u, w->u, P * d * 8, s)) return rc;
+  if (int rc = download(o.p, w->p, P * d * 8, s)) return rc;
+  if (int rc = download(o.L, w->L, P * 8, s)) return rc;
+  if (int rc = download(o.start, w->start, P * 8, s)) return rc;
+  if (int rc = download(o.ever, w->ever, P, s)) return rc;
+  if (int rc = download(o.last, w->last, P, s)) return rc;
+  if (o.tleft)
+    if (int rc = download(o.tleft, w->tl, P * 8, s)) return rc;
+  if (o.tright)
+    if (int rc = download(o.tright, w->tr, P * 8, s)) return rc;
+  if (int rc = download(o.counts, w->out, kRwalkOut * sizeof(double), s)) return rc;
+  CK(hipStreamSynchronize(s));
+  o.counts[kRwalkOut] = fused ? 0.0 : 1.0;
+  *next_offset = offset + rwalk_philox_per_refill(w->P, w->nsteps, w->d);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -350,9 +511,9 @@ int mlf_walkers_destroy(mlf_walkers *w) {
   DevBuf *all[] = {&w->allu, &w->allL, &w->generation, &w->currentt, &w->currentv, &w->left, &w->right, &w->sl,
                    &w->sr, &w->currentp, &w->unew, &w->movable, &w->acceptable, &w->success, &w->pnew, &w->Lnew,
                    &w->dist2, &w->gmax, &w->flags, &w->snap, &w->idx, &w->rows, &w->vals, &w->vidx, &w->vrows, &w->unif, &w->blk, &w->compact,
-                   &w->pc, &w->Lc, &w->rec, &w->aux, &w->axes, &w->live, &w->std, &w->lay_ctr, &w->lay_mat,
-                   &w->lay_wrap, &w->liveL, &w->ring, &w->partials};
+                   &w->pc, &w->Lc, &w->rec, &w->aux, &w->ring, &w->partials};
   for (DevBuf *b : all) b->release();
+  w->release_copies();
   w->d_sp.release();
   for (DevBuf *b : {&w->r_ctl, &w->r_flags, &w->r_dist2, &w->r_out, &w->r_sp, &w->r_last, &w->r_parts, &w->live_stage}) b->release();
   if (w->h_live) (void)hipHostFree(w->h_live);
@@ -439,24 +600,7 @@ int mlf_walkers_brackets(mlf_walkers *w, const int64_t *idx, size_t n, double sc
 int mlf_walkers_set_direction_data(mlf_walkers *w, const double *axes, const double *live, size_t nlive,
                                    const double *std) {
   if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
-  hipStream_t s = ctx_stream();
-  const size_t d = (size_t)w->d;
-  if (axes) {
-    if (int rc = upload(w->axes, axes, d * d * 8, s)) return rc;
-    w->have_axes = true;
-  }
-  if (live) {
-    if (nlive < 2) return fail_arg(MLF_E_BADARG, "differential directions need at least two live points");
-    if (int rc = upload(w->live, live, nlive * d * 8, s)) return rc;
-    w->nlive = (int)nlive;
-    w->have_live = true;
-  }
-  if (std) {
-    if (int rc = upload(w->std, std, d * 8, s)) return rc;
-    w->have_std = true;
-  }
-  CK(hipStreamSynchronize(s));
-  return 0;
+  return set_direction_data(w, axes, live, nlive, std);
 }
 
 int mlf_walkers_brackets_philox(mlf_walkers *w, double scale, int kind, double dirscale, uint64_t seed,
@@ -473,22 +617,7 @@ int mlf_walkers_brackets_philox(mlf_walkers *w, double scale, int kind, double d
 int mlf_walkers_set_layer(mlf_walkers *w, int kind, const double *ctr, const double *mat, const double *wrap,
                           double maxradiussq) {
   if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (kind < 0) {
-    w->layer_kind = -1;
-    return 0;
-  }
-  if (kind > 1 || !ctr || !mat) return fail_arg(MLF_E_BADARG, "layer kind must be 0 (affine) or 1 (scaling)");
-  hipStream_t s = ctx_stream();
-  const size_t d = (size_t)w->d;
-  if (int rc = upload(w->lay_ctr, ctr, d * 8, s)) return rc;
-  if (int rc = upload(w->lay_mat, mat, (kind == 0 ? d * d : d) * 8, s)) return rc;
-  w->layer_wrap = wrap != nullptr;
-  if (wrap)
-    if (int rc = upload(w->lay_wrap, wrap, d * 8, s)) return rc;
-  CK(hipStreamSynchronize(s));
-  w->layer_kind = kind;
-  w->r2 = maxradiussq;
-  return 0;
+  return set_layer(w, kind, ctr, mat, wrap, maxradiussq);
 }
 
 int mlf_walkers_propose(mlf_walkers *w, const double *unif, uint64_t seed, uint64_t offset, double *unew_out,
@@ -554,14 +683,7 @@ int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, i
 
 int mlf_walkers_set_live(mlf_walkers *w, const double *us, const double *Ls, size_t nlive) {
   if (!w || !us || !Ls) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (nlive < 2) return fail_arg(MLF_E_BADARG, "at least two live points are needed");
-  hipStream_t s = ctx_stream();
-  if (int rc = upload(w->live, us, nlive * (size_t)w->d * 8, s)) return rc;
-  if (int rc = upload(w->liveL, Ls, nlive * 8, s)) return rc;
-  w->nlive = (int)nlive;
-  w->have_live = true;
-  w->have_liveL = true;
-  return 0;
+  return set_live(w, us, Ls, nlive);
 }
 
 int mlf_walkers_update_live(mlf_walkers *w, const int64_t *rows, size_t count, const double *us_rows, const double *Ls_rows) {
@@ -738,6 +860,79 @@ int mlf_walkers_export(mlf_walkers *w, double *allu, double *allL, int64_t *gene
   if (sr) CK(hipMemcpyAsync(sr, w->sr.p, P, hipMemcpyDeviceToHost, s));
   CK(hipStreamSynchronize(s));
   return 0;
+}
+
+// ---- PopulationRandomWalkSampler's refill -----------------------------------------------------------
+int mlf_rwalk_create(mlf_rwalk **out, size_t popsize, size_t nsteps, size_t d) {
+  if (!out) return fail_arg(MLF_E_BADARG, "null pointer");
+  *out = nullptr;
+  if (popsize == 0 || nsteps == 0 || d == 0) return fail_arg(MLF_E_BADARG, "mlf_rwalk_create: popsize, nsteps, d must be positive");
+  if (d > 128) return fail_arg(MLF_E_DIM, "the random-walk population (one wave per walker, lane = coordinate pair) covers up to 128 dimensions");
+  // walker * nsteps + step and walker * d + coordinate are ints on the device
+  if (popsize > (1u << 24) || nsteps > 65535 || popsize * nsteps > 0x7fffffffull || popsize * d > 0x7fffffffull)
+    return fail_arg(MLF_E_BADARG, "mlf_rwalk_create: population too large");
+  if (int rc = ensure_ctx()) return rc;
+  mlf_rwalk *w = new mlf_rwalk();
+  w->P = (int)popsize;
+  w->nsteps = (int)nsteps;
+  w->d = (int)d;
+  const size_t P = popsize;
+  struct {
+    DevBuf *b;
+    size_t bytes;
+  } plan[] = {{&w->u, P * d * 8},    {&w->p, P * d * 8},    {&w->L, P * 8},      {&w->start, P * 8}, {&w->ever, P},
+              {&w->last, P},         {&w->rej, P * 4},      {&w->tl, P * 8},     {&w->tr, P * 8},    {&w->dist2, P * 8},
+              {&w->unew, P * d * 8}, {&w->pnew, P * d * 8}, {&w->Lnew, P * 8},   {&w->inside, P},    {&w->aux, d * 8},
+              {&w->parts, ((P + 1023) / 1024) * kRwalkOut * 8},                  {&w->out, kRwalkOut * 8}};
+  for (auto &e : plan) {
+    hipError_t err = e.b->reserve(e.bytes);
+    if (err != hipSuccess) {
+      mlf_rwalk_destroy(w);
+      return fail_hip(err, "device allocation for the random-walk population", "mlf_walk_api.hip", __LINE__);
+    }
+  }
+  *out = w;
+  return 0;
+}
+
+int mlf_rwalk_destroy(mlf_rwalk *w) {
+  if (!w) return 0;
+  for (DevBuf *b : w->all) b->release();
+  w->release_copies();
+  delete w;
+  return 0;
+}
+
+int mlf_rwalk_set_layer(mlf_rwalk *w, int kind, const double *ctr, const double *mat, const double *wrap, double maxradiussq) {
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
+  return set_layer(w, kind, ctr, mat, wrap, maxradiussq);
+}
+
+int mlf_rwalk_set_direction_data(mlf_rwalk *w, const double *axes, const double *live, size_t nlive, const double *std) {
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
+  return set_direction_data(w, axes, live, nlive, std);
+}
+
+int mlf_rwalk_set_live(mlf_rwalk *w, const double *us, const double *Ls, size_t nlive) {
+  if (!w || !us || !Ls) return fail_arg(MLF_E_BADARG, "null pointer");
+  return set_live(w, us, Ls, nlive);
+}
+
+int mlf_rwalk_refill_dev(mlf_rwalk *w, double Lmin, int dirkind, double dirscale, uint64_t seed, uint64_t offset, int tkind,
+                         double ta, double tb, int lkind, const double *aux, double sigma, int form, double *out_u,
+                         double *out_p, double *out_L, int64_t *out_start, uint8_t *out_ever, uint8_t *out_last,
+                         double *out_tleft, double *out_tright, double *counts, uint64_t *next_offset) {
+  return rwalk_refill(w, Lmin, dirkind, dirscale, seed, offset, StepEval{nullptr, tkind, ta, tb, lkind, aux, sigma}, form,
+                      RwalkOut{out_u, out_p, out_L, out_start, out_ever, out_last, out_tleft, out_tright, counts}, next_offset);
+}
+
+int mlf_rwalk_refill_user(mlf_rwalk *w, double Lmin, int dirkind, double dirscale, uint64_t seed, uint64_t offset,
+                          mlf_usermodel *model, double *out_u, double *out_p, double *out_L, int64_t *out_start,
+                          uint8_t *out_ever, uint8_t *out_last, double *out_tleft, double *out_tright, double *counts,
+                          uint64_t *next_offset) {
+  if (!model) return fail_arg(MLF_E_BADARG, "null pointer");
+  return rwalk_refill(w, Lmin, dirkind, dirscale, seed, offset, StepEval{model}, 1,
+                      RwalkOut{out_u, out_p, out_L, out_start, out_ever, out_last, out_tleft, out_tright, counts}, next_offset);
 }
 
 // ------------------------------------------------------------------ stateless forms ------------

@@ -343,7 +343,9 @@ class StaticNestedSampler(object):
                 ph["stepsampler_s"] += tick() - t0
                 ph["stepsampler_calls"] += 1
                 self.ncall += nc
-                if newu is not None:
+                # (a batched population sampler hands out points prepared under an earlier threshold: the driver discards
+                # those that no longer lie above the current one, integrator.py:1941-1950)
+                if newu is not None and newl > Lmin:
                     break
             while self.stepsampler is None:
                 # the threshold only rises: walk the batch once, like the driver's index `ib` (:1942-1950)

@@ -21,6 +21,10 @@ proposals then make one round trip), or the device likelihoods of ``ultranest_am
 (objects with ``device_spec``), which are evaluated in place on the device, or a user model's callbacks
 (``ultranest_amd.devicemodel.DeviceModel``: HIP device functions compiled at run time), which run per step on the
 device (no graph replay, no multi-round kernel).
+
+``PopulationRandomWalkSampler`` takes the same ``device_rng=``: with a direction generator that has a ``device_kind`` and a
+resident model (device likelihoods, or a user model) a whole refill -- start rows, ``nsteps`` moves of every walker,
+diagnostics, counts -- is one device call (csrc/mlf_rwalk.hip); otherwise its host loop runs as before.
 """
 import ctypes
 
@@ -107,6 +111,48 @@ class GenericPopulationSampler(object):
         pass
 
 
+def _resident_model(transform, loglike):
+    """``(tspec, lspec, user)`` of a callback pair: the built-in ``device_spec`` tuples (None unless BOTH callbacks carry one)
+    and the user model's ``(model, with_transform)`` (``devicemodel.device_route``; None otherwise).  A user model paired
+    with a foreign callback is neither: host callbacks."""
+    tspec, lspec = getattr(transform, "device_spec", None), getattr(loglike, "device_spec", None)
+    user = devicemodel.device_route(transform, loglike)
+    if user is not None or devicemodel.is_user_spec(tspec) or devicemodel.is_user_spec(lspec) or tspec is None or lspec is None:
+        tspec = lspec = None    # never unpacked as (kind, a, b)
+    return tspec, lspec, user
+
+
+def _sync_region_copies(w, seen, region, ndim, device_kind, skip_live=False):
+    """Device copies of what the region contributes to a population handle `w` (``set_layer`` / ``set_direction_data``):
+    the layer of the move diagnostics whenever region, layer or radius changed, and, for a Philox direction generator of
+    kind `device_kind` (None: directions come from the host), the data that kind reads.  `seen` remembers what was uploaded."""
+    layer = region.transformLayer
+    r2 = region.maxradiussq
+    if seen["region"] is not region or seen["layer"] is not layer or seen["r2"] != r2:
+        try:
+            kind, ctr, mat = layer.device_params(ndim)
+            wrap = layer.wrap_shift_vector(ndim)
+        except AttributeError:      # a foreign layer object: whiten through its numpy attributes
+            kind, ctr, mat, wrap = 0, np.broadcast_to(layer.ctr, (ndim,)), layer.T, None
+        if r2 is None:
+            w.set_layer(-1, None, None, None, 1.0)
+        else:
+            w.set_layer(kind, ctr, mat, wrap, r2)
+        seen.update(layer=layer, r2=r2)
+    kind = device_kind
+    if kind is not None:
+        fresh = seen["region"] is not region
+        if kind in (3, 4, 6) and fresh:
+            w.set_direction_data(axes=region.transformLayer.axes)
+        if kind == 1 and (fresh or seen["calls"] % 32 == 0):
+            w.set_direction_data(std=region.u.std(axis=0))
+        # (the whole-step paths keep live points and their likelihoods together: set_live)
+        if kind in (5, 6) and not skip_live and (fresh or region.u.size <= 32768 or seen["calls"] % 32 == 0):
+            w.set_direction_data(live=region.u)
+    seen["region"] = region
+    seen["calls"] += 1
+
+
 class _BatchedPopulationSampler(GenericPopulationSampler):
     """The two samplers of the reference that advance the WHOLE population by `nsteps` moves in one call and then hand the
     walkers out one per call (reference popstepsampler.py:192-358 and :746-1001).  The moves themselves are the vectorised
@@ -134,7 +180,7 @@ class PopulationRandomWalkSampler(_BatchedPopulationSampler):
     """Vectorized Gaussian random walk (reference popstepsampler.py:192-358; same constructor and ``__next__`` contract)."""
 
     def __init__(self, popsize, nsteps, generate_direction, scale, scale_adapt_factor=0.9, scale_min=1e-20, scale_max=20,
-                 log=False, logfile=None):
+                 log=False, logfile=None, device_rng=None):
         assert scale_adapt_factor <= 1
         self.popsize, self.nsteps, self.generate_direction = popsize, nsteps, generate_direction
         self.scale, self.scale_adapt_factor, self.scale_min, self.scale_max = scale, scale_adapt_factor, scale_min, scale_max
@@ -142,12 +188,40 @@ class PopulationRandomWalkSampler(_BatchedPopulationSampler):
         self.log, self.logfile, self.logstat = log, logfile, []
         self.logstat_labels = ['accept_rate', 'efficiency', 'scale', 'far_enough', 'mean_rel_jump']
         self.prepared_samples = []
+        if device_rng is not None and not isinstance(device_rng, DeviceRNG):
+            raise TypeError("device_rng must be an ultranest_amd.regions.DeviceRNG")
+        self.device_rng = device_rng
+        self.force_chain_form = False     # tests: the general form (three launches per step) where one launch would do
+        self._rwalk = None
+        self._seen = dict(region=None, layer=None, r2=None, calls=0)
 
     def __str__(self):
         return 'PopulationRandomWalkSampler(popsize=%d, nsteps=%d, generate_direction=%s, scale=%.g)' % (
             self.popsize, self.nsteps, self.generate_direction, self.scale)
 
+    def _device_route(self, transform, loglike, ndim=None):
+        """What a refill runs on: None = the host loop; else ``(device_kind, tspec, lspec, user)`` of a whole refill on the
+        device -- it takes ``device_rng``, a direction generator with a ``device_kind``, a resident model (both callbacks
+        with a built-in ``device_spec``, or a user model as ``devicemodel.device_route`` decides it) and at most 128
+        dimensions (``mlf_rwalk``: one wave per walker, lane = coordinate pair)."""
+        if self.device_rng is None or (ndim is not None and ndim > 128):
+            return None
+        device_kind = getattr(self.generate_direction, "device_kind", None)
+        if device_kind is None:
+            return None
+        tspec, lspec, user = _resident_model(transform, loglike)
+        if user is None and tspec is None:
+            return None
+        return device_kind, tspec, lspec, user
+
+    def region_changed(self, Ls, region):
+        """Nothing of the region is cached on the host; the device copies are refreshed at the next refill."""
+        self._seen["region"] = None
+
     def _refill(self, region, Lmin, us, Ls, transform, loglike):
+        route = self._device_route(transform, loglike, us.shape[1])
+        if route is not None:
+            return self._refill_on_device(region, Lmin, us, Ls, *route)
         import scipy.stats
         nlive = len(us)
         nmoves = self.nsteps * self.popsize
@@ -175,10 +249,44 @@ class PopulationRandomWalkSampler(_BatchedPopulationSampler):
         # (the reference diagnoses the walkers that accepted their LAST move: reference :334)
         far_enough, (moved, radius) = diagnose_move_distances(region, us[start[accepted], :], allu[accepted, :])
         self.prepared_samples = list(zip(allu, allp, allL))
+        return self._after_refill(rejects_before, accepted.mean(), np.mean(far_enough),
+                                  np.exp(np.mean(np.log(moved / radius + 1e-10))))
+
+    def _refill_on_device(self, region, Lmin, us, Ls, device_kind, tspec, lspec, user):
+        """The whole refill in one device call (``mlf_rwalk_refill_dev`` / ``_refill_user``): start rows, directions and
+        truncated-normal steps come from Philox, nothing but the live points is uploaded, and per-walker results with
+        the counts come back; statistics, log line and scale adaptation are the host path's."""
+        nlive, ndim = us.shape
+        if self._rwalk is None or self._rwalk.shape != (self.popsize, self.nsteps, ndim):
+            self._rwalk = _RandomWalkers(self.popsize, self.nsteps, ndim)
+            self._seen.update(region=None, layer=None, r2=None)
+        w = self._rwalk
+        _sync_region_copies(w, self._seen, region, ndim, device_kind, skip_live=True)
+        w.set_live(us, Ls)
+        rejects_before = self.nrejects
+        out = w.refill(Lmin, device_kind, self.scale, self.device_rng, tspec, lspec, user, force_chain=self.force_chain_form)
+        self.last_refill = out
+        self.nrejects += out["nrejects"]
+        assert out["nnever"] == 0, 'some walkers never moved! Double nsteps of PopulationRandomWalkSampler.'
+        self.prepared_samples = list(zip(out["u"], out["p"], out["L"]))
+        nlast = out["nlast"]
+        if region.maxradiussq is None:
+            far = jump = 0
+        elif nlast == 0:    # (nobody accepted the last move: the host path's means of nothing)
+            far = jump = np.nan
+        else:
+            far, jump = out["nfar"] / nlast, np.exp(out["sumlog"] / nlast)
+        return self._after_refill(rejects_before, nlast / self.popsize, far, jump)
+
+    def _after_refill(self, rejects_before, last_accept_rate, far_enough_fraction, mean_rel_jump):
+        """Step statistics, log line and scale adaptation after a refill that added its rejects to ``self.nrejects``
+        (reference :336-353); returns the refill's number of likelihood evaluations."""
+        nmoves = self.nsteps * self.popsize
+        target_rejects = nmoves * (1 - 0.234)              # the acceptance rate the scale is steered to
         expected = rejects_before + target_rejects
         # (efficiency in the reference's own arithmetic, :339: the count before this call is recovered from `expected`)
-        self.logstat.append([accepted.mean(), 1 - (self.nrejects - (expected - target_rejects)) / nmoves,
-                             self.scale, self.nsteps, np.mean(far_enough), np.exp(np.mean(np.log(moved / radius + 1e-10)))])
+        self.logstat.append([last_accept_rate, 1 - (self.nrejects - (expected - target_rejects)) / nmoves,
+                             self.scale, self.nsteps, far_enough_fraction, mean_rel_jump])
         if self.logfile:    # (the reference's own format string takes five of the six columns)
             row = self.logstat[-1]
             self.logfile.write("rescale\t%.4f\t%.4f\t%g\t%.4f%g\n" % (row[0], row[1], row[2], row[4], row[5]))
@@ -258,6 +366,61 @@ class PopulationSimpleSliceSampler(_BatchedPopulationSampler):
         else:
             self.scale *= self.scale_adapt_factor
         return nc
+
+
+class _RandomWalkers(object):
+    """Owner of one ``mlf_rwalk`` handle (include/mlfriends_hip.h): the population of PopulationRandomWalkSampler."""
+
+    def __init__(self, popsize, nsteps, ndim):
+        self.shape = (int(popsize), int(nsteps), int(ndim))
+        self.popsize, self.nsteps, self.ndim = self.shape
+        handle = ctypes.c_void_p()
+        check(_lib.lib().mlf_rwalk_create(ctypes.byref(handle), self.popsize, self.nsteps, self.ndim))
+        self._h = handle
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                _lib.lib().mlf_rwalk_destroy(h)
+            except Exception:
+                pass
+
+    def set_layer(self, kind, ctr, mat, wrap, maxradiussq):
+        check(_lib.lib().mlf_rwalk_set_layer(self._h, int(kind), ptr(None if ctr is None else f64(ctr)),
+                                             ptr(None if mat is None else f64(mat)),
+                                             ptr(None if wrap is None else f64(wrap)), float(maxradiussq)))
+
+    def set_direction_data(self, axes=None, live=None, std=None):
+        live = None if live is None else f64(live)
+        check(_lib.lib().mlf_rwalk_set_direction_data(
+            self._h, ptr(None if axes is None else f64(axes)), ptr(live), 0 if live is None else len(live),
+            ptr(None if std is None else f64(std))))
+
+    def set_live(self, us, Ls):
+        us, Ls = f64(us), f64(Ls)
+        check(_lib.lib().mlf_rwalk_set_live(self._h, ptr(us), ptr(Ls), len(Ls)))
+
+    def refill(self, Lmin, kind, dirscale, rng, tspec=None, lspec=None, user=None, force_chain=False):
+        """One refill; advances rng.offset.  dict of per-walker arrays u, p, L, start, ever, last, tleft, tright (the cube
+        limits of the last step), the counts nrejects, nlast, nfar, sumlog, nnever and chain_form (which form ran)."""
+        P, d = self.popsize, self.ndim
+        out = dict(u=np.empty((P, d)), p=np.empty((P, d)), L=np.empty(P), start=np.empty(P, dtype=np.int64),
+                   ever=np.empty(P, dtype=np.uint8), last=np.empty(P, dtype=np.uint8), tleft=np.empty(P), tright=np.empty(P))
+        counts = np.empty(6)
+        nxt = ctypes.c_uint64(0)
+        outs = tuple(ptr(out[k]) for k in ("u", "p", "L", "start", "ever", "last", "tleft", "tright")) + (ptr(counts), ctypes.byref(nxt))
+        head = (self._h, float(Lmin), int(kind), float(dirscale), ctypes.c_uint64(rng.seed), ctypes.c_uint64(rng.offset))
+        if user is not None:
+            model, with_transform = user
+            check(_lib.lib().mlf_rwalk_refill_user(*head, model.handle(with_transform), *outs))
+        else:
+            check(_lib.lib().mlf_rwalk_refill_dev(*head, *_Walkers._builtin_args(tspec, lspec), 1 if force_chain else 0, *outs))
+        rng.offset = nxt.value
+        out["ever"], out["last"] = out["ever"].view(np.bool_), out["last"].view(np.bool_)
+        out.update(nrejects=int(counts[0]), nlast=int(counts[1]), nfar=counts[2], sumlog=counts[3], nnever=int(counts[4]),
+                   chain_form=bool(counts[5]))
+        return out
 
 
 class _Walkers(object):
@@ -502,33 +665,8 @@ class PopulationSliceSampler(GenericPopulationSampler):
 
     # ---- device copies of what the region contributes -----------------------------------------
     def _sync_region(self, region, skip_live=False):
-        w, seen = self._walkers, self._seen
-        layer = region.transformLayer
-        r2 = region.maxradiussq
-        if seen["region"] is not region or seen["layer"] is not layer or seen["r2"] != r2:
-            ndim = self._walkers.ndim
-            try:
-                kind, ctr, mat = layer.device_params(ndim)
-                wrap = layer.wrap_shift_vector(ndim)
-            except AttributeError:      # a foreign layer object: whiten through its numpy attributes
-                kind, ctr, mat, wrap = 0, np.broadcast_to(layer.ctr, (ndim,)), layer.T, None
-            if r2 is None:
-                w.set_layer(-1, None, None, None, 1.0)
-            else:
-                w.set_layer(kind, ctr, mat, wrap, r2)
-            seen.update(layer=layer, r2=r2)
-        kind = getattr(self.generate_direction, "device_kind", None)
-        if self.device_rng is not None and kind is not None:
-            fresh = seen["region"] is not region
-            if kind in (3, 4, 6) and fresh:
-                w.set_direction_data(axes=region.transformLayer.axes)
-            if kind == 1 and (fresh or seen["calls"] % 32 == 0):
-                w.set_direction_data(std=region.u.std(axis=0))
-            # (the whole-step path keeps live points and their likelihoods together: set_live)
-            if kind in (5, 6) and not skip_live and (fresh or region.u.size <= 32768 or seen["calls"] % 32 == 0):
-                w.set_direction_data(live=region.u)
-        seen["region"] = region
-        seen["calls"] += 1
+        kind = getattr(self.generate_direction, "device_kind", None) if self.device_rng is not None else None
+        _sync_region_copies(self._walkers, self._seen, region, self._walkers.ndim, kind, skip_live=skip_live)
 
     # ---- one sampler step ------------------------------------------------------------------------
     def __next__(self, region, Lmin, us, Ls, transform, loglike, ndraw=10, plot=False, tregion=None, log=False):
@@ -538,10 +676,7 @@ class PopulationSliceSampler(GenericPopulationSampler):
         if self._walkers is None:
             self._walkers = _Walkers(self.popsize, self.nsteps, ndim)
         w = self._walkers
-        tspec, lspec = getattr(transform, "device_spec", None), getattr(loglike, "device_spec", None)
-        user = devicemodel.device_route(transform, loglike)     # (model, with_transform) of a user model, or None
-        if user is not None or devicemodel.is_user_spec(tspec) or devicemodel.is_user_spec(lspec):
-            tspec = lspec = None   # never unpacked as (kind, a, b); a user model paired with another callback: host callbacks
+        tspec, lspec, user = _resident_model(transform, loglike)     # user: (model, with_transform) of a user model, or None
         device_kind = getattr(self.generate_direction, "device_kind", None)
         whole_step = self.device_rng is not None and device_kind is not None and (
             user is not None or (tspec is not None and lspec is not None))
