@@ -463,6 +463,52 @@ int mlf_rwalk_refill_dev(mlf_rwalk *w, double Lmin, int dirkind, double dirscale
                          uint8_t *out_last, double *out_tleft, double *out_tright, double *counts,
                          uint64_t *next_offset);
 
+/* Whole-population simple slice sampling = one refill of PopulationSimpleSliceSampler (popstepsampler.py:907-1002,
+ * stepfuncs.pyx:537-630) on the device: popsize points, each nsteps slice steps without stepping out; popsize workers
+ * (likelihood slots) per iteration, the workers of finished points dealt round-robin to the unfinished ones; at most max_it
+ * iterations per step.  The handle owns the state and the device copies its setters upload (set_layer /
+ * set_direction_data / set_live: as the mlf_walkers setters of the same names).
+ *   refill_dev   built-in transform (tkind, ta, tb) and likelihood (lkind, aux, sigma), as mlf_walkers_finish_dev.  Point i
+ *                starts at live row below(word, nlive) with L = Ls[row] and a NaN p row.  Step s: v = the direction of kind
+ *                dirkind (0-6) and length dirscale[s]; the slice = the line's part inside the unit cube (limit 0) or that
+ *                clipped to [-1, 1] (limit 1).  Iteration: worker j serves point k(j) (the first iteration: j; later the
+ *                unfinished points in ascending order, zlist[j % nz]), draws t = lo_k + (hi_k - lo_k) q_j and evaluates u_k +
+ *                t v_k (every worker; no cube test).  The update visits the workers in worker order: t outside the point's
+ *                current [lo, hi]: skipped, and counted as discarded if L > Lmin; 0 < t < hi: hi = t / shrink; 0 > t > lo: lo
+ *                = t / shrink; the first worker inside with L > Lmin becomes the point's successor, later ones still shrink.
+ *                A point without a successor after max_it iterations keeps its state.
+ *                Outputs, one row / entry per point: out_u, out_p (NaN for a point that never moved), out_L, out_start (live
+ *                row), out_tleft / out_tright (may be NULL: the slice after the last step), out_taken / out_taken_it (may be
+ *                NULL: worker and iteration of the last step's successor, -1 without one).  out_iters (nsteps): iterations of
+ *                every step.  out_widths (nsteps x popsize): tright - tleft of every point after every step (the host takes
+ *                the medians).  counts (5 doubles): discarded proposals; iterations in all (likelihood evaluations =
+ *                popsize times this); moves farther than the MLFriends radius and the sum of log(distance / radius + 1e-10)
+ *                over ALL points, start row -> final point through the layer (0 without a layer); points with a non-finite
+ *                p row.
+ *                Philox: every draw is a function of (seed, offset, point or worker, step, iteration) only.  Directions:
+ *                stream 2, block group point * nsteps + step of (d + 1) / 2 + 2 blocks.  Stream 8: block offset + i, word 0 =
+ *                start row of point i; block offset + popsize + (step * max_it + it) * popsize + j, words 0, 1 = the uniform
+ *                of worker j.  *next_offset = offset + max(popsize * nsteps * ((d + 1) / 2 + 2), popsize * (1 + nsteps *
+ *                max_it)).
+ *                The iteration count is known on the device only: the host queues slots (propose, evaluation, update,
+ *                deal), each of which reads from a control block what it serves, and polls that block once per batch.
+ *                slots_per_poll: the batch size, 0 = the library's policy.  Results do not depend on it.
+ *   refill_user  the same with a user model's kernel as the evaluation. */
+typedef struct mlf_sslice mlf_sslice;
+int mlf_sslice_create(mlf_sslice **out, size_t popsize, size_t nsteps, size_t d, size_t max_it);
+int mlf_sslice_destroy(mlf_sslice *w);
+int mlf_sslice_set_layer(mlf_sslice *w, int kind, const double *ctr, const double *mat, const double *wrap,
+                         double maxradiussq);
+int mlf_sslice_set_direction_data(mlf_sslice *w, const double *axes, const double *live, size_t nlive,
+                                  const double *std);
+int mlf_sslice_set_live(mlf_sslice *w, const double *us, const double *Ls, size_t nlive);
+int mlf_sslice_refill_dev(mlf_sslice *w, double Lmin, int dirkind, const double *dirscale, int limit, double shrink,
+                          uint64_t seed, uint64_t offset, int slots_per_poll, int tkind, double ta, double tb, int lkind,
+                          const double *aux, double sigma, double *out_u, double *out_p, double *out_L,
+                          int64_t *out_start, double *out_tleft, double *out_tright, int32_t *out_taken,
+                          int32_t *out_taken_it, int32_t *out_iters, double *out_widths, double *counts,
+                          uint64_t *next_offset);
+
 /* ---- integrator bookkeeping on the host (no GPU involved) -----------------
  * MultiCounter.passing_node of ultranest/netiter.py:721-855 for (nbootstraps + 1) counters, with the
  * insertion-order U test of ultranest/ordertest.py.  member: [ncounters][nroots] uint8, row 0 all
@@ -557,6 +603,11 @@ int mlf_rwalk_refill_user(mlf_rwalk *w, double Lmin, int dirkind, double dirscal
                           mlf_usermodel *model, double *out_u, double *out_p, double *out_L, int64_t *out_start,
                           uint8_t *out_ever, uint8_t *out_last, double *out_tleft, double *out_tright, double *counts,
                           uint64_t *next_offset);
+int mlf_sslice_refill_user(mlf_sslice *w, double Lmin, int dirkind, const double *dirscale, int limit, double shrink,
+                           uint64_t seed, uint64_t offset, int slots_per_poll, mlf_usermodel *model, double *out_u,
+                           double *out_p, double *out_L, int64_t *out_start, double *out_tleft, double *out_tright,
+                           int32_t *out_taken, int32_t *out_taken_it, int32_t *out_iters, double *out_widths,
+                           double *counts, uint64_t *next_offset);
 
 /* ---- bench / profiling helpers ---------------------------------------------------------- */
 /* Runs the neighbour-scan kernel `reps` times on device data and returns the mean kernel time

@@ -147,6 +147,16 @@ SIGNATURES = {
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mlf_rwalk_refill_user": [_vp, _dbl, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _vp,
                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mlf_sslice_create": [_vp, _sz, _sz, _sz, _sz],
+    "mlf_sslice_destroy": [_vp],
+    "mlf_sslice_set_layer": [_vp, _int, _vp, _vp, _vp, _dbl],
+    "mlf_sslice_set_direction_data": [_vp, _vp, _vp, _sz, _vp],
+    "mlf_sslice_set_live": [_vp, _vp, _vp, _sz],
+    "mlf_sslice_refill_dev": [_vp, _dbl, _int, _vp, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _int,
+                              _int, _dbl, _dbl, _int, _vp, _dbl,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mlf_sslice_refill_user": [_vp, _dbl, _int, _vp, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _int, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

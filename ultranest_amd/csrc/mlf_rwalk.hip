@@ -62,30 +62,6 @@ __device__ __noinline__ double truncnorm_draw(double a, double b, double q) {
   return fmin(fmax(t, a), b);
 }
 
-__device__ __forceinline__ double rwalk_move(double u, double v, double t) {
-  const double step = v * t;
-  return u + step;
-}
-
-__device__ __forceinline__ double rwalk_transform(int tkind, double x, double ta, double tb) {
-  double p = x;
-  if (tkind == 1) {
-    const double m = x * ta;
-    p = m + tb;
-  } else if (tkind == 2) {
-    const double m = x * ta;
-    p = m * tb;
-  }
-  return p;
-}
-
-// dw_direction reads only the dimensionality of the state it is given
-__device__ __forceinline__ WalkState direction_state(int d) {
-  WalkState ws{};
-  ws.d = d;
-  return ws;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------ chain form -----------------------------------------

@@ -2,6 +2,7 @@
 // "population step sampler"): argument checks, device buffers, staging, kernel sequencing.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -12,12 +13,13 @@
 #include "mlf_misc.hpp"
 #include "mlf_rwalk.hpp"
 #include "mlf_sample.hpp"
+#include "mlf_sslice.hpp"
 #include "mlf_walk.hpp"
 
 using namespace mlf;
 
-// Device copies of what the region and the live points contribute, with the state of their setters: shared by the two
-// population handles (mlf_walkers, mlf_rwalk)
+// Device copies of what the region and the live points contribute, with the state of their setters: shared by the three
+// population handles (mlf_walkers, mlf_rwalk, mlf_sslice)
 struct RegionCopies {
   int d = 0;
   DevBuf axes, live, std, lay_ctr, lay_mat, lay_wrap, liveL;
@@ -37,6 +39,17 @@ struct mlf_rwalk : RegionCopies {
   int P = 0, nsteps = 0;
   DevBuf u, p, L, start, ever, last, rej, tl, tr, dist2, unew, pnew, Lnew, inside, aux, parts, out;
   DevBuf *all[17] = {&u, &p, &L, &start, &ever, &last, &rej, &tl, &tr, &dist2, &unew, &pnew, &Lnew, &inside, &aux, &parts, &out};
+};
+
+// PopulationSimpleSliceSampler's population (mlf_sslice.hip): points, one iteration's proposals per worker, the control block
+struct mlf_sslice : RegionCopies {
+  int P = 0, nsteps = 0, max_it = 0;
+  DevBuf u, p, L, start, v, tl, tr, status, zlist, taken, taken_it, t, unew, pnew, Lnew, member, widths, iters, dist2, nanrow, ctl,
+      dirscale, aux, out;
+  DevBuf *all[24] = {&u, &p, &L, &start, &v, &tl, &tr, &status, &zlist, &taken, &taken_it, &t, &unew, &pnew, &Lnew, &member,
+                     &widths, &iters, &dist2, &nanrow, &ctl, &dirscale, &aux, &out};
+  SsliceCtl *h_ctl = nullptr;      // pinned: the control block as the last poll saw it
+  long long last_total_it = 0;     // iterations of the previous refill (batch policy)
 };
 
 struct mlf_walkers : RegionCopies {
@@ -461,6 +474,141 @@ int rwalk_refill(mlf_rwalk *w, double Lmin, int dirkind, double dirscale, uint64
   CK(hipStreamSynchronize(s));
   o.counts[kRwalkOut] = fused ? 0.0 : 1.0;
   *next_offset = offset + rwalk_philox_per_refill(w->P, w->nsteps, w->d);
+  return 0;
+}
+
+// ---- mlf_sslice: one refill = start rows, nsteps slice steps of the whole population, diagnostics and counts.  The host
+// queues slots (propose, evaluation, update, deal) without knowing which step they serve and reads the control block once
+// per batch (a pinned copy and one synchronisation) until `finished` is set.
+struct SsliceOut {
+  double *u, *p, *L;
+  int64_t *start;
+  double *tleft, *tright;
+  int32_t *taken, *taken_it, *iters;
+  double *widths, *counts;
+};
+
+// Batch policy (slots_per_poll == 0).  A slot past the end costs four launches that exit at their first load (the built-in
+// likelihood kernel, which has no such load, evaluates P stale rows), a poll costs one synchronisation.  The first batch is
+// the previous refill's iteration count plus an eighth (at least 2) -- refills of one run resemble each other -- or, for a
+// handle's first refill, 6 per step; each later batch is the steps still open times the mean iterations per step so far (at
+// least 2 per step, at least 4 slots).  Never more than the worst case that is left.
+long long sslice_batch(const mlf_sslice *w, const SsliceCtl &c, bool first) {
+  const long long left = (long long)(w->nsteps - c.step) * w->max_it - c.it;
+  long long n;
+  if (first) {
+    n = w->last_total_it ? w->last_total_it + std::max(2ll, w->last_total_it / 8) : (long long)w->nsteps * std::min(w->max_it, 6);
+  } else {
+    const long long per = c.step ? (c.total_it + c.step - 1) / c.step : c.total_it;
+    n = std::max(4ll, (long long)(w->nsteps - c.step) * std::min((long long)w->max_it, std::max(2ll, per)));
+  }
+  return std::min(n, left);
+}
+
+int sslice_refill(mlf_sslice *w, double Lmin, int dirkind, const double *dirscale, int limit, double shrink, uint64_t seed,
+                  uint64_t offset, const StepEval &ev, int slots_per_poll, const SsliceOut &o, uint64_t *next_offset) {
+  if (!w || !dirscale || !o.u || !o.p || !o.L || !o.start || !o.iters || !o.widths || !o.counts || !next_offset)
+    return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!w->have_liveL) return fail_arg(MLF_E_STATE, "mlf_sslice_set_live not called");
+  if (dirkind < 0 || dirkind > DIR_MIXTURE) return fail_arg(MLF_E_BADARG, "unknown direction kind");
+  if (limit < 0 || limit > 1) return fail_arg(MLF_E_BADARG, "slice limit must be 0 (unit cube) or 1 (clipped to [-1, 1])");
+  if (!(shrink >= 1.0)) return fail_arg(MLF_E_BADARG, "the shrink factor must be at least 1");
+  if (slots_per_poll < 0) return fail_arg(MLF_E_BADARG, "slots per poll must not be negative");
+  if (int rc = ev.check(w)) return rc;
+  if (int rc = check_direction_data(w, dirkind)) return rc;
+  hipStream_t s = ctx_stream();
+  const size_t P = (size_t)w->P, d = (size_t)w->d, nsteps = (size_t)w->nsteps;
+  if (ev.aux)
+    if (int rc = upload(w->aux, ev.aux, d * 8, s)) return rc;
+  if (int rc = upload(w->dirscale, dirscale, nsteps * 8, s)) return rc;
+  CK(hipMemsetAsync(w->ctl.p, 0, sizeof(SsliceCtl), s));
+  SsliceArgs a{};
+  a.w.P = w->P;
+  a.w.nsteps = w->nsteps;
+  a.w.d = w->d;
+  a.w.max_it = w->max_it;
+  a.w.u = w->u.as<double>();
+  a.w.p = w->p.as<double>();
+  a.w.L = w->L.as<double>();
+  a.w.start = w->start.as<long long>();
+  a.w.v = w->v.as<double>();
+  a.w.tl = w->tl.as<double>();
+  a.w.tr = w->tr.as<double>();
+  a.w.status = w->status.as<uint8_t>();
+  a.w.zlist = w->zlist.as<int>();
+  a.w.taken = w->taken.as<int>();
+  a.w.taken_it = w->taken_it.as<int>();
+  a.w.t = w->t.as<double>();
+  a.w.unew = w->unew.as<double>();
+  a.w.pnew = w->pnew.as<double>();
+  a.w.Lnew = w->Lnew.as<double>();
+  a.w.member = w->member.as<uint8_t>();
+  a.w.widths = w->widths.as<double>();
+  a.w.iters = w->iters.as<int>();
+  a.w.dist2 = w->dist2.as<double>();
+  a.w.nanrow = w->nanrow.as<uint8_t>();
+  a.w.ctl = w->ctl.as<SsliceCtl>();
+  a.live = w->live.as<double>();
+  a.Ls = w->liveL.as<double>();
+  a.nlive = w->nlive;
+  a.dirkind = dirkind;
+  a.dirscale = w->dirscale.as<double>();
+  a.dd = dir_data(w);
+  a.limit = limit;
+  a.shrink = shrink;
+  a.tkind = ev.tkind;
+  a.ta = ev.ta;
+  a.tb = ev.tb;
+  a.ly = layer_of(w);
+  a.Lmin = Lmin;
+  a.seed = seed;
+  a.offset = offset;
+  a.out = w->out.as<double>();
+  launch_sslice_start(a, s);
+  SsliceCtl seen{};
+  for (bool first = true; !seen.finished; first = false) {
+    const long long left = (long long)(w->nsteps - seen.step) * w->max_it - seen.it;
+    const long long nslots = slots_per_poll ? std::min((long long)slots_per_poll, left) : sslice_batch(w, seen, first);
+    for (long long slot = 0; slot < nslots; ++slot) {
+      launch_sslice_propose(a, s);
+      if (ev.model) {
+        if (int rc = usermodel_rows(ev.model, a.w.unew, w->P, a.w.member, a.w.pnew, a.w.Lnew, s)) return rc;
+      } else {
+        launch_loglike(ev.lkind, a.w.pnew, w->d, w->P, w->aux.as<double>(), ev.sigma, a.w.Lnew, s);
+      }
+      launch_sslice_update(a, s);
+      launch_sslice_deal(a, s);
+    }
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(w->h_ctl, w->ctl.p, sizeof(SsliceCtl), hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    const SsliceCtl now = *w->h_ctl;
+    // every slot of an unfinished refill is one iteration: anything else means the control block is not ours
+    if (!now.finished && now.total_it != seen.total_it + nslots) return fail_arg(MLF_E_STATE, "mlf_sslice: the control block did not advance");
+    seen = now;
+  }
+  launch_sslice_finish(a, s);
+  CK(hipGetLastError());
+  if (int rc = download(o.u, w->u, P * d * 8, s)) return rc;
+  if (int rc = download(o.p, w->p, P * d * 8, s)) return rc;
+  if (int rc = download(o.L, w->L, P * 8, s)) return rc;
+  if (int rc = download(o.start, w->start, P * 8, s)) return rc;
+  if (o.tleft)
+    if (int rc = download(o.tleft, w->tl, P * 8, s)) return rc;
+  if (o.tright)
+    if (int rc = download(o.tright, w->tr, P * 8, s)) return rc;
+  if (o.taken)
+    if (int rc = download(o.taken, w->taken, P * 4, s)) return rc;
+  if (o.taken_it)
+    if (int rc = download(o.taken_it, w->taken_it, P * 4, s)) return rc;
+  if (int rc = download(o.iters, w->iters, nsteps * 4, s)) return rc;
+  if (int rc = download(o.widths, w->widths, nsteps * P * 8, s)) return rc;
+  if (int rc = download(o.counts + 2, w->out, kSsliceOut * sizeof(double), s)) return rc;
+  CK(hipStreamSynchronize(s));
+  o.counts[0] = (double)seen.discarded;
+  o.counts[1] = (double)seen.total_it;
+  w->last_total_it = seen.total_it;
+  *next_offset = offset + sslice_philox_per_refill(w->P, w->nsteps, w->d, w->max_it);
   return 0;
 }
 
@@ -933,6 +1081,93 @@ int mlf_rwalk_refill_user(mlf_rwalk *w, double Lmin, int dirkind, double dirscal
   if (!model) return fail_arg(MLF_E_BADARG, "null pointer");
   return rwalk_refill(w, Lmin, dirkind, dirscale, seed, offset, StepEval{model}, 1,
                       RwalkOut{out_u, out_p, out_L, out_start, out_ever, out_last, out_tleft, out_tright, counts}, next_offset);
+}
+
+// ---- PopulationSimpleSliceSampler's refill ----------------------------------------------------------
+int mlf_sslice_create(mlf_sslice **out, size_t popsize, size_t nsteps, size_t d, size_t max_it) {
+  if (!out) return fail_arg(MLF_E_BADARG, "null pointer");
+  *out = nullptr;
+  if (popsize == 0 || nsteps == 0 || d == 0 || max_it == 0)
+    return fail_arg(MLF_E_BADARG, "mlf_sslice_create: popsize, nsteps, d, max_it must be positive");
+  if (d > 128) return fail_arg(MLF_E_DIM, "the simple slice population (one wave per worker, lane = coordinate pair) covers up to 128 dimensions");
+  // point * nsteps + step, point * d + coordinate and nsteps * max_it are ints on the device or the host
+  if (popsize > (1u << 24) || nsteps > 65535 || max_it > 65535 || popsize * nsteps > 0x7fffffffull || popsize * d > 0x7fffffffull ||
+      nsteps * max_it > 0x7fffffffull)
+    return fail_arg(MLF_E_BADARG, "mlf_sslice_create: population too large");
+  if (int rc = ensure_ctx()) return rc;
+  mlf_sslice *w = new mlf_sslice();
+  w->P = (int)popsize;
+  w->nsteps = (int)nsteps;
+  w->d = (int)d;
+  w->max_it = (int)max_it;
+  const size_t P = popsize;
+  struct {
+    DevBuf *b;
+    size_t bytes;
+  } plan[] = {{&w->u, P * d * 8},    {&w->p, P * d * 8},      {&w->L, P * 8},          {&w->start, P * 8},
+              {&w->v, P * d * 8},    {&w->tl, P * 8},         {&w->tr, P * 8},         {&w->status, P},
+              {&w->zlist, P * 4},    {&w->taken, P * 4},      {&w->taken_it, P * 4},   {&w->t, P * 8},
+              {&w->unew, P * d * 8}, {&w->pnew, P * d * 8},   {&w->Lnew, P * 8},       {&w->member, P},
+              {&w->widths, nsteps * P * 8},                   {&w->iters, nsteps * 4}, {&w->dist2, P * 8},
+              {&w->nanrow, P},       {&w->ctl, sizeof(SsliceCtl)},                     {&w->dirscale, nsteps * 8},
+              {&w->aux, d * 8},      {&w->out, kSsliceOut * 8}};
+  hipError_t err = hipHostMalloc((void **)&w->h_ctl, sizeof(SsliceCtl), hipHostMallocDefault);
+  for (auto &e : plan)
+    if (err == hipSuccess) err = e.b->reserve(e.bytes);
+  if (err != hipSuccess) {
+    mlf_sslice_destroy(w);
+    return fail_hip(err, "allocation for the simple slice population", "mlf_walk_api.hip", __LINE__);
+  }
+  *out = w;
+  return 0;
+}
+
+int mlf_sslice_destroy(mlf_sslice *w) {
+  if (!w) return 0;
+  for (DevBuf *b : w->all) b->release();
+  w->release_copies();
+  if (w->h_ctl) (void)hipHostFree(w->h_ctl);
+  delete w;
+  return 0;
+}
+
+int mlf_sslice_set_layer(mlf_sslice *w, int kind, const double *ctr, const double *mat, const double *wrap, double maxradiussq) {
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
+  return set_layer(w, kind, ctr, mat, wrap, maxradiussq);
+}
+
+int mlf_sslice_set_direction_data(mlf_sslice *w, const double *axes, const double *live, size_t nlive, const double *std) {
+  if (!w) return fail_arg(MLF_E_BADARG, "null pointer");
+  return set_direction_data(w, axes, live, nlive, std);
+}
+
+int mlf_sslice_set_live(mlf_sslice *w, const double *us, const double *Ls, size_t nlive) {
+  if (!w || !us || !Ls) return fail_arg(MLF_E_BADARG, "null pointer");
+  return set_live(w, us, Ls, nlive);
+}
+
+int mlf_sslice_refill_dev(mlf_sslice *w, double Lmin, int dirkind, const double *dirscale, int limit, double shrink,
+                          uint64_t seed, uint64_t offset, int slots_per_poll, int tkind, double ta, double tb, int lkind,
+                          const double *aux, double sigma, double *out_u, double *out_p, double *out_L, int64_t *out_start,
+                          double *out_tleft, double *out_tright, int32_t *out_taken, int32_t *out_taken_it, int32_t *out_iters,
+                          double *out_widths, double *counts, uint64_t *next_offset) {
+  return sslice_refill(w, Lmin, dirkind, dirscale, limit, shrink, seed, offset, StepEval{nullptr, tkind, ta, tb, lkind, aux, sigma},
+                       slots_per_poll,
+                       SsliceOut{out_u, out_p, out_L, out_start, out_tleft, out_tright, out_taken, out_taken_it, out_iters,
+                                 out_widths, counts},
+                       next_offset);
+}
+
+int mlf_sslice_refill_user(mlf_sslice *w, double Lmin, int dirkind, const double *dirscale, int limit, double shrink,
+                           uint64_t seed, uint64_t offset, int slots_per_poll, mlf_usermodel *model, double *out_u,
+                           double *out_p, double *out_L, int64_t *out_start, double *out_tleft, double *out_tright,
+                           int32_t *out_taken, int32_t *out_taken_it, int32_t *out_iters, double *out_widths, double *counts,
+                           uint64_t *next_offset) {
+  if (!model) return fail_arg(MLF_E_BADARG, "null pointer");
+  return sslice_refill(w, Lmin, dirkind, dirscale, limit, shrink, seed, offset, StepEval{model}, slots_per_poll,
+                       SsliceOut{out_u, out_p, out_L, out_start, out_tleft, out_tright, out_taken, out_taken_it, out_iters,
+                                 out_widths, counts},
+                       next_offset);
 }
 
 // ------------------------------------------------------------------ stateless forms ------------

@@ -1,6 +1,7 @@
 // mlf_walk_dev.hpp -- device functions shared by the population step samplers' kernels (mlf_walk.hip: the resident slice
-// walkers; mlf_rwalk.hip: the whole-population random walk).  Every form of a sampler that promises the bits of another calls
-// the SAME function here, stage by stage: the direction draw, the cube-line intersection, the move diagnostics.
+// walkers; mlf_rwalk.hip: the whole-population random walk; mlf_sslice.hip: the whole-population simple slice sampler).
+// Every form of a sampler that promises the bits of another calls the SAME function here, stage by stage: the direction
+// draw, the cube-line intersection, the move diagnostics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -156,6 +157,31 @@ __device__ inline void dw_direction(const WalkState &w, int i, int lane, int kin
         if (lane + 64 * h < d) vr[h] = acc[h];
     }
   }
+}
+
+// ---- a proposal on the line and its built-in prior transform (the whole-population samplers: mlf_rwalk.hip, mlf_sslice.hip)
+__device__ __forceinline__ double rwalk_move(double u, double v, double t) {
+  const double step = v * t;
+  return u + step;
+}
+
+__device__ __forceinline__ double rwalk_transform(int tkind, double x, double ta, double tb) {
+  double p = x;
+  if (tkind == 1) {
+    const double m = x * ta;
+    p = m + tb;
+  } else if (tkind == 2) {
+    const double m = x * ta;
+    p = m * tb;
+  }
+  return p;
+}
+
+// dw_direction reads only the dimensionality of the state it is given
+__device__ __forceinline__ WalkState direction_state(int d) {
+  WalkState ws{};
+  ws.d = d;
+  return ws;
 }
 
 // diagnose_move_distances for one walker that moved (wave-wide, lane = whitened coordinate; T rows are read

@@ -25,6 +25,11 @@ device (no graph replay, no multi-round kernel).
 ``PopulationRandomWalkSampler`` takes the same ``device_rng=``: with a direction generator that has a ``device_kind`` and a
 resident model (device likelihoods, or a user model) a whole refill -- start rows, ``nsteps`` moves of every walker,
 diagnostics, counts -- is one device call (csrc/mlf_rwalk.hip); otherwise its host loop runs as before.
+
+``PopulationSimpleSliceSampler`` takes it too: with the same conditions and one of this module's two ``slice_limit``
+functions, a refill -- start rows, ``nsteps`` slice steps of the whole population (each as many shrinking iterations as its
+slowest point needs, up to ``max_it``), diagnostics, counts -- runs on the device (csrc/mlf_sslice.hip); the host takes the
+per-step median widths from one downloaded array and keeps its bookkeeping.  Otherwise its host loop runs as before.
 """
 import ctypes
 
@@ -302,10 +307,11 @@ class PopulationSimpleSliceSampler(_BatchedPopulationSampler):
     (or ``[-1, 1]`` of the scaled direction, ``slice_limit_to_scale``) and shrinks towards the current point
     (reference popstepsampler.py:746-1001; same constructor and ``__next__`` contract).  The likelihood is always called
     with ``popsize`` points: workers whose point has found its successor are dealt to the points still searching
-    (``update_vectorised_slice_sampler``, reference stepfuncs.pyx:537-630 -- one workgroup on the device here)."""
+    (``update_vectorised_slice_sampler``, reference stepfuncs.pyx:537-630 -- one workgroup on the device here).  With
+    ``device_rng=DeviceRNG(seed)`` and the conditions of ``_device_route`` the whole refill runs on the device instead."""
 
     def __init__(self, popsize, nsteps, generate_direction, scale_adapt_factor=1.0, adapt_slice_scale_target=2.0, scale=1.0,
-                 scale_jitter_func=None, slice_limit=slice_limit_to_unitcube, max_it=100, shrink_factor=1.0):
+                 scale_jitter_func=None, slice_limit=slice_limit_to_unitcube, max_it=100, shrink_factor=1.0, device_rng=None):
         assert shrink_factor >= 1.0, "The shrink factor should be greater than 1.0 to be efficient"
         self.popsize, self.nsteps, self.generate_direction = popsize, nsteps, generate_direction
         self.max_it, self.shrink_factor = max_it, shrink_factor
@@ -316,13 +322,83 @@ class PopulationSimpleSliceSampler(_BatchedPopulationSampler):
         self.logstat = []
         self.logstat_labels = ['accept_rate', 'efficiency', 'scale', 'far_enough', 'mean_rel_jump']
         self.prepared_samples = []
+        if device_rng is not None and not isinstance(device_rng, DeviceRNG):
+            raise TypeError("device_rng must be an ultranest_amd.regions.DeviceRNG")
+        self.device_rng = device_rng
+        self.force_slots_per_poll = 0     # tests: slots queued between two reads of the control block (0: the library's policy)
+        self._sslice = None
+        self._seen = dict(region=None, layer=None, r2=None, calls=0)
 
     def __str__(self):
         return 'PopulationSimpleSliceSampler(popsize=%d, nsteps=%d, generate_direction=%s, scale=%.g)' % (
             self.popsize, self.nsteps, self.generate_direction, self.scale)
 
+    def _device_route(self, transform, loglike, ndim=None, test=False):
+        """What a refill runs on: None = the host loop; else ``(device_kind, limit, tspec, lspec, user)`` of a whole refill on
+        the device -- it takes ``device_rng``, a direction generator with a ``device_kind``, a resident model (both
+        callbacks with a built-in ``device_spec``, or a user model as ``devicemodel.device_route`` decides it), at most 128
+        dimensions (``mlf_sslice``: one wave per worker, lane = coordinate pair), one of this module's two ``slice_limit``
+        functions (by identity; `limit` 0 = unit cube, 1 = clipped to [-1, 1]) and no ``test`` start."""
+        if self.device_rng is None or test or (ndim is not None and ndim > 128):
+            return None
+        device_kind = getattr(self.generate_direction, "device_kind", None)
+        if device_kind is None:
+            return None
+        if self.slice_limit is slice_limit_to_unitcube:
+            limit = 0
+        elif self.slice_limit is slice_limit_to_scale:
+            limit = 1
+        else:
+            return None
+        tspec, lspec, user = _resident_model(transform, loglike)
+        if user is None and tspec is None:
+            return None
+        return device_kind, limit, tspec, lspec, user
+
+    def region_changed(self, Ls, region):
+        """Nothing of the region is cached on the host; the device copies are refreshed at the next refill."""
+        self._seen["region"] = None
+
+    def _refill_on_device(self, region, Lmin, us, Ls, device_kind, limit, tspec, lspec, user):
+        """The whole refill on the device (``mlf_sslice_refill_dev`` / ``_refill_user``): start rows, directions and slice
+        draws come from Philox, nothing but the live points and the per-step direction lengths is uploaded.  The jitter
+        function is called ``nsteps`` times up front, in step order.  Counts, scale adaptation, the assertion and
+        ``prepared_samples`` are the host path's, from the numbers that come back (kept in ``last_refill``)."""
+        nlive, ndim = us.shape
+        P = self.popsize
+        if self._sslice is None or self._sslice.shape != (P, self.nsteps, ndim, self.max_it):
+            self._sslice = _SliceWalkers(P, self.nsteps, ndim, self.max_it)
+            self._seen.update(region=None, layer=None, r2=None)
+        w = self._sslice
+        _sync_region_copies(w, self._seen, region, ndim, device_kind, skip_live=True)
+        w.set_live(us, Ls)
+        dirscale = np.array([self.scale * self.scale_jitter_func() for _ in range(self.nsteps)], dtype=float)
+        out = w.refill(Lmin, device_kind, dirscale, limit, self.shrink_factor, self.device_rng, tspec, lspec, user,
+                       slots_per_poll=self.force_slots_per_poll)
+        self.last_refill = out
+        nc = P * out["niter"]
+        width_sum = 0.
+        for row in out["widths"]:
+            width_sum += np.median(row)
+        mean_width = width_sum / self.nsteps
+        self.discarded += out["discarded"]
+        self.ncalls += nc
+        assert out["nnan"] == 0, 'some walkers never moved! Double nsteps of PopulationSimpleSliceSampler.'
+        self.prepared_samples = list(zip(out["u"], out["p"], out["L"]))
+        have = region.maxradiussq is not None
+        self.logstat.append([P / nc, self.scale, self.nsteps, out["nfar"] / P if have else 0,
+                             np.exp(out["sumlog"] / P) if have else 0])
+        if mean_width >= 1. / self.adapt_slice_scale_target:
+            self.scale *= 1. / self.scale_adapt_factor
+        else:
+            self.scale *= self.scale_adapt_factor
+        return nc
+
     def _refill(self, region, Lmin, us, Ls, transform, loglike, test=False):
         nlive, ndim = us.shape
+        route = self._device_route(transform, loglike, ndim, test=test)
+        if route is not None:
+            return self._refill_on_device(region, Lmin, us, Ls, *route)
         P = self.popsize
         start = np.random.randint(0, nlive, size=P)
         allu = np.array(us if test else us[start, :], dtype=float)        # test: the live points themselves (reversibility checks)
@@ -420,6 +496,67 @@ class _RandomWalkers(object):
         out["ever"], out["last"] = out["ever"].view(np.bool_), out["last"].view(np.bool_)
         out.update(nrejects=int(counts[0]), nlast=int(counts[1]), nfar=counts[2], sumlog=counts[3], nnever=int(counts[4]),
                    chain_form=bool(counts[5]))
+        return out
+
+
+class _SliceWalkers(object):
+    """Owner of one ``mlf_sslice`` handle (include/mlfriends_hip.h): the population of PopulationSimpleSliceSampler."""
+
+    def __init__(self, popsize, nsteps, ndim, max_it):
+        self.shape = (int(popsize), int(nsteps), int(ndim), int(max_it))
+        self.popsize, self.nsteps, self.ndim, self.max_it = self.shape
+        handle = ctypes.c_void_p()
+        check(_lib.lib().mlf_sslice_create(ctypes.byref(handle), *self.shape))
+        self._h = handle
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                _lib.lib().mlf_sslice_destroy(h)
+            except Exception:
+                pass
+
+    def set_layer(self, kind, ctr, mat, wrap, maxradiussq):
+        check(_lib.lib().mlf_sslice_set_layer(self._h, int(kind), ptr(None if ctr is None else f64(ctr)),
+                                              ptr(None if mat is None else f64(mat)),
+                                              ptr(None if wrap is None else f64(wrap)), float(maxradiussq)))
+
+    def set_direction_data(self, axes=None, live=None, std=None):
+        live = None if live is None else f64(live)
+        check(_lib.lib().mlf_sslice_set_direction_data(
+            self._h, ptr(None if axes is None else f64(axes)), ptr(live), 0 if live is None else len(live),
+            ptr(None if std is None else f64(std))))
+
+    def set_live(self, us, Ls):
+        us, Ls = f64(us), f64(Ls)
+        check(_lib.lib().mlf_sslice_set_live(self._h, ptr(us), ptr(Ls), len(Ls)))
+
+    def refill(self, Lmin, kind, dirscale, limit, shrink, rng, tspec=None, lspec=None, user=None, slots_per_poll=0):
+        """One refill; advances rng.offset.  dict of per-point arrays u, p, L, start, tleft, tright (the slice after the last
+        step), taken, taken_it (worker and iteration of the last step's successor, -1 without one), the per-step iters and
+        widths (nsteps x popsize), and the counts discarded, niter (iterations in all), nfar, sumlog, nnan (points with a
+        non-finite p row)."""
+        P, d, nsteps = self.popsize, self.ndim, self.nsteps
+        dirscale = f64(dirscale)
+        if dirscale.shape != (nsteps,):
+            raise ValueError("one direction length per step is needed")
+        out = dict(u=np.empty((P, d)), p=np.empty((P, d)), L=np.empty(P), start=np.empty(P, dtype=np.int64), tleft=np.empty(P),
+                   tright=np.empty(P), taken=np.empty(P, dtype=np.int32), taken_it=np.empty(P, dtype=np.int32),
+                   iters=np.empty(nsteps, dtype=np.int32), widths=np.empty((nsteps, P)))
+        counts = np.empty(5)
+        nxt = ctypes.c_uint64(0)
+        outs = tuple(ptr(out[k]) for k in ("u", "p", "L", "start", "tleft", "tright", "taken", "taken_it", "iters", "widths")) + (
+            ptr(counts), ctypes.byref(nxt))
+        head = (self._h, float(Lmin), int(kind), ptr(dirscale), int(limit), float(shrink), ctypes.c_uint64(rng.seed),
+                ctypes.c_uint64(rng.offset), int(slots_per_poll))
+        if user is not None:
+            model, with_transform = user
+            check(_lib.lib().mlf_sslice_refill_user(*head, model.handle(with_transform), *outs))
+        else:
+            check(_lib.lib().mlf_sslice_refill_dev(*head, *_Walkers._builtin_args(tspec, lspec), *outs))
+        rng.offset = nxt.value
+        out.update(discarded=int(counts[0]), niter=int(counts[1]), nfar=counts[2], sumlog=counts[3], nnan=int(counts[4]))
         return out
 
 
