@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MLF_ABI_VERSION 2
+#define MLF_ABI_VERSION 3
 
 #define MLF_E_BADARG 1      /* null pointer, zero dimension, inconsistent sizes            */
 #define MLF_E_DIM 2         /* dimensionality above MLF_MAX_DIM                            */
@@ -582,13 +582,33 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
  *                          model runs ONLY in mlf_region_refill_user on a region with a t-region set; every other launch of it
  *                          (eval, eval_dev, the walkers, a refill without t-region) returns MLF_E_STATE.  Its entry is
  *                          mlf_user_rows_tregion: create_variant returns MLF_E_BADARG for a code object compiled as the
- *                          other variant. */
+ *                          other variant.
+ *   MLF_USERMODEL_SUM      the summed form (-DMLF_USER_SUM=1): the likelihood is a sum over data terms.  The source defines
+ *                            __device__ double mlf_user_loglike_term(const double *p, int d, const double *aux, long long naux,
+ *                                                                    long long k);
+ *                          instead of mlf_user_loglike, and L(p) = sum over k in [0, nterms) of term(k).  One wave owns one row
+ *                          (the default form: one thread), its 64 lanes split the terms and read aux side by side.  The order
+ *                          of the sum is part of the interface: lane l starts from 0.0 and adds term(l), term(l + 64), ...
+ *                          in ascending order, one plain addition each; then six exchange steps with lane distances 32, 16,
+ *                          8, 4, 2, 1, in that order, each setting every lane to s_l + s_(l xor m); L is the value all lanes
+ *                          then hold.  It depends neither on the row's place in the batch nor on the batch, the mask or the
+ *                          route; a NaN term gives NaN, -inf terms give -inf.  The transform runs on one lane of the wave.
+ *                          Entry mlf_user_rows_sum (the default kernel's eight parameters, then long long nterms).  Such a
+ *                          model runs wherever a default one does.
+ *   MLF_USERMODEL_SUM_TREGION  summed and gated (-DMLF_USER_SUM=1 -DMLF_USER_TREGION=1): entry mlf_user_rows_sum_tregion
+ *                          (nterms, then the gate's five parameters); runs where MLF_USERMODEL_TREGION runs.
+ * A summed code object is loaded with mlf_usermodel_create_sum (variant MLF_USERMODEL_SUM or _SUM_TREGION, nterms >= 1;
+ * everything else as create_variant, which returns MLF_E_BADARG for these two variants). */
 #define MLF_USERMODEL_DEFAULT 0
 #define MLF_USERMODEL_TREGION 1
+#define MLF_USERMODEL_SUM 2
+#define MLF_USERMODEL_SUM_TREGION 3
 int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant,
                                   void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap);
 int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int has_transform, int variant,
                                  const double *aux, size_t naux, mlf_usermodel **out);
+int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
+                             const double *aux, size_t naux, mlf_usermodel **out);
 int mlf_usermodel_destroy(mlf_usermodel *model);
 int mlf_usermodel_eval(mlf_usermodel *model, const double *u, size_t n, double *p_out, double *L_out);
 int mlf_usermodel_eval_dev(mlf_usermodel *model, const double *d_u, size_t n, const uint8_t *d_member, double *d_p,

@@ -28,7 +28,9 @@ struct mlf_usermodel {
   hipFunction_t fn = nullptr;
   int d = 0;
   bool has_transform = false;
-  bool gated = false;   // the MLF_USERMODEL_TREGION variant: mlf_user_rows takes the gate's five parameters as well
+  bool gated = false;   // the MLF_USERMODEL_TREGION / _SUM_TREGION variants: the kernel takes the gate's five parameters as well
+  bool summed = false;  // the MLF_USERMODEL_SUM / _SUM_TREGION variants: one wave per row, nterms behind the first eight parameters
+  long long nterms = 0;
   long long naux = 0;
   DevBuf aux;
   DevBuf hu, hp, hL;   // staging of mlf_usermodel_eval (host arrays)
@@ -111,9 +113,11 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
     return fail_arg(MLF_E_STATE, m->gated ? "user model loaded as the t-region variant: it runs only in a refill with a t-region set"
                                           : "user model not loaded as the t-region variant (mlf_usermodel_create_variant)");
   if (n <= 0) return 0;
-  const long long blocks = (n + 63) / 64;
+  // default form: one thread per row, 64 rows per workgroup; summed form: one wave (= one workgroup) per row
+  const long long blocks = m->summed ? n : (n + 63) / 64;
   if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
-  const unsigned lds = mlf_user_rows_lds_bytes(m->d, p != nullptr && m->has_transform);
+  const bool p_buffer = p != nullptr && m->has_transform;
+  const unsigned lds = m->summed ? mlf_user_rows_sum_lds_bytes(m->d, p_buffer) : mlf_user_rows_lds_bytes(m->d, p_buffer);
   // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
   const double *a_u = u;
   long long a_n = n;
@@ -122,20 +126,75 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
   const double *a_aux = m->aux.as<double>();
   long long a_naux = m->naux;
   double *a_p = p, *a_L = L;
+  long long a_nterms = m->nterms;
+  const double *g_A = nullptr, *g_ctr = nullptr, *g_fixed = nullptr;
+  double g_enlarge = 0.0;
+  unsigned char *g_member2 = nullptr;
   if (gate) {
-    const double *g_A = gate->A, *g_ctr = gate->ctr, *g_fixed = gate->fixed_val;
-    double g_enlarge = gate->enlarge;
-    unsigned char *g_member2 = gate->member2;
-    void *args[] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L, &g_A, &g_ctr, &g_fixed, &g_enlarge, &g_member2};
-    CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
-    return 0;
+    g_A = gate->A, g_ctr = gate->ctr, g_fixed = gate->fixed_val;
+    g_enlarge = gate->enlarge;
+    g_member2 = gate->member2;
   }
-  void *args[] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
+  // the first eight, nterms in the ninth place of a summed model, the gate's five behind them when gated
+  void *args[14] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
+  int na = 8;
+  if (m->summed) args[na++] = &a_nterms;
+  if (gate) {
+    void *g[] = {&g_A, &g_ctr, &g_fixed, &g_enlarge, &g_member2};
+    for (void *x : g) args[na++] = x;
+  }
   CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
   return 0;
 }
 
 }  // namespace mlf
+
+namespace {
+
+// the checks every create entry makes before it touches the device
+int check_create_args(const void *code, size_t nbytes, size_t d) {
+  if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
+  if (d > MLF_MAX_DIM) return fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
+  if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return fail_arg(MLF_E_BADARG, "not a code object (ELF)");
+  return 0;
+}
+
+// loads the code object as `variant` (arguments checked by the caller); nterms: 0 unless the variant is a summed one
+int load_model(const void *code, size_t d, int has_transform, int variant, size_t nterms, const double *aux, size_t naux,
+               mlf_usermodel **out) {
+  if (int rc = ensure_ctx()) return rc;
+  hipStream_t s = ctx_stream();
+  mlf_usermodel *m = new mlf_usermodel();
+  m->d = (int)d;
+  m->has_transform = has_transform != 0;
+  m->gated = variant == MLF_USERMODEL_TREGION || variant == MLF_USERMODEL_SUM_TREGION;
+  m->summed = variant == MLF_USERMODEL_SUM || variant == MLF_USERMODEL_SUM_TREGION;
+  m->nterms = (long long)nterms;
+  m->naux = (long long)naux;
+  const char *entry = m->summed ? (m->gated ? "mlf_user_rows_sum_tregion" : "mlf_user_rows_sum")
+                                : (m->gated ? "mlf_user_rows_tregion" : "mlf_user_rows");
+  hipError_t e = hipModuleLoadData(&m->module, code);
+  if (e == hipSuccess && hipModuleGetFunction(&m->fn, m->module, entry) != hipSuccess) {
+    // the variants' entries differ in name: this code object was compiled as the other one (or is no user model at all)
+    (void)hipGetLastError();
+    (void)hipModuleUnload(m->module);
+    delete m;
+    return fail_arg(MLF_E_BADARG, "the code object has no entry of this variant (compiled as another variant?)");
+  }
+  if (e == hipSuccess) e = m->aux.reserve(naux ? naux * sizeof(double) : sizeof(double));
+  if (e == hipSuccess && naux) e = hipMemcpyAsync(m->aux.p, aux, naux * sizeof(double), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    if (m->module) (void)hipModuleUnload(m->module);
+    m->aux.release();
+    delete m;
+    return fail_hip(e, "mlf_usermodel_create", "mlf_user.hip", __LINE__);
+  }
+  *out = m;
+  return 0;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -148,8 +207,11 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
 int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant, void *code_out,
                                   size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
   if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION)
+  if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION && variant != MLF_USERMODEL_SUM &&
+      variant != MLF_USERMODEL_SUM_TREGION)
     return fail_arg(MLF_E_BADARG, "unknown user-model variant");
+  const bool v_gated = variant == MLF_USERMODEL_TREGION || variant == MLF_USERMODEL_SUM_TREGION;
+  const bool v_summed = variant == MLF_USERMODEL_SUM || variant == MLF_USERMODEL_SUM_TREGION;
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
@@ -162,7 +224,8 @@ int mlf_usermodel_compile_variant(const char *source, const char *include_dir, i
   const std::string inc = std::string("-I") + include_dir;
   const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
                         has_transform ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
-                        variant == MLF_USERMODEL_TREGION ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0"};
+                        v_gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
+                        v_summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0"};
   hiprtcProgram prog = nullptr;
   hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
   if (res != HIPRTC_SUCCESS) {
@@ -210,37 +273,23 @@ int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int 
                                  size_t naux, mlf_usermodel **out) {
   if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
+  if (variant == MLF_USERMODEL_SUM || variant == MLF_USERMODEL_SUM_TREGION)
+    return fail_arg(MLF_E_BADARG, "a summed user-model variant needs its number of terms: mlf_usermodel_create_sum");
   if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION)
     return fail_arg(MLF_E_BADARG, "unknown user-model variant");
-  if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
-  if (d > MLF_MAX_DIM) return fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
-  if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return fail_arg(MLF_E_BADARG, "not a code object (ELF)");
-  if (int rc = ensure_ctx()) return rc;
-  hipStream_t s = ctx_stream();
-  mlf_usermodel *m = new mlf_usermodel();
-  m->d = (int)d;
-  m->has_transform = has_transform != 0;
-  m->gated = variant == MLF_USERMODEL_TREGION;
-  m->naux = (long long)naux;
-  hipError_t e = hipModuleLoadData(&m->module, code);
-  if (e == hipSuccess && hipModuleGetFunction(&m->fn, m->module, m->gated ? "mlf_user_rows_tregion" : "mlf_user_rows") != hipSuccess) {
-    // the variants' entries differ in name: this code object was compiled as the other one (or is no user model at all)
-    (void)hipGetLastError();
-    (void)hipModuleUnload(m->module);
-    delete m;
-    return fail_arg(MLF_E_BADARG, "the code object has no entry of this variant (compiled as another variant?)");
-  }
-  if (e == hipSuccess) e = m->aux.reserve(naux ? naux * sizeof(double) : sizeof(double));
-  if (e == hipSuccess && naux) e = hipMemcpyAsync(m->aux.p, aux, naux * sizeof(double), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    if (m->module) (void)hipModuleUnload(m->module);
-    m->aux.release();
-    delete m;
-    return fail_hip(e, "mlf_usermodel_create", "mlf_user.hip", __LINE__);
-  }
-  *out = m;
-  return 0;
+  if (int rc = check_create_args(code, nbytes, d)) return rc;
+  return load_model(code, d, has_transform, variant, 0, aux, naux, out);
+}
+
+int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
+                             const double *aux, size_t naux, mlf_usermodel **out) {
+  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
+  *out = nullptr;
+  if (variant != MLF_USERMODEL_SUM && variant != MLF_USERMODEL_SUM_TREGION)
+    return fail_arg(MLF_E_BADARG, "mlf_usermodel_create_sum: the variant must be MLF_USERMODEL_SUM or MLF_USERMODEL_SUM_TREGION");
+  if (nterms == 0 || nterms > 0x7fffffffffffffffull) return fail_arg(MLF_E_BADARG, "a summed user model has at least one term");
+  if (int rc = check_create_args(code, nbytes, d)) return rc;
+  return load_model(code, d, has_transform, variant, nterms, aux, naux, out);
 }
 
 int mlf_usermodel_destroy(mlf_usermodel *m) {

@@ -29,6 +29,31 @@
 // tests it, calls the likelihood only if it passes and writes member2[i] = member[i] && inside(p_i); the kernel is named
 // mlf_user_rows_tregion and takes (tr_A, tr_ctr, tr_fixed, tr_enlarge, member2) behind its other parameters.  Matrix, centre and fixed values are read
 // through wave-uniform addresses: no extra LDS, the same choice of form.
+//
+// Summed form (MLF_USER_SUM=1, its own code objects: mlf_user_rows_sum and, with MLF_USER_TREGION=1,
+// mlf_user_rows_sum_tregion; they are the only kernel of their program).  The user's source defines, instead of mlf_user_loglike,
+//
+//   __device__ double mlf_user_loglike_term(const double *p, int d, const double *aux, long long naux, long long k);
+//
+// and L(p) = sum over k in [0, nterms) of term(k).  The kernels take the eight parameters above, then `long long nterms`, then
+// the gate's five in the gated entry (9 and 14).  ONE WAVE OWNS ONE ROW (one wave per workgroup, blockIdx.x = row: every
+// barrier is wave-local and the wave of a row outside the mask leaves at once, having written L = -inf (and member2 = 0) from
+// lane 0 and read nothing but its member byte).  The wave copies the u row into LDS with coalesced loads; lane 0 alone runs
+// mlf_user_transform from that row into a second LDS row (O(d) work on one lane: accepted, the terms are where the time goes)
+// and, in the gated entry, mlf_tregion_inside on the p row (the function and arithmetic of the gated default kernel), whose
+// result is made wave-uniform; all lanes read the p row back from LDS.  The p row of every member row leaves LDS with coalesced
+// stores, whether or not it passes the gate.  Inside the term function p points into LDS and k differs from lane to lane, so
+// aux[... k ...] is read by neighbouring lanes at neighbouring addresses.
+//
+// The order of the sum is part of the interface (compiled with -ffp-contract=off like everything here):
+//   per lane      lane l (0..63) starts from s_l = 0.0 and adds term(k) for k = l, l + 64, l + 128, ... < nterms, ascending,
+//                 one plain addition each;
+//   across lanes  six exchange steps with lane distances 32, 16, 8, 4, 2, 1 in that order, each setting every lane to
+//                 s_l + s_(l xor m) (__shfl_xor on the double);
+//   result        IEEE addition commutes, so after the six steps all lanes hold the same bits: L is that value.
+// L therefore does not depend on the row's place in the batch, the batch size, the mask or the route; a NaN term gives NaN,
+// -inf terms give -inf.  LDS per wave: (p buffer ? 2 : 1) * d * 8 bytes (mlf_user_rows_sum_lds_bytes; at most 16 KiB at
+// MLF_MAX_DIM = 1024, so there is no direct form and no threshold in d).
 #pragma once
 
 #define MLF_USER_ROWS_LDS_BUDGET 65536
@@ -39,6 +64,11 @@ __host__ __device__ inline unsigned mlf_user_rows_lds_bytes(int d, bool has_p_bu
   return bytes <= MLF_USER_ROWS_LDS_BUDGET ? (unsigned)bytes : 0u;
 }
 
+// bytes of dynamic LDS a launch of the summed form needs: the u row, and the p row where a transform writes one
+__host__ __device__ inline unsigned mlf_user_rows_sum_lds_bytes(int d, bool has_p_buffer) {
+  return (unsigned)((has_p_buffer ? 2u : 1u) * (unsigned)d * 8u);
+}
+
 #ifndef MLF_USER_ROWS_HOST
 
 #ifndef MLF_USER_HAS_TRANSFORM
@@ -46,6 +76,9 @@ __host__ __device__ inline unsigned mlf_user_rows_lds_bytes(int d, bool has_p_bu
 #endif
 #ifndef MLF_USER_TREGION
 #define MLF_USER_TREGION 0
+#endif
+#ifndef MLF_USER_SUM
+#define MLF_USER_SUM 0
 #endif
 #if MLF_USER_TREGION
 #include "mlf_tregion_dev.hpp"
@@ -117,6 +150,8 @@ __device__ inline void transform_row(const double *x, double *y, int d, const do
 }
 
 }  // namespace mlf_user_detail
+
+#if !MLF_USER_SUM
 
 extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const double *u, long long n, int d, const unsigned char *member,
                                                                 const double *aux, long long naux, double *p, double *L
@@ -190,5 +225,77 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const doubl
 #endif
   if (L != nullptr && lane < nrows) L[i] = like;
 }
+
+#else  // MLF_USER_SUM
+
+#if MLF_USER_TREGION
+#define MLF_USER_SUM_ENTRY mlf_user_rows_sum_tregion
+#else
+#define MLF_USER_SUM_ENTRY mlf_user_rows_sum
+#endif
+
+extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(const double *u, long long n, int d, const unsigned char *member,
+                                                               const double *aux, long long naux, double *p, double *L,
+                                                               long long nterms
+#if MLF_USER_TREGION
+                                                               ,
+                                                               const double *__restrict__ tr_A, const double *__restrict__ tr_ctr,
+                                                               const double *__restrict__ tr_fixed, double tr_enlarge,
+                                                               unsigned char *member2
+#endif
+) {
+  using namespace mlf_user_detail;
+  const int lane = threadIdx.x;
+  const long long i = blockIdx.x;   // one wave, one row
+  if (i >= n) return;
+  if (member != nullptr && member[i] == 0) {   // the same byte in every lane: the whole wave leaves
+    if (lane == 0) {
+      if (L != nullptr) L[i] = neg_inf();
+#if MLF_USER_TREGION
+      member2[i] = 0;
+#endif
+    }
+    return;
+  }
+  extern __shared__ __attribute__((aligned(16))) double mlf_user_lds[];
+  const bool p_buffer = p != nullptr && MLF_USER_HAS_TRANSFORM;
+  double *a = mlf_user_lds;            // the u row
+  double *b = p_buffer ? a + d : a;    // the p row (the u row itself without a transform)
+  const double *src = u + i * d;
+  for (int e = lane; e < d; e += 64) a[e] = src[e];
+  __syncthreads();
+#if MLF_USER_HAS_TRANSFORM
+  if (p_buffer) {
+    if (lane == 0) mlf_user_transform(a, b, d, aux, naux);
+    __syncthreads();   // the other lanes read lane 0's p row from LDS
+  }
+#endif
+#if MLF_USER_TREGION
+  int inside = 0;
+  if (lane == 0) inside = mlf_tregion_inside(b, d, tr_A, tr_ctr, tr_fixed, tr_enlarge) ? 1 : 0;
+  const bool pass = __builtin_amdgcn_readfirstlane(inside) != 0;   // all 64 lanes are active: lane 0 is the first
+#else
+  const bool pass = true;
+#endif
+  if (p != nullptr) {
+    double *dst = p + i * d;
+    for (int e = lane; e < d; e += 64) dst[e] = b[e];
+  }
+  double s = neg_inf();
+  if (L != nullptr && pass) {
+    s = 0.0;
+    for (long long k = lane; k < nterms; k += 64) s = s + mlf_user_loglike_term(b, d, aux, naux, k);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m);
+  }
+  if (lane == 0) {
+    if (L != nullptr) L[i] = s;
+#if MLF_USER_TREGION
+    member2[i] = pass ? 1 : 0;
+#endif
+  }
+}
+
+#endif  // MLF_USER_SUM
 
 #endif  // MLF_USER_ROWS_HOST

@@ -5,7 +5,7 @@ The GPU counterpart of the reference's compiled-language likelihoods (reference 
 device functions, the package compiles them at run time for gfx950 (hiprtc) around one wrapper kernel
 (``csrc/mlf_user_rows.hpp``) and hands back a pair of vectorized callbacks::
 
-    model = DeviceModel(ndim, loglike_source, transform_source=None, aux=None)
+    model = DeviceModel(ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None)
     model.loglike(theta)    # (n, ndim) -> (n,)       vectorized callback, evaluated on the GPU
     model.transform(u)      # (n, ndim) -> (n, ndim)  vectorized callback (identity without a transform source)
 
@@ -43,6 +43,48 @@ Not covered (a user model then runs on the per-step route, which returns the sam
 
 Derived parameters (``num_params != x_dim``) keep the host route: a model has ``nparams == ndim``.
 
+Likelihoods summed over data terms (``nterms=K``)
+-------------------------------------------------
+The default form gives every row one thread: a likelihood that loops over ``aux`` (chi-square over spectral bins, a
+Gaussian over observations) walks its data serially in that thread, all 64 lanes of a wave reading the same ``aux[k]``.
+The routes above evaluate populations of 10^2 to 10^4 rows, which is a few dozen waves on a device with 1024 SIMDs.  With
+``nterms=K`` (a Python int, K >= 1) the likelihood source defines, INSTEAD of ``mlf_user_loglike``::
+
+    __device__ double mlf_user_loglike_term(const double *p, int d, const double *aux, long long naux, long long k);
+
+and ``L(p) = sum over k in [0, K) of term(k)``.  One wave then owns one row, its 64 lanes split the terms and read ``aux``
+side by side (index ``aux`` by ``k``).  Transform source, ``aux``, the callbacks, ``eval_dev`` and ``device_route`` are
+unchanged, and every route recognises a summed model exactly as it does a default one; its four programs (with or without
+transform, gated or not) are compiled with ``-DMLF_USER_SUM=1`` under their own cache keys and loaded through
+``mlf_usermodel_create_sum``.  The prior transform of a summed model runs on one lane of the row's wave.
+
+The order of the sum is part of the interface (``csrc/mlf_user_rows.hpp``; ``-ffp-contract=off`` as above):
+
+* per lane: lane ``l`` (0..63) starts from ``s_l = 0.0`` and adds ``term(k)`` for ``k = l, l+64, l+128, ... < K`` in
+  ascending order, one plain addition each;
+* across lanes: six exchange steps with lane distances 32, 16, 8, 4, 2, 1, in that order, each setting every lane to
+  ``s_l + s_(l xor m)``;
+* result: IEEE addition commutes, so all lanes hold the same bits after the six steps, and ``L`` is that value.
+
+In numpy (sequential additions; ``np.sum`` is pairwise and is NOT this order)::
+
+    s = np.zeros(64)
+    for k in range(K): s[k % 64] += t[k]
+    for m in (32, 16, 8, 4, 2, 1): s = s + s[np.arange(64) ^ m]
+    L = s[0]
+
+So ``L`` does not depend on the row's position in the batch, the batch size, the membership mask or the route; a NaN term
+gives NaN; ``-inf`` terms give ``-inf``.  A non-additive tail -- a final function of the sum, per-row constants added once --
+is out of scope: constants can live in term 0.
+
+Which form.  Measured with ``usermodels.linear_sum`` against its twin at d = 10 (``scripts/summed_model_bench.py``,
+``profiles/summed_model_bench.json``): at 1024 rows the summed form is 29.5 times faster with 1024 terms and 35.5 times with
+16384 terms, at 16384 rows still 3.9 and 1.9 times; the crossover lies between 16384 and 65536 rows per call, and at 2^17
+rows the default form is about 4 times faster (every row's wave then reads all of ``aux`` through the caches, which the
+default form reads once per 64 rows).  So: the summed form for what the population routes send -- ``PopulationSliceSampler``,
+the whole-refill samplers, region refills of a few thousand draws, up to about 10^4 rows per call -- and for many terms; the
+default form for batches of 10^5 rows and more, or for a likelihood of a handful of terms.
+
 Compiling needs no GPU; code objects are cached per process, keyed by a hash of the source, the options and the
 wrapper header.  Evaluating without a GPU raises ``HipLibraryError`` like every other compute call (no CPU fallback).
 """
@@ -58,8 +100,9 @@ from ._lib import check, f64, ptr
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 HEADER = os.path.join(INCLUDE_DIR, "mlf_user_rows.hpp")
 GATE_HEADER = os.path.join(INCLUDE_DIR, "mlf_tregion_dev.hpp")      # included by the gated variant only
-VARIANT_DEFAULT, VARIANT_TREGION = 0, 1                             # MLF_USERMODEL_* of include/mlfriends_hip.h
-# what mlf_usermodel_compile passes to hiprtc besides -I, -DMLF_USER_HAS_TRANSFORM and -DMLF_USER_TREGION (part of the cache key)
+VARIANT_DEFAULT, VARIANT_TREGION, VARIANT_SUM, VARIANT_SUM_TREGION = 0, 1, 2, 3     # MLF_USERMODEL_* of include/mlfriends_hip.h
+# what mlf_usermodel_compile passes to hiprtc besides -I, -DMLF_USER_HAS_TRANSFORM, -DMLF_USER_TREGION and -DMLF_USER_SUM (part
+# of the cache key)
 COMPILE_OPTIONS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off")
 MLF_E_COMPILE = 5
 
@@ -75,7 +118,7 @@ class DeviceModelCompileError(RuntimeError):
         RuntimeError.__init__(self, "the device model did not compile:\n" + log)
 
 
-def _cache_key(source, has_transform, gated=False):
+def _cache_key(source, has_transform, gated=False, summed=False):
     h = hashlib.sha256()
     with open(HEADER, "rb") as fh:
         header = fh.read()
@@ -84,16 +127,20 @@ def _cache_key(source, has_transform, gated=False):
         options += " tregion"
         with open(GATE_HEADER, "rb") as fh:
             header += fh.read()
+    if summed:
+        options += " sum"
     for part in (source.encode(), b"\0", options.encode(), b"\0", header):
         h.update(part)
     return h.hexdigest()
 
 
-def compile_model(source, has_transform, gated=False):
+def compile_model(source, has_transform, gated=False, summed=False):
     """The gfx950 code object (bytes) of `source` + the wrapper kernel; cached per process.  gated: the variant with the
-    t-region test between transform and likelihood (module docstring), another program under its own key."""
+    t-region test between transform and likelihood (module docstring), another program under its own key.  summed: the
+    one-wave-per-row form around ``mlf_user_loglike_term`` (module docstring), two more programs under their own keys."""
     global compile_calls
-    key = _cache_key(source, has_transform, gated)
+    key = _cache_key(source, has_transform, gated, summed)
+    variant = (VARIANT_TREGION if gated else VARIANT_DEFAULT) + (VARIANT_SUM if summed else 0)
     code = _code_cache.get(key)
     if code is not None:
         return code
@@ -104,9 +151,9 @@ def compile_model(source, has_transform, gated=False):
     for _ in range(2):
         buf = ctypes.create_string_buffer(cap)
         compile_calls += 1
-        if gated:
+        if variant != VARIANT_DEFAULT:
             rc = L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)),
-                                                 VARIANT_TREGION, buf, cap, ctypes.byref(size), log, len(log))
+                                                 variant, buf, cap, ctypes.byref(size), log, len(log))
         else:
             rc = L.mlf_usermodel_compile(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), buf, cap,
                                          ctypes.byref(size), log, len(log))
@@ -146,9 +193,13 @@ class _Callback(object):
 class _Handle(object):
     """One loaded model (``mlf_usermodel``) on the library's device."""
 
-    def __init__(self, code, ndim, has_transform, aux, gated=False):
+    def __init__(self, code, ndim, has_transform, aux, gated=False, nterms=None):
         h = ctypes.c_void_p()
-        if gated:
+        if nterms is not None:
+            check(_lib.lib().mlf_usermodel_create_sum(code, len(code), int(ndim), int(bool(has_transform)),
+                                                      VARIANT_SUM_TREGION if gated else VARIANT_SUM, int(nterms), ptr(aux),
+                                                      len(aux), ctypes.byref(h)))
+        elif gated:
             check(_lib.lib().mlf_usermodel_create_variant(code, len(code), int(ndim), int(bool(has_transform)),
                                                           VARIANT_TREGION, ptr(aux), len(aux), ctypes.byref(h)))
         else:
@@ -174,37 +225,57 @@ class _Handle(object):
 
 
 class DeviceModel(object):
-    """A likelihood (and optional prior transform) written as HIP device functions (module docstring)."""
+    """A likelihood (and optional prior transform) written as HIP device functions (module docstring).  nterms=K: the
+    summed form, whose likelihood source defines ``mlf_user_loglike_term`` and whose L is the sum of its K terms in the
+    documented order; a non-additive tail (a function of the sum, per-row constants) is out of scope."""
 
     _count = 0
 
-    def __init__(self, ndim, loglike_source, transform_source=None, aux=None, name=None):
+    def __init__(self, ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None):
         self.ndim = int(ndim)
         if self.ndim <= 0:
             raise ValueError("ndim must be positive")
+        if nterms is not None:
+            if isinstance(nterms, bool) or not isinstance(nterms, (int, np.integer)):
+                raise ValueError("nterms must be an integer (the number of terms of the summed form), got %r" % (nterms,))
+            if nterms < 1:
+                raise ValueError("nterms must be at least 1, got %d" % nterms)
+            nterms = int(nterms)
+        self.nterms = nterms
         self.has_transform = transform_source is not None
         self.source = loglike_source if transform_source is None else loglike_source + "\n" + transform_source
         self.aux = np.empty(0) if aux is None else f64(np.ravel(aux)).copy()
         DeviceModel._count += 1
         self.name = name or "DeviceModel%d" % DeviceModel._count
-        self.code = compile_model(self.source, self.has_transform)
+        self.code = compile_model(self.source, self.has_transform, summed=self.summed)
         self._handles = {}
         self.loglike = _Callback(self, "loglike")
         self.transform = _Callback(self, "transform")
 
+    @property
+    def summed(self):
+        return self.nterms is not None
+
     def handle(self, with_transform=True, gated=False):
         """The loaded model (created on first use: needs the GPU).  with_transform=False: the variant whose prior
         transform is the identity (a route that pairs this model's likelihood with ``identity_transform``).  gated=True:
-        the variant with the t-region test (compiled and loaded on first gated use; it runs in a gated refill only)."""
+        the variant with the t-region test (compiled and loaded on first gated use; it runs in a gated refill only).  A summed
+        model (``nterms``) loads its own programs under its own keys."""
         tr = bool(with_transform and self.has_transform)
         key = (tr, True) if gated else tr
+        if self.summed:
+            key = (tr, bool(gated), "sum")
         h = self._handles.get(key)
         if h is None:
             if gated:
-                code = compile_model(self.source, tr, gated=True)
+                code = compile_model(self.source, tr, gated=True, summed=self.summed)
             else:
-                code = self.code if tr == self.has_transform else compile_model(self.source, tr)
-            h = self._handles[key] = _Handle(code, self.ndim, tr, self.aux, gated=gated)
+                code = self.code if tr == self.has_transform else compile_model(self.source, tr, summed=self.summed)
+            if self.summed:
+                h = _Handle(code, self.ndim, tr, self.aux, gated=gated, nterms=self.nterms)
+            else:
+                h = _Handle(code, self.ndim, tr, self.aux, gated=gated)
+            self._handles[key] = h
         return h.handle
 
     def close(self):

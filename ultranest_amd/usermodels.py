@@ -6,6 +6,16 @@
   funnel      examples/testfunnel.py: theta0 = log10 sigma with its own prior (x * 6 - 3), the rest x * 20 - 10; the data vector
               is the model's aux array
   gauss       docs/gauss.py:25-27 with the centres in aux (identity transform there; an affine one optionally)
+
+Likelihoods summed over data terms (``DeviceModel(..., nterms=K)``: one wave per row, the lanes split the terms), each with a
+default-form twin that computes the same terms in a serial loop k = 0..K-1 inside ``mlf_user_loglike``:
+
+  linear_sum     weighted least squares of a linear model: aux = design matrix X[k, j] (K x d), data y_k, weights
+                 w_k = 1 / sigma_k (the inverse is stored: nothing is divided on the device).  m = sum_j p_j X_kj from 0.0 in
+                 ascending j, r = (y_k - m) * w_k, term = -0.5 * r * r: only +, - and *, so numpy restates every term bit for bit
+  staircase_sum  term = -floor(fabs(p[k % d] - c_k) * 8.0): every term is a small integer, so every summation order gives the
+                 same bits and the summed model equals its twin bit for bit -- whole sampler runs can be compared between
+                 the two forms without a threshold decision hanging on a last bit
 """
 import numpy as np
 
@@ -92,3 +102,89 @@ def gauss_centers(ndim, sigma=0.1):
 def gauss(ndim, sigma=0.1, affine=False):
     return DeviceModel(ndim, GAUSS_LOGLIKE % float(sigma), AFFINE_TRANSFORM if affine else None,
                        aux=gauss_centers(ndim, sigma), name="gauss%d" % ndim)
+
+
+LINEAR_TERM = r"""
+#define MLF_LINEAR_K %dLL
+__device__ inline double mlf_linear_term(const double *p, int d, const double *aux, long long k) {
+  const double *x = aux + k * d;
+  double m = 0.0;
+  for (int j = 0; j < d; ++j) m = m + p[j] * x[j];
+  const double r = (aux[MLF_LINEAR_K * d + k] - m) * aux[MLF_LINEAR_K * d + MLF_LINEAR_K + k];
+  return -0.5 * r * r;
+}
+"""
+
+STAIRCASE_TERM = r"""
+#define MLF_STAIRCASE_K %dLL
+__device__ inline double mlf_staircase_term(const double *p, int d, const double *aux, long long k) {
+  return -floor(fabs(p[(int)(k %% d)] - aux[k]) * 8.0);
+}
+"""
+
+# the two forms around a term function NAME(p, d, aux, k) with K terms
+SUMMED_LOGLIKE = r"""
+__device__ double mlf_user_loglike_term(const double *p, int d, const double *aux, long long naux, long long k) {
+  return %(name)s(p, d, aux, k);
+}
+"""
+
+TWIN_LOGLIKE = r"""
+__device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux) {
+  double s = 0.0;
+  for (long long k = 0; k < %(K)s; ++k) s = s + %(name)s(p, d, aux, k);
+  return s;
+}
+"""
+
+
+def _two_forms(term_source, name, K, ndim, ndata, aux, affine, summed, label):
+    if summed:
+        source = term_source % ndata + SUMMED_LOGLIKE % dict(name=name)
+    else:
+        source = term_source % ndata + TWIN_LOGLIKE % dict(name=name, K=K)
+    return DeviceModel(ndim, source, AFFINE_TRANSFORM if affine else None, aux=aux,
+                       name="%s%s%dx%d" % (label, "_sum" if summed else "_twin", ndim, ndata),
+                       nterms=int(ndata) if summed else None)
+
+
+def linear_data(ndim, ndata, seed=1):
+    """(X (ndata, ndim), y (ndata), w (ndata) = 1 / sigma) of linear_sum and its twin"""
+    rs = np.random.RandomState(seed)
+    X = rs.normal(size=(ndata, ndim))
+    sigma = rs.uniform(0.5, 2.0, size=ndata)
+    y = X.dot(rs.normal(size=ndim)) + sigma * rs.normal(size=ndata)
+    return X, y, 1.0 / sigma
+
+
+def linear_aux(ndim, ndata, seed=1):
+    X, y, w = linear_data(ndim, ndata, seed)
+    return np.concatenate([X.ravel(), y, w])
+
+
+def linear_sum(ndim, ndata, seed=1, affine=False):
+    """summed form: K = ndata terms, one wave per row"""
+    return _two_forms(LINEAR_TERM, "mlf_linear_term", "MLF_LINEAR_K", ndim, ndata, linear_aux(ndim, ndata, seed), affine, True,
+                      "linear")
+
+
+def linear_twin(ndim, ndata, seed=1, affine=False):
+    """default form of linear_sum: the same terms, k = 0..K-1 serially in one thread per row"""
+    return _two_forms(LINEAR_TERM, "mlf_linear_term", "MLF_LINEAR_K", ndim, ndata, linear_aux(ndim, ndata, seed), affine, False,
+                      "linear")
+
+
+def staircase_data(ndim, ndata, seed=1, affine=False):
+    """the centres c_k, drawn where the parameters live (the cube, or the affine transform's [-10, 10))"""
+    c = np.random.RandomState(seed).uniform(size=ndata)
+    return c * 20.0 - 10.0 if affine else c
+
+
+def staircase_sum(ndim, ndata, seed=1, affine=False):
+    return _two_forms(STAIRCASE_TERM, "mlf_staircase_term", "MLF_STAIRCASE_K", ndim, ndata,
+                      staircase_data(ndim, ndata, seed, affine), affine, True, "staircase")
+
+
+def staircase_twin(ndim, ndata, seed=1, affine=False):
+    return _two_forms(STAIRCASE_TERM, "mlf_staircase_term", "MLF_STAIRCASE_K", ndim, ndata,
+                      staircase_data(ndim, ndata, seed, affine), affine, False, "staircase")
