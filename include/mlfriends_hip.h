@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MLF_ABI_VERSION 3
+#define MLF_ABI_VERSION 4
 
 #define MLF_E_BADARG 1      /* null pointer, zero dimension, inconsistent sizes            */
 #define MLF_E_DIM 2         /* dimensionality above MLF_MAX_DIM                            */
@@ -597,14 +597,38 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
  *                          model runs wherever a default one does.
  *   MLF_USERMODEL_SUM_TREGION  summed and gated (-DMLF_USER_SUM=1 -DMLF_USER_TREGION=1): entry mlf_user_rows_sum_tregion
  *                          (nterms, then the gate's five parameters); runs where MLF_USERMODEL_TREGION runs.
- * A summed code object is loaded with mlf_usermodel_create_sum (variant MLF_USERMODEL_SUM or _SUM_TREGION, nterms >= 1;
- * everything else as create_variant, which returns MLF_E_BADARG for these two variants). */
+ *   MLF_USERMODEL_SUMS     several sums and a final function (-DMLF_USER_SUM=1 -DMLF_USER_NSUMS=M, 1 <= M <=
+ *                          MLF_USERMODEL_MAX_SUMS, a constant of the program).  The source defines, instead of
+ *                          mlf_user_loglike_term,
+ *                            __device__ void mlf_user_loglike_terms(const double *p, int d, const double *aux, long long naux,
+ *                                                                   long long k, double *t);
+ *                            __device__ double mlf_user_loglike_finish(const double *s, int nsums, const double *p, int d,
+ *                                                                      const double *aux, long long naux);
+ *                          terms writes all M entries of t for data index k (t is not pre-set), s_j = sum over k of t_j(k), and
+ *                          L = finish(s, M, p, ...).  Each accumulator j follows, independently, exactly the order of
+ *                          MLF_USERMODEL_SUM (per lane from 0.0 in ascending k, then the six exchange steps); a lane without a
+ *                          term never calls terms and keeps 0.0; every lane calls finish with the same M values (a pure
+ *                          function of its arguments) and lane 0's result is L; a row outside the mask or the gate calls
+ *                          neither function and gets -inf.  Entry mlf_user_rows_sums, the parameters of mlf_user_rows_sum; runs
+ *                          wherever a default model does.
+ *   MLF_USERMODEL_SUMS_TREGION  the same, gated: entry mlf_user_rows_sums_tregion, the parameters of
+ *                          mlf_user_rows_sum_tregion; runs where MLF_USERMODEL_TREGION runs.
+ * A summed code object is loaded with mlf_usermodel_create_sum (variant MLF_USERMODEL_SUM, _SUM_TREGION, _SUMS or
+ * _SUMS_TREGION, nterms >= 1; everything else as create_variant, which returns MLF_E_BADARG for these four variants).  The two
+ * _SUMS variants are compiled with mlf_usermodel_compile_sums (nsums = M; MLF_E_BADARG for any other variant and for M outside
+ * 1 ... MLF_USERMODEL_MAX_SUMS; compile_variant returns MLF_E_BADARG for them); M is part of the program, so create_sum and the
+ * launches take no further argument. */
 #define MLF_USERMODEL_DEFAULT 0
 #define MLF_USERMODEL_TREGION 1
 #define MLF_USERMODEL_SUM 2
 #define MLF_USERMODEL_SUM_TREGION 3
+#define MLF_USERMODEL_SUMS 4
+#define MLF_USERMODEL_SUMS_TREGION 5
+#define MLF_USERMODEL_MAX_SUMS 8
 int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant,
                                   void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap);
+int mlf_usermodel_compile_sums(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
+                               void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap);
 int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int has_transform, int variant,
                                  const double *aux, size_t naux, mlf_usermodel **out);
 int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,

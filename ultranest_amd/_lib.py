@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmlfriends_hip.so")
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _c_double_p = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -135,6 +135,7 @@ SIGNATURES = {
     "mlf_region_set_tregion_center": [_vp, _vp],
     "mlf_region_clear_tregion": [_vp],
     "mlf_usermodel_compile_variant": [ctypes.c_char_p, ctypes.c_char_p, _int, _int, _vp, _sz, _vp, _vp, _sz],
+    "mlf_usermodel_compile_sums": [ctypes.c_char_p, ctypes.c_char_p, _int, _int, _int, _vp, _sz, _vp, _vp, _sz],
     "mlf_usermodel_create_variant": [_vp, _sz, _sz, _int, _int, _vp, _sz, _vp],
     "mlf_usermodel_create_sum": [_vp, _sz, _sz, _int, _int, _sz, _vp, _sz, _vp],
     "mlf_walkers_finish_user": [_vp, _dbl, _vp, ctypes.c_int64, _vp],

@@ -28,8 +28,10 @@ struct mlf_usermodel {
   hipFunction_t fn = nullptr;
   int d = 0;
   bool has_transform = false;
-  bool gated = false;   // the MLF_USERMODEL_TREGION / _SUM_TREGION variants: the kernel takes the gate's five parameters as well
-  bool summed = false;  // the MLF_USERMODEL_SUM / _SUM_TREGION variants: one wave per row, nterms behind the first eight parameters
+  bool gated = false;   // the MLF_USERMODEL_TREGION / _SUM_TREGION / _SUMS_TREGION variants: the kernel takes the gate's five
+                        // parameters as well
+  bool summed = false;  // the MLF_USERMODEL_SUM / _SUM_TREGION / _SUMS / _SUMS_TREGION variants: one wave per row, nterms behind
+                        // the first eight parameters (the number of sums is baked into a _SUMS program)
   long long nterms = 0;
   long long naux = 0;
   DevBuf aux;
@@ -151,6 +153,10 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
 
 namespace {
 
+bool variant_gated(int v) { return v == MLF_USERMODEL_TREGION || v == MLF_USERMODEL_SUM_TREGION || v == MLF_USERMODEL_SUMS_TREGION; }
+bool variant_multi(int v) { return v == MLF_USERMODEL_SUMS || v == MLF_USERMODEL_SUMS_TREGION; }
+bool variant_summed(int v) { return v == MLF_USERMODEL_SUM || v == MLF_USERMODEL_SUM_TREGION || variant_multi(v); }
+
 // the checks every create entry makes before it touches the device
 int check_create_args(const void *code, size_t nbytes, size_t d) {
   if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
@@ -167,12 +173,13 @@ int load_model(const void *code, size_t d, int has_transform, int variant, size_
   mlf_usermodel *m = new mlf_usermodel();
   m->d = (int)d;
   m->has_transform = has_transform != 0;
-  m->gated = variant == MLF_USERMODEL_TREGION || variant == MLF_USERMODEL_SUM_TREGION;
-  m->summed = variant == MLF_USERMODEL_SUM || variant == MLF_USERMODEL_SUM_TREGION;
+  m->gated = variant_gated(variant);
+  m->summed = variant_summed(variant);
   m->nterms = (long long)nterms;
   m->naux = (long long)naux;
-  const char *entry = m->summed ? (m->gated ? "mlf_user_rows_sum_tregion" : "mlf_user_rows_sum")
-                                : (m->gated ? "mlf_user_rows_tregion" : "mlf_user_rows");
+  const char *entry = variant_multi(variant) ? (m->gated ? "mlf_user_rows_sums_tregion" : "mlf_user_rows_sums")
+                      : m->summed            ? (m->gated ? "mlf_user_rows_sum_tregion" : "mlf_user_rows_sum")
+                                             : (m->gated ? "mlf_user_rows_tregion" : "mlf_user_rows");
   hipError_t e = hipModuleLoadData(&m->module, code);
   if (e == hipSuccess && hipModuleGetFunction(&m->fn, m->module, entry) != hipSuccess) {
     // the variants' entries differ in name: this code object was compiled as the other one (or is no user model at all)
@@ -194,24 +201,11 @@ int load_model(const void *code, size_t d, int has_transform, int variant, size_
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mlf_usermodel_compile(const char *source, const char *include_dir, int has_transform, void *code_out, size_t code_cap,
-                          size_t *code_size, char *log, size_t log_cap) {
-  return mlf_usermodel_compile_variant(source, include_dir, has_transform, MLF_USERMODEL_DEFAULT, code_out, code_cap, code_size,
-                                       log, log_cap);
-}
-
-int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant, void *code_out,
-                                  size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION && variant != MLF_USERMODEL_SUM &&
-      variant != MLF_USERMODEL_SUM_TREGION)
-    return fail_arg(MLF_E_BADARG, "unknown user-model variant");
-  const bool v_gated = variant == MLF_USERMODEL_TREGION || variant == MLF_USERMODEL_SUM_TREGION;
-  const bool v_summed = variant == MLF_USERMODEL_SUM || variant == MLF_USERMODEL_SUM_TREGION;
+// hiprtc on `source` + the wrapper header as `variant` (checked by the caller); nsums: 0 unless the variant is a _SUMS one
+int compile_program(const char *source, const char *include_dir, int has_transform, int variant, int nsums, void *code_out,
+                    size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
+  const bool v_gated = variant_gated(variant);
+  const bool v_summed = variant_summed(variant);
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
@@ -222,10 +216,13 @@ int mlf_usermodel_compile_variant(const char *source, const char *include_dir, i
   const Rtc &r = g_rtc;
   const std::string src = std::string(source) + "\n#include \"mlf_user_rows.hpp\"\n";
   const std::string inc = std::string("-I") + include_dir;
-  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
-                        has_transform ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
-                        v_gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
-                        v_summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0"};
+  const std::string sums = "-DMLF_USER_NSUMS=" + std::to_string(nsums);
+  // (a _SUMS variant adds its one option behind the others: the other variants' programs are compiled as they were)
+  const char *opts[9] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
+                         has_transform ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
+                         v_gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
+                         v_summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0", sums.c_str()};
+  const int nopts = variant_multi(variant) ? 9 : 8;
   hiprtcProgram prog = nullptr;
   hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
   if (res != HIPRTC_SUCCESS) {
@@ -233,7 +230,7 @@ int mlf_usermodel_compile_variant(const char *source, const char *include_dir, i
     put_log(log, log_cap, msg);
     return fail_arg(MLF_E_COMPILE, msg.c_str());
   }
-  res = r.compile(prog, (int)(sizeof opts / sizeof opts[0]), opts);
+  res = r.compile(prog, nopts, opts);
   if (res != HIPRTC_SUCCESS) {
     std::string text = std::string("hiprtcCompileProgram: ") + r.error_string(res);
     size_t nlog = 0;
@@ -264,6 +261,37 @@ int mlf_usermodel_compile_variant(const char *source, const char *include_dir, i
   return rc;
 }
 
+}  // namespace
+
+extern "C" {
+
+int mlf_usermodel_compile(const char *source, const char *include_dir, int has_transform, void *code_out, size_t code_cap,
+                          size_t *code_size, char *log, size_t log_cap) {
+  return mlf_usermodel_compile_variant(source, include_dir, has_transform, MLF_USERMODEL_DEFAULT, code_out, code_cap, code_size,
+                                       log, log_cap);
+}
+
+int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant, void *code_out,
+                                  size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
+  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (variant_multi(variant))
+    return fail_arg(MLF_E_BADARG, "a user-model variant with several sums needs their number: mlf_usermodel_compile_sums");
+  if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION && variant != MLF_USERMODEL_SUM &&
+      variant != MLF_USERMODEL_SUM_TREGION)
+    return fail_arg(MLF_E_BADARG, "unknown user-model variant");
+  return compile_program(source, include_dir, has_transform, variant, 0, code_out, code_cap, code_size, log, log_cap);
+}
+
+int mlf_usermodel_compile_sums(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
+                               void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
+  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!variant_multi(variant))
+    return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_sums: the variant must be MLF_USERMODEL_SUMS or MLF_USERMODEL_SUMS_TREGION");
+  if (nsums < 1 || nsums > MLF_USERMODEL_MAX_SUMS)
+    return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_sums: nsums must be 1 to 8");
+  return compile_program(source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log, log_cap);
+}
+
 int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_transform, const double *aux, size_t naux,
                          mlf_usermodel **out) {
   return mlf_usermodel_create_variant(code, nbytes, d, has_transform, MLF_USERMODEL_DEFAULT, aux, naux, out);
@@ -273,7 +301,7 @@ int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int 
                                  size_t naux, mlf_usermodel **out) {
   if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
-  if (variant == MLF_USERMODEL_SUM || variant == MLF_USERMODEL_SUM_TREGION)
+  if (variant_summed(variant))
     return fail_arg(MLF_E_BADARG, "a summed user-model variant needs its number of terms: mlf_usermodel_create_sum");
   if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION)
     return fail_arg(MLF_E_BADARG, "unknown user-model variant");
@@ -285,8 +313,8 @@ int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_
                              const double *aux, size_t naux, mlf_usermodel **out) {
   if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
-  if (variant != MLF_USERMODEL_SUM && variant != MLF_USERMODEL_SUM_TREGION)
-    return fail_arg(MLF_E_BADARG, "mlf_usermodel_create_sum: the variant must be MLF_USERMODEL_SUM or MLF_USERMODEL_SUM_TREGION");
+  if (!variant_summed(variant))
+    return fail_arg(MLF_E_BADARG, "mlf_usermodel_create_sum: the variant must be MLF_USERMODEL_SUM, _SUM_TREGION, _SUMS or _SUMS_TREGION");
   if (nterms == 0 || nterms > 0x7fffffffffffffffull) return fail_arg(MLF_E_BADARG, "a summed user model has at least one term");
   if (int rc = check_create_args(code, nbytes, d)) return rc;
   return load_model(code, d, has_transform, variant, nterms, aux, naux, out);

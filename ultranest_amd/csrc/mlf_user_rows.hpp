@@ -54,6 +54,27 @@
 // L therefore does not depend on the row's place in the batch, the batch size, the mask or the route; a NaN term gives NaN,
 // -inf terms give -inf.  LDS per wave: (p buffer ? 2 : 1) * d * 8 bytes (mlf_user_rows_sum_lds_bytes; at most 16 KiB at
 // MLF_MAX_DIM = 1024, so there is no direct form and no threshold in d).
+//
+// Several sums and a final function (MLF_USER_SUM=1 with MLF_USER_NSUMS=M, 1 <= M <= 8, a compile-time constant; its own code
+// objects: mlf_user_rows_sums and, with MLF_USER_TREGION=1, mlf_user_rows_sums_tregion, with the parameter lists of the summed
+// entries, 9 and 14).  The user's source defines, instead of mlf_user_loglike_term,
+//
+//   __device__ void mlf_user_loglike_terms(const double *p, int d, const double *aux, long long naux, long long k, double *t);
+//   __device__ double mlf_user_loglike_finish(const double *s, int nsums, const double *p, int d, const double *aux, long long naux);
+//
+// terms writes all M entries t[0..M) for data index k (t is not pre-set: an entry left unwritten is undefined); finish receives
+// the M sums s_j = sum over k of t_j(k), the row's p and the data, and returns L.  M = 1 is a function of one sum; per-row
+// constants go into term 0 or into finish.  Everything but the sum itself is the summed kernel above, unchanged (and without
+// MLF_USER_NSUMS the summed entries are the programs they were).  The order contract, extended:
+//   each sum      accumulator j follows, independently of the others, exactly the order of the single-sum form: lane l starts
+//                 from s_j = 0.0 and adds t_j(k) for k = l, l + 64, ... < nterms, ascending, one plain addition each; then the
+//                 six exchange steps 32, 16, 8, 4, 2, 1, each setting every lane's s_j to s_j + s_j(l xor m);
+//   no term       a lane without a term (nterms < 64) never calls terms; its accumulators stay 0.0;
+//   finish        after the exchange all lanes hold the same M values; every lane calls finish with them (it must be a pure
+//                 function of its arguments) and lane 0's result is L;
+//   not called    a row outside the membership mask, or one that fails the t-region gate, calls neither function: L = -inf.
+// A NaN term of accumulator j reaches finish as NaN in s[j] only.  The accumulators and t live in registers (M is a constant and
+// every loop over j is unrolled).
 #pragma once
 
 #define MLF_USER_ROWS_LDS_BUDGET 65536
@@ -228,7 +249,14 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const doubl
 
 #else  // MLF_USER_SUM
 
+#ifdef MLF_USER_NSUMS
+static_assert(MLF_USER_NSUMS >= 1 && MLF_USER_NSUMS <= 8, "MLF_USER_NSUMS: 1 to 8 sums");
 #if MLF_USER_TREGION
+#define MLF_USER_SUM_ENTRY mlf_user_rows_sums_tregion
+#else
+#define MLF_USER_SUM_ENTRY mlf_user_rows_sums
+#endif
+#elif MLF_USER_TREGION
 #define MLF_USER_SUM_ENTRY mlf_user_rows_sum_tregion
 #else
 #define MLF_USER_SUM_ENTRY mlf_user_rows_sum
@@ -281,6 +309,26 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(const double
     double *dst = p + i * d;
     for (int e = lane; e < d; e += 64) dst[e] = b[e];
   }
+#ifdef MLF_USER_NSUMS
+  double s = neg_inf();   // L: the finish function of the sums
+  if (L != nullptr && pass) {
+    double acc[MLF_USER_NSUMS];   // registers: every loop over j is unrolled
+#pragma unroll
+    for (int j = 0; j < MLF_USER_NSUMS; ++j) acc[j] = 0.0;
+    for (long long k = lane; k < nterms; k += 64) {
+      double t[MLF_USER_NSUMS];   // not pre-set: the terms function writes all of it
+      mlf_user_loglike_terms(b, d, aux, naux, k, t);
+#pragma unroll
+      for (int j = 0; j < MLF_USER_NSUMS; ++j) acc[j] = acc[j] + t[j];
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+      for (int j = 0; j < MLF_USER_NSUMS; ++j) acc[j] = acc[j] + __shfl_xor(acc[j], m);
+    }
+    s = mlf_user_loglike_finish(acc, MLF_USER_NSUMS, b, d, aux, naux);   // every lane, the same arguments; lane 0's is L
+  }
+#else
   double s = neg_inf();
   if (L != nullptr && pass) {
     s = 0.0;
@@ -288,6 +336,7 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(const double
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m);
   }
+#endif
   if (lane == 0) {
     if (L != nullptr) L[i] = s;
 #if MLF_USER_TREGION

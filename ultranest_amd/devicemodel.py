@@ -5,7 +5,7 @@ The GPU counterpart of the reference's compiled-language likelihoods (reference 
 device functions, the package compiles them at run time for gfx950 (hiprtc) around one wrapper kernel
 (``csrc/mlf_user_rows.hpp``) and hands back a pair of vectorized callbacks::
 
-    model = DeviceModel(ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None)
+    model = DeviceModel(ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None)
     model.loglike(theta)    # (n, ndim) -> (n,)       vectorized callback, evaluated on the GPU
     model.transform(u)      # (n, ndim) -> (n, ndim)  vectorized callback (identity without a transform source)
 
@@ -74,8 +74,49 @@ In numpy (sequential additions; ``np.sum`` is pairwise and is NOT this order)::
     L = s[0]
 
 So ``L`` does not depend on the row's position in the batch, the batch size, the membership mask or the route; a NaN term
-gives NaN; ``-inf`` terms give ``-inf``.  A non-additive tail -- a final function of the sum, per-row constants added once --
-is out of scope: constants can live in term 0.
+gives NaN; ``-inf`` terms give ``-inf``.  Per-row constants can live in term 0; a likelihood that is a FUNCTION of one or more
+sums uses the next form.
+
+Several sums and a final function (``nterms=K, nsums=M``)
+---------------------------------------------------------
+A profiled or marginalised amplitude (``L`` a function of ``sum y^2/sigma^2``, ``sum y f/sigma^2``, ``sum f^2/sigma^2``), a
+marginalised noise level (``-(K/2) log sum r^2``), a Poisson fit with a free normalisation: a handful of sums over the data,
+then a few scalar operations.  With ``nsums=M`` (a Python int, 1 <= M <= 8; it requires ``nterms``) the likelihood source
+defines, INSTEAD of ``mlf_user_loglike_term``::
+
+    __device__ void   mlf_user_loglike_terms(const double *p, int d, const double *aux, long long naux, long long k, double *t);
+    __device__ double mlf_user_loglike_finish(const double *s, int nsums, const double *p, int d, const double *aux, long long naux);
+
+``terms`` writes all M entries ``t[0..M)`` for data index ``k`` (the kernel does not pre-set ``t``: an entry the function
+leaves unwritten is undefined); ``finish`` receives the M sums, the row's ``p`` and the data and returns ``L``.  ``nsums=1`` is
+a function of one sum.  Per-row constants go into term 0 or into ``finish``.  M is a constant of the program (the accumulators
+live in registers); the programs are compiled with ``-DMLF_USER_SUM=1 -DMLF_USER_NSUMS=M`` under their own cache keys (entries
+``mlf_user_rows_sums`` / ``mlf_user_rows_sums_tregion``) and loaded through ``mlf_usermodel_create_sum`` as variants 4 and 5;
+everything else -- transform, ``aux``, callbacks, ``eval_dev``, ``device_route``, every route -- is that of a summed model.
+
+The order contract extends the one above and is part of the interface:
+
+* each accumulator ``j`` follows, independently, exactly the order of the single-sum form: lane ``l`` starts from
+  ``s_j = 0.0`` and adds ``t_j(k)`` for ``k = l, l+64, ... < K`` in ascending order, one plain addition each; then the six
+  exchange steps with lane distances 32, 16, 8, 4, 2, 1, each setting every lane's ``s_j`` to ``s_j + s_j(l xor m)``;
+* a lane with no term (``K < 64``) never calls ``terms``; its accumulators stay 0.0;
+* after the exchange all lanes hold the same M values; ``finish`` is called by every lane with those values (it must be a
+  pure function of its arguments), and lane 0's result is ``L``;
+* a row outside the membership mask, or one that fails the t-region gate, calls neither function and gets ``L = -inf``.
+
+In numpy::
+
+    s = np.zeros((M, 64))
+    for k in range(K): s[:, k % 64] += t[:, k]
+    for m in (32, 16, 8, 4, 2, 1): s = s + s[:, np.arange(64) ^ m]
+    L = finish(s[:, 0])
+
+A NaN term of accumulator ``j`` reaches ``finish`` as NaN in ``s[j]`` only.  ``usermodels.amplitude_sum`` (M = 3, a profiled
+amplitude) and ``usermodels.staircase3_sum`` are examples, each with a default-form twin.  Measured at d = 10
+(``scripts/multisum_model_bench.py``, ``profiles/multisum_model_bench.json``): ``amplitude_sum`` takes 0.98 to 1.03 times the
+time of the single-sum ``linear_sum`` on the same data at every shape (two more accumulators and the finish do not show), and
+is 29 (1024 terms) and 49 (16384 terms) times faster than its twin at 1024 rows, 4.2 and 2.5 times at 16384 rows; no crossover
+up to 16384 rows per call, the largest count measured -- "which form" above applies unchanged.
 
 Which form.  Measured with ``usermodels.linear_sum`` against its twin at d = 10 (``scripts/summed_model_bench.py``,
 ``profiles/summed_model_bench.json``): at 1024 rows the summed form is 29.5 times faster with 1024 terms and 35.5 times with
@@ -101,8 +142,10 @@ INCLUDE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 HEADER = os.path.join(INCLUDE_DIR, "mlf_user_rows.hpp")
 GATE_HEADER = os.path.join(INCLUDE_DIR, "mlf_tregion_dev.hpp")      # included by the gated variant only
 VARIANT_DEFAULT, VARIANT_TREGION, VARIANT_SUM, VARIANT_SUM_TREGION = 0, 1, 2, 3     # MLF_USERMODEL_* of include/mlfriends_hip.h
-# what mlf_usermodel_compile passes to hiprtc besides -I, -DMLF_USER_HAS_TRANSFORM, -DMLF_USER_TREGION and -DMLF_USER_SUM (part
-# of the cache key)
+VARIANT_SUMS, VARIANT_SUMS_TREGION = 4, 5
+MAX_SUMS = 8                                                                        # MLF_USERMODEL_MAX_SUMS
+# what mlf_usermodel_compile passes to hiprtc besides -I, -DMLF_USER_HAS_TRANSFORM, -DMLF_USER_TREGION, -DMLF_USER_SUM and (with
+# nsums) -DMLF_USER_NSUMS (part of the cache key)
 COMPILE_OPTIONS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off")
 MLF_E_COMPILE = 5
 
@@ -118,7 +161,20 @@ class DeviceModelCompileError(RuntimeError):
         RuntimeError.__init__(self, "the device model did not compile:\n" + log)
 
 
-def _cache_key(source, has_transform, gated=False, summed=False):
+def _check_nsums(nsums, summed):
+    """nsums as an int (None stays None); ValueError naming ``nsums`` otherwise.  No library call."""
+    if nsums is None:
+        return None
+    if isinstance(nsums, bool) or not isinstance(nsums, (int, np.integer)):
+        raise ValueError("nsums must be an integer (the number of sums of the summed form), got %r" % (nsums,))
+    if not 1 <= nsums <= MAX_SUMS:
+        raise ValueError("nsums must be 1 to %d, got %d" % (MAX_SUMS, nsums))
+    if not summed:
+        raise ValueError("nsums needs the summed form: give nterms (the number of data terms) as well")
+    return int(nsums)
+
+
+def _cache_key(source, has_transform, gated=False, summed=False, nsums=None):
     h = hashlib.sha256()
     with open(HEADER, "rb") as fh:
         header = fh.read()
@@ -129,18 +185,26 @@ def _cache_key(source, has_transform, gated=False, summed=False):
             header += fh.read()
     if summed:
         options += " sum"
+    if nsums is not None:
+        options += " sums=%d" % nsums
     for part in (source.encode(), b"\0", options.encode(), b"\0", header):
         h.update(part)
     return h.hexdigest()
 
 
-def compile_model(source, has_transform, gated=False, summed=False):
+def compile_model(source, has_transform, gated=False, summed=False, nsums=None):
     """The gfx950 code object (bytes) of `source` + the wrapper kernel; cached per process.  gated: the variant with the
     t-region test between transform and likelihood (module docstring), another program under its own key.  summed: the
-    one-wave-per-row form around ``mlf_user_loglike_term`` (module docstring), two more programs under their own keys."""
+    one-wave-per-row form around ``mlf_user_loglike_term`` (module docstring), two more programs under their own keys.
+    nsums=M (with summed): M sums and a final function (``mlf_user_loglike_terms`` / ``_finish``), two more programs per M."""
     global compile_calls
-    key = _cache_key(source, has_transform, gated, summed)
-    variant = (VARIANT_TREGION if gated else VARIANT_DEFAULT) + (VARIANT_SUM if summed else 0)
+    nsums = _check_nsums(nsums, summed)
+    if nsums is None:
+        key = _cache_key(source, has_transform, gated, summed)
+        variant = (VARIANT_TREGION if gated else VARIANT_DEFAULT) + (VARIANT_SUM if summed else 0)
+    else:
+        key = _cache_key(source, has_transform, gated, summed, nsums=nsums)
+        variant = VARIANT_SUMS_TREGION if gated else VARIANT_SUMS
     code = _code_cache.get(key)
     if code is not None:
         return code
@@ -151,7 +215,10 @@ def compile_model(source, has_transform, gated=False, summed=False):
     for _ in range(2):
         buf = ctypes.create_string_buffer(cap)
         compile_calls += 1
-        if variant != VARIANT_DEFAULT:
+        if nsums is not None:
+            rc = L.mlf_usermodel_compile_sums(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), variant, nsums,
+                                              buf, cap, ctypes.byref(size), log, len(log))
+        elif variant != VARIANT_DEFAULT:
             rc = L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)),
                                                  variant, buf, cap, ctypes.byref(size), log, len(log))
         else:
@@ -193,12 +260,15 @@ class _Callback(object):
 class _Handle(object):
     """One loaded model (``mlf_usermodel``) on the library's device."""
 
-    def __init__(self, code, ndim, has_transform, aux, gated=False, nterms=None):
+    def __init__(self, code, ndim, has_transform, aux, gated=False, nterms=None, nsums=None):
         h = ctypes.c_void_p()
         if nterms is not None:
-            check(_lib.lib().mlf_usermodel_create_sum(code, len(code), int(ndim), int(bool(has_transform)),
-                                                      VARIANT_SUM_TREGION if gated else VARIANT_SUM, int(nterms), ptr(aux),
-                                                      len(aux), ctypes.byref(h)))
+            if nsums is not None:        # (the number of sums is baked into the program: the variant alone names its entry)
+                variant = VARIANT_SUMS_TREGION if gated else VARIANT_SUMS
+            else:
+                variant = VARIANT_SUM_TREGION if gated else VARIANT_SUM
+            check(_lib.lib().mlf_usermodel_create_sum(code, len(code), int(ndim), int(bool(has_transform)), variant,
+                                                      int(nterms), ptr(aux), len(aux), ctypes.byref(h)))
         elif gated:
             check(_lib.lib().mlf_usermodel_create_variant(code, len(code), int(ndim), int(bool(has_transform)),
                                                           VARIANT_TREGION, ptr(aux), len(aux), ctypes.byref(h)))
@@ -227,11 +297,12 @@ class _Handle(object):
 class DeviceModel(object):
     """A likelihood (and optional prior transform) written as HIP device functions (module docstring).  nterms=K: the
     summed form, whose likelihood source defines ``mlf_user_loglike_term`` and whose L is the sum of its K terms in the
-    documented order; a non-additive tail (a function of the sum, per-row constants) is out of scope."""
+    documented order.  nterms=K, nsums=M (1 <= M <= 8): the source defines ``mlf_user_loglike_terms`` (M terms per data
+    index) and ``mlf_user_loglike_finish`` (L from the M sums) instead; each sum follows that order."""
 
     _count = 0
 
-    def __init__(self, ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None):
+    def __init__(self, ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None):
         self.ndim = int(ndim)
         if self.ndim <= 0:
             raise ValueError("ndim must be positive")
@@ -242,12 +313,13 @@ class DeviceModel(object):
                 raise ValueError("nterms must be at least 1, got %d" % nterms)
             nterms = int(nterms)
         self.nterms = nterms
+        self.nsums = _check_nsums(nsums, nterms is not None)
         self.has_transform = transform_source is not None
         self.source = loglike_source if transform_source is None else loglike_source + "\n" + transform_source
         self.aux = np.empty(0) if aux is None else f64(np.ravel(aux)).copy()
         DeviceModel._count += 1
         self.name = name or "DeviceModel%d" % DeviceModel._count
-        self.code = compile_model(self.source, self.has_transform, summed=self.summed)
+        self.code = self._compile(self.has_transform, False)
         self._handles = {}
         self.loglike = _Callback(self, "loglike")
         self.transform = _Callback(self, "transform")
@@ -256,22 +328,29 @@ class DeviceModel(object):
     def summed(self):
         return self.nterms is not None
 
+    def _compile(self, tr, gated):
+        if self.nsums is not None:
+            return compile_model(self.source, tr, gated=gated, summed=True, nsums=self.nsums)
+        return compile_model(self.source, tr, gated=gated, summed=self.summed)
+
     def handle(self, with_transform=True, gated=False):
         """The loaded model (created on first use: needs the GPU).  with_transform=False: the variant whose prior
         transform is the identity (a route that pairs this model's likelihood with ``identity_transform``).  gated=True:
         the variant with the t-region test (compiled and loaded on first gated use; it runs in a gated refill only).  A summed
-        model (``nterms``) loads its own programs under its own keys."""
+        model (``nterms``) loads its own programs under its own keys, and so does one of several sums (``nsums``)."""
         tr = bool(with_transform and self.has_transform)
         key = (tr, True) if gated else tr
         if self.summed:
-            key = (tr, bool(gated), "sum")
+            key = (tr, bool(gated), "sum" if self.nsums is None else "sums")
         h = self._handles.get(key)
         if h is None:
             if gated:
-                code = compile_model(self.source, tr, gated=True, summed=self.summed)
+                code = self._compile(tr, True)
             else:
-                code = self.code if tr == self.has_transform else compile_model(self.source, tr, summed=self.summed)
-            if self.summed:
+                code = self.code if tr == self.has_transform else self._compile(tr, False)
+            if self.nsums is not None:
+                h = _Handle(code, self.ndim, tr, self.aux, gated=gated, nterms=self.nterms, nsums=self.nsums)
+            elif self.summed:
                 h = _Handle(code, self.ndim, tr, self.aux, gated=gated, nterms=self.nterms)
             else:
                 h = _Handle(code, self.ndim, tr, self.aux, gated=gated)

@@ -16,6 +16,17 @@ default-form twin that computes the same terms in a serial loop k = 0..K-1 insid
   staircase_sum  term = -floor(fabs(p[k % d] - c_k) * 8.0): every term is a small integer, so every summation order gives the
                  same bits and the summed model equals its twin bit for bit -- whole sampler runs can be compared between
                  the two forms without a threshold decision hanging on a last bit
+
+Likelihoods of several sums and a final function (``DeviceModel(..., nterms=K, nsums=M)``), each with a default-form twin whose
+``mlf_user_loglike`` adds the same terms serially, k = 0..K-1, into M sums and calls the same finish text:
+
+  amplitude_sum   M = 3: the linear model of linear_sum with its overall amplitude profiled out analytically.  aux as in
+                  linear_data; f_k = X_k . p (from 0.0 in ascending j), a = w_k * y_k, b = w_k * f_k, terms a * a, a * b, b * b
+                  (w^2 y^2, w^2 y f, w^2 f^2: only + and *, so numpy restates every term bit for bit);
+                  L = -0.5 * (s0 - s1 * s1 / s2) - 0.5 * log(s2)
+  staircase3_sum  M = 3: a = fabs(p[k % d] - c_k) on three scales, terms -floor(a * 8), floor(a * 4), -floor(a * 2): small
+                  integers, so every partial sum is exact in any order; L = s0 - s1 * s1 / (1.0 - s2) with s2 <= 0 (+ - * /
+                  only, the denominator is at least 1), so the two forms agree bit for bit
 """
 import numpy as np
 
@@ -188,3 +199,89 @@ def staircase_sum(ndim, ndata, seed=1, affine=False):
 def staircase_twin(ndim, ndata, seed=1, affine=False):
     return _two_forms(STAIRCASE_TERM, "mlf_staircase_term", "MLF_STAIRCASE_K", ndim, ndata,
                       staircase_data(ndim, ndata, seed, affine), affine, False, "staircase")
+
+
+AMPLITUDE_TERMS = r"""
+#define MLF_AMPLITUDE_K %dLL
+__device__ inline void mlf_amplitude_terms(const double *p, int d, const double *aux, long long k, double *t) {
+  const double *x = aux + k * d;
+  double f = 0.0;
+  for (int j = 0; j < d; ++j) f = f + p[j] * x[j];
+  const double w = aux[MLF_AMPLITUDE_K * d + MLF_AMPLITUDE_K + k];
+  const double a = w * aux[MLF_AMPLITUDE_K * d + k], b = w * f;
+  t[0] = a * a;
+  t[1] = a * b;
+  t[2] = b * b;
+}
+__device__ inline double mlf_amplitude_finish(const double *s) {
+  return -0.5 * (s[0] - s[1] * s[1] / s[2]) - 0.5 * log(s[2]);
+}
+"""
+
+STAIRCASE3_TERMS = r"""
+#define MLF_STAIRCASE3_K %dLL
+__device__ inline void mlf_staircase3_terms(const double *p, int d, const double *aux, long long k, double *t) {
+  const double a = fabs(p[(int)(k %% d)] - aux[k]);
+  t[0] = -floor(a * 8.0);
+  t[1] = floor(a * 4.0);
+  t[2] = -floor(a * 2.0);
+}
+__device__ inline double mlf_staircase3_finish(const double *s) {
+  return s[0] - s[1] * s[1] / (1.0 - s[2]);
+}
+"""
+
+# the two forms around NAME_terms(p, d, aux, k, t) and NAME_finish(s) with K terms and M sums
+MULTISUM_LOGLIKE = r"""
+__device__ void mlf_user_loglike_terms(const double *p, int d, const double *aux, long long naux, long long k, double *t) {
+  %(name)s_terms(p, d, aux, k, t);
+}
+__device__ double mlf_user_loglike_finish(const double *s, int nsums, const double *p, int d, const double *aux, long long naux) {
+  return %(name)s_finish(s);
+}
+"""
+
+MULTISUM_TWIN_LOGLIKE = r"""
+__device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux) {
+  double s[%(M)d];
+  for (int j = 0; j < %(M)d; ++j) s[j] = 0.0;
+  for (long long k = 0; k < %(K)s; ++k) {
+    double t[%(M)d];
+    %(name)s_terms(p, d, aux, k, t);
+    for (int j = 0; j < %(M)d; ++j) s[j] = s[j] + t[j];
+  }
+  return %(name)s_finish(s);
+}
+"""
+
+
+def _two_multisum_forms(terms_source, name, K, M, ndim, ndata, aux, affine, summed, label):
+    if summed:
+        source = terms_source % ndata + MULTISUM_LOGLIKE % dict(name=name)
+    else:
+        source = terms_source % ndata + MULTISUM_TWIN_LOGLIKE % dict(name=name, K=K, M=M)
+    return DeviceModel(ndim, source, AFFINE_TRANSFORM if affine else None, aux=aux,
+                       name="%s%s%dx%d" % (label, "_sum" if summed else "_twin", ndim, ndata),
+                       nterms=int(ndata) if summed else None, nsums=M if summed else None)
+
+
+def amplitude_sum(ndim, ndata, seed=1, affine=False):
+    """three sums and a finish: K = ndata terms, one wave per row"""
+    return _two_multisum_forms(AMPLITUDE_TERMS, "mlf_amplitude", "MLF_AMPLITUDE_K", 3, ndim, ndata,
+                               linear_aux(ndim, ndata, seed), affine, True, "amplitude")
+
+
+def amplitude_twin(ndim, ndata, seed=1, affine=False):
+    """default form of amplitude_sum: the same terms, k = 0..K-1 serially in one thread per row, the same finish"""
+    return _two_multisum_forms(AMPLITUDE_TERMS, "mlf_amplitude", "MLF_AMPLITUDE_K", 3, ndim, ndata,
+                               linear_aux(ndim, ndata, seed), affine, False, "amplitude")
+
+
+def staircase3_sum(ndim, ndata, seed=1, affine=False):
+    return _two_multisum_forms(STAIRCASE3_TERMS, "mlf_staircase3", "MLF_STAIRCASE3_K", 3, ndim, ndata,
+                               staircase_data(ndim, ndata, seed, affine), affine, True, "staircase3")
+
+
+def staircase3_twin(ndim, ndata, seed=1, affine=False):
+    return _two_multisum_forms(STAIRCASE3_TERMS, "mlf_staircase3", "MLF_STAIRCASE3_K", 3, ndim, ndata,
+                               staircase_data(ndim, ndata, seed, affine), affine, False, "staircase3")
