@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MLF_ABI_VERSION 4
+#define MLF_ABI_VERSION 5
 
 #define MLF_E_BADARG 1      /* null pointer, zero dimension, inconsistent sizes            */
 #define MLF_E_DIM 2         /* dimensionality above MLF_MAX_DIM                            */
@@ -555,7 +555,8 @@ int mlf_region_first_index_dev(mlf_region *r, const double *d_pts, size_t np, in
  * every other entry point works as before) for gfx950 with -O3 -std=c++17 -ffp-contract=off, followed by
  * `#include "mlf_user_rows.hpp"` (csrc/), which defines the one kernel the library launches (mlf_user_rows).  The user
  * code runs on a shared GPU: it reads aux only within naux, writes nothing but the p row it is handed, and uses no inline
- * assembly.  nparams == d (derived parameters are not covered).
+ * assembly.  Inside every route a p row is d wide; derived parameters (nparams = d + nderived) are the separate derive program
+ * below (MLF_USERMODEL_DERIVED), run on the rows a route hands out.
  *   compile  include_dir: the directory of mlf_user_rows.hpp.  code_out == NULL: size query (*code_size); a buffer of
  *            code_cap < the size returns MLF_E_BADARG with *code_size set.  On MLF_E_COMPILE the hiprtc log (or why hiprtc
  *            could not be loaded) is written to `log` (NUL-terminated, truncated to log_cap).  Needs no GPU.
@@ -617,13 +618,35 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
  * _SUMS_TREGION, nterms >= 1; everything else as create_variant, which returns MLF_E_BADARG for these four variants).  The two
  * _SUMS variants are compiled with mlf_usermodel_compile_sums (nsums = M; MLF_E_BADARG for any other variant and for M outside
  * 1 ... MLF_USERMODEL_MAX_SUMS; compile_variant returns MLF_E_BADARG for them); M is part of the program, so create_sum and the
- * launches take no further argument. */
+ * launches take no further argument.
+ *
+ * Derived parameters (MLF_USERMODEL_DERIVED): output columns computed from a row's parameters (the reference driver's
+ * derived_param_names).  The program is compiled with mlf_usermodel_compile_variant(source, ..., has_transform (ignored),
+ * MLF_USERMODEL_DERIVED, ...) from the model's source followed by a derived source that defines
+ *   __device__ void mlf_user_derived(const double *p, int d, double *q, int nq, const double *aux, long long naux);
+ * (-DMLF_USER_DERIVED=1; the function writes all of q[0..nq) from the row's d transformed parameters and is a pure function of
+ * its arguments; the same contract as every user function).  Its only kernel is mlf_user_derive_rows (csrc/mlf_user_rows.hpp).
+ *   create_derived  loads it (nderived >= 1, d + nderived <= MLF_MAX_DIM; MLF_E_BADARG for a code object without the entry).
+ *                   Such a handle runs in derive, derive_dev and mlf_region_refill_user_derived only; every evaluating entry
+ *                   (eval, eval_dev, the refills, the walkers) returns MLF_E_STATE for it, and the three derive entries return
+ *                   MLF_E_STATE for a handle that is no derive handle.  Destroyed with mlf_usermodel_destroy.
+ *   derive          host arrays: p (n, d) -> out (n, d + nderived), out_i = [p_i | q_i].  Synchronous.
+ *   derive_dev      the same on DEVICE pointers (they must not overlap), enqueued on `stream`.
+ *   derive_lds_bytes  introspection only (tests, benchmarks; no caller needs it to launch anything): the dynamic LDS of one
+ *                   launch, mlf_user_rows_derive_lds_bytes of the header; 0 means the direct form, and is also what invalid
+ *                   arguments (d or nderived of 0 or above MLF_MAX_DIM) return.
+ *   mlf_region_refill_user_derived  mlf_region_refill_user with the derive kernel run on the kept rows after the threshold cut
+ *                   and compaction: out_p has room for capacity rows of d + nderived doubles and receives [p | q]; draws,
+ *                   counts, u, L and the offset are those of mlf_region_refill_user with `model`.  No row inside the refill
+ *                   changes its width.  A region with a t-region set returns MLF_E_STATE (the reference's t-region spans all
+ *                   nparams columns, so its gate would need q before the likelihood: such a batch takes the host sequence). */
 #define MLF_USERMODEL_DEFAULT 0
 #define MLF_USERMODEL_TREGION 1
 #define MLF_USERMODEL_SUM 2
 #define MLF_USERMODEL_SUM_TREGION 3
 #define MLF_USERMODEL_SUMS 4
 #define MLF_USERMODEL_SUMS_TREGION 5
+#define MLF_USERMODEL_DERIVED 6
 #define MLF_USERMODEL_MAX_SUMS 8
 int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant,
                                   void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap);
@@ -633,6 +656,11 @@ int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int 
                                  const double *aux, size_t naux, mlf_usermodel **out);
 int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
                              const double *aux, size_t naux, mlf_usermodel **out);
+int mlf_usermodel_create_derived(const void *code, size_t nbytes, size_t d, size_t nderived, const double *aux, size_t naux,
+                                 mlf_usermodel **out);
+int mlf_usermodel_derive(mlf_usermodel *derive, const double *p, size_t n, double *out);
+int mlf_usermodel_derive_dev(mlf_usermodel *derive, const double *d_p, size_t n, double *d_out, void *stream);
+int mlf_usermodel_derive_lds_bytes(size_t d, size_t nderived);
 int mlf_usermodel_destroy(mlf_usermodel *model);
 int mlf_usermodel_eval(mlf_usermodel *model, const double *u, size_t n, double *p_out, double *L_out);
 int mlf_usermodel_eval_dev(mlf_usermodel *model, const double *d_u, size_t n, const uint8_t *d_member, double *d_p,
@@ -640,6 +668,9 @@ int mlf_usermodel_eval_dev(mlf_usermodel *model, const double *d_u, size_t n, co
 int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
                            mlf_usermodel *model, double *out_u, double *out_p, double *out_L, size_t capacity,
                            size_t *nevaluated, size_t *nkept, uint64_t *next_offset);
+int mlf_region_refill_user_derived(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
+                                   mlf_usermodel *model, mlf_usermodel *derive, double *out_u, double *out_p, double *out_L,
+                                   size_t capacity, size_t *nevaluated, size_t *nkept, uint64_t *next_offset);
 int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, int64_t ringindex, double *rec);
 int mlf_walkers_step_user(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                           uint64_t offset, mlf_usermodel *model, double *rec, uint64_t *next_offset);

@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmlfriends_hip.so")
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _c_double_p = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -138,6 +138,12 @@ SIGNATURES = {
     "mlf_usermodel_compile_sums": [ctypes.c_char_p, ctypes.c_char_p, _int, _int, _int, _vp, _sz, _vp, _vp, _sz],
     "mlf_usermodel_create_variant": [_vp, _sz, _sz, _int, _int, _vp, _sz, _vp],
     "mlf_usermodel_create_sum": [_vp, _sz, _sz, _int, _int, _sz, _vp, _sz, _vp],
+    "mlf_usermodel_create_derived": [_vp, _sz, _sz, _sz, _vp, _sz, _vp],
+    "mlf_usermodel_derive": [_vp, _vp, _sz, _vp],
+    "mlf_usermodel_derive_dev": [_vp, _vp, _sz, _vp, _vp],
+    "mlf_usermodel_derive_lds_bytes": [_sz, _sz],
+    "mlf_region_refill_user_derived": [_vp, _int, _sz, ctypes.c_uint64, ctypes.c_uint64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp,
+                                       _vp],
     "mlf_walkers_finish_user": [_vp, _dbl, _vp, ctypes.c_int64, _vp],
     "mlf_walkers_step_user": [_vp, _dbl, _dbl, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp],
     "mlf_rwalk_create": [_vp, _sz, _sz, _sz],

@@ -226,6 +226,7 @@ struct mlf_region {
   // the driver's parameter-space wrapping ellipsoid (mlf_region_set_tregion): dense d x d matrix, centre, fixed values; the
   // refill calls gate on it while tr_on.  rf_member2: accepted && gate of the batch under evaluation
   mlf::DevBuf tr_A, tr_ctr, tr_fixed, rf_member2;
+  mlf::DevBuf rf_wide;   // the kept rows as [p | q] of a refill with derived parameters (mlf_region_refill_user_derived)
   bool tr_on = false;
   double tr_enlarge = 0.0;
   std::vector<hipEvent_t> events;  // 4 per timed call

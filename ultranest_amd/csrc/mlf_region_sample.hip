@@ -160,10 +160,11 @@ TregionGate region_tregion(const mlf_region *r) {
 // transform and the likelihood of the n rows (p into p_buf, or *prow = rows for the identity; L into L_buf).  With a t-region on
 // the handle, evaluate also fills r->rf_member2 = member && inside(p) (region_tregion): that mask replaces the membership
 // mask from there on and its count is *nevaluated; the choice between the two routes keeps using the region's count.
+// derive (a derive handle, or none): out_p receives the kept rows as [p | q], d + nderived wide (mlf_region_refill_user_derived).
 template <class Evaluate>
 int region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin, Evaluate evaluate,
                   double *out_u, double *out_p, double *out_L, size_t capacity, size_t *nevaluated, size_t *nkept,
-                  uint64_t *next_offset) {
+                  uint64_t *next_offset, const mlf_usermodel *derive = nullptr) {
   *nevaluated = 0;
   *nkept = 0;
   Drawn b;
@@ -213,9 +214,16 @@ int region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed, uin
   kept.scatter(r->rf_L.as<double>(), 1, oL, capacity);
   size_t take = 0;
   CK(kept.count(capacity, &take));
+  size_t pw = (size_t)d;   // width of a row of out_p
+  if (take && derive) {    // derived parameters: [p | q] of the kept rows, the only rows that leave (no row above changes width)
+    pw += (size_t)usermodel_nderived(derive);
+    CK(r->rf_wide.reserve(take * pw * sizeof(double)));   // (the kept rows alone: capacity may be the whole batch)
+    if (int rc = usermodel_derive_rows(derive, op, (long long)take, r->rf_wide.as<double>(), s)) return rc;
+    op = r->rf_wide.as<double>();
+  }
   if (take) {
     CK(hipMemcpyAsync(out_u, ou, take * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s));
-    CK(hipMemcpyAsync(out_p, op, take * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(out_p, op, take * pw * sizeof(double), hipMemcpyDeviceToHost, s));
     CK(hipMemcpyAsync(out_L, oL, take * sizeof(double), hipMemcpyDeviceToHost, s));
     CK(hipStreamSynchronize(s));
   }
@@ -333,6 +341,30 @@ int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t 
   };
   return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
                        next_offset);
+}
+
+int mlf_region_refill_user_derived(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
+                                   mlf_usermodel *model, mlf_usermodel *derive, double *out_u, double *out_p, double *out_L,
+                                   size_t capacity, size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
+  if (!r || !model || !derive || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
+    return fail_arg(MLF_E_BADARG, "null pointer");
+  if (usermodel_nderived(derive) == 0) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+  if (usermodel_dim(derive) != usermodel_dim(model))
+    return fail_arg(MLF_E_BADARG, "user model and its derive program differ in dimensionality");
+  if (r->ready && usermodel_dim(model) != r->d) return fail_arg(MLF_E_BADARG, "user model and region differ in dimensionality");
+  // the reference's t-region spans all nparams columns: its gate would need q before the likelihood (such a batch takes the host
+  // sequence)
+  if (r->tr_on) return fail_arg(MLF_E_STATE, "derived parameters together with a t-region do not run on the device");
+  if (usermodel_gated(model)) return fail_arg(MLF_E_STATE, "user model loaded as MLF_USERMODEL_TREGION, but the region has no t-region");
+  // the evaluation of mlf_region_refill_user without a t-region; region_refill widens the kept rows alone
+  auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
+                      const double **prow) -> int {
+    double *p = usermodel_has_transform(model) ? pbuf : nullptr;
+    if (p) *prow = p;
+    return usermodel_rows(model, rows, n, member, p, Lbuf, s);
+  };
+  return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
+                       next_offset, derive);
 }
 
 }  // extern "C"

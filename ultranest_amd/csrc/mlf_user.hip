@@ -33,6 +33,8 @@ struct mlf_usermodel {
   bool summed = false;  // the MLF_USERMODEL_SUM / _SUM_TREGION / _SUMS / _SUMS_TREGION variants: one wave per row, nterms behind
                         // the first eight parameters (the number of sums is baked into a _SUMS program)
   long long nterms = 0;
+  int nderived = 0;     // the MLF_USERMODEL_DERIVED variant: fn is mlf_user_derive_rows, p (n, d) -> [p | q] (n, d + nderived); such a
+                        // handle runs in the derive entries only
   long long naux = 0;
   DevBuf aux;
   DevBuf hu, hp, hL;   // staging of mlf_usermodel_eval (host arrays)
@@ -107,9 +109,11 @@ namespace mlf {
 int usermodel_dim(const mlf_usermodel *m) { return m->d; }
 bool usermodel_has_transform(const mlf_usermodel *m) { return m->has_transform; }
 bool usermodel_gated(const mlf_usermodel *m) { return m->gated; }
+int usermodel_nderived(const mlf_usermodel *m) { return m->nderived; }
 
 int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
                    hipStream_t s, const TregionGate *gate) {
+  if (m->nderived) return fail_arg(MLF_E_STATE, "a derive handle (mlf_usermodel_create_derived) evaluates nothing: it runs in the derive entries only");
   // the two variants differ in their parameter lists: never launch one with the other's
   if (m->gated != (gate != nullptr))
     return fail_arg(MLF_E_STATE, m->gated ? "user model loaded as the t-region variant: it runs only in a refill with a t-region set"
@@ -149,6 +153,24 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
   return 0;
 }
 
+int usermodel_derive_rows(const mlf_usermodel *m, const double *p, long long n, double *out, hipStream_t s) {
+  if (!m->nderived) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+  if (n <= 0) return 0;
+  const long long blocks = (n + 63) / 64;   // one thread per row, 64 rows per workgroup
+  if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
+  const unsigned lds = mlf_user_rows_derive_lds_bytes(m->d, m->nderived);
+  // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
+  const double *a_p = p;
+  long long a_n = n;
+  int a_d = m->d, a_nq = m->nderived;
+  const double *a_aux = m->aux.as<double>();
+  long long a_naux = m->naux;
+  double *a_out = out;
+  void *args[7] = {&a_p, &a_n, &a_d, &a_nq, &a_aux, &a_naux, &a_out};
+  CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
+  return 0;
+}
+
 }  // namespace mlf
 
 namespace {
@@ -165,9 +187,10 @@ int check_create_args(const void *code, size_t nbytes, size_t d) {
   return 0;
 }
 
-// loads the code object as `variant` (arguments checked by the caller); nterms: 0 unless the variant is a summed one
+// loads the code object as `variant` (arguments checked by the caller); nterms: 0 unless the variant is a summed one; nderived:
+// 0 unless the variant is MLF_USERMODEL_DERIVED
 int load_model(const void *code, size_t d, int has_transform, int variant, size_t nterms, const double *aux, size_t naux,
-               mlf_usermodel **out) {
+               mlf_usermodel **out, size_t nderived = 0) {
   if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   mlf_usermodel *m = new mlf_usermodel();
@@ -176,8 +199,10 @@ int load_model(const void *code, size_t d, int has_transform, int variant, size_
   m->gated = variant_gated(variant);
   m->summed = variant_summed(variant);
   m->nterms = (long long)nterms;
+  m->nderived = (int)nderived;
   m->naux = (long long)naux;
-  const char *entry = variant_multi(variant) ? (m->gated ? "mlf_user_rows_sums_tregion" : "mlf_user_rows_sums")
+  const char *entry = variant == MLF_USERMODEL_DERIVED ? "mlf_user_derive_rows"
+                      : variant_multi(variant) ? (m->gated ? "mlf_user_rows_sums_tregion" : "mlf_user_rows_sums")
                       : m->summed            ? (m->gated ? "mlf_user_rows_sum_tregion" : "mlf_user_rows_sum")
                                              : (m->gated ? "mlf_user_rows_tregion" : "mlf_user_rows");
   hipError_t e = hipModuleLoadData(&m->module, code);
@@ -206,6 +231,7 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
                     size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
   const bool v_gated = variant_gated(variant);
   const bool v_summed = variant_summed(variant);
+  const bool v_derived = variant == MLF_USERMODEL_DERIVED;
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
@@ -217,12 +243,13 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
   const std::string src = std::string(source) + "\n#include \"mlf_user_rows.hpp\"\n";
   const std::string inc = std::string("-I") + include_dir;
   const std::string sums = "-DMLF_USER_NSUMS=" + std::to_string(nsums);
-  // (a _SUMS variant adds its one option behind the others: the other variants' programs are compiled as they were)
+  // (a _SUMS variant adds its one option behind the others, and so does the derive program, which never calls the transform:
+  // the other variants' programs are compiled as they were)
   const char *opts[9] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
-                         has_transform ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
+                         has_transform && !v_derived ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
                          v_gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
-                         v_summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0", sums.c_str()};
-  const int nopts = variant_multi(variant) ? 9 : 8;
+                         v_summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0", v_derived ? "-DMLF_USER_DERIVED=1" : sums.c_str()};
+  const int nopts = variant_multi(variant) || v_derived ? 9 : 8;
   hiprtcProgram prog = nullptr;
   hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
   if (res != HIPRTC_SUCCESS) {
@@ -277,7 +304,7 @@ int mlf_usermodel_compile_variant(const char *source, const char *include_dir, i
   if (variant_multi(variant))
     return fail_arg(MLF_E_BADARG, "a user-model variant with several sums needs their number: mlf_usermodel_compile_sums");
   if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION && variant != MLF_USERMODEL_SUM &&
-      variant != MLF_USERMODEL_SUM_TREGION)
+      variant != MLF_USERMODEL_SUM_TREGION && variant != MLF_USERMODEL_DERIVED)
     return fail_arg(MLF_E_BADARG, "unknown user-model variant");
   return compile_program(source, include_dir, has_transform, variant, 0, code_out, code_cap, code_size, log, log_cap);
 }
@@ -320,6 +347,21 @@ int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_
   return load_model(code, d, has_transform, variant, nterms, aux, naux, out);
 }
 
+int mlf_usermodel_create_derived(const void *code, size_t nbytes, size_t d, size_t nderived, const double *aux, size_t naux,
+                                 mlf_usermodel **out) {
+  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
+  *out = nullptr;
+  if (nderived == 0) return fail_arg(MLF_E_BADARG, "a derive program has at least one derived parameter");
+  if (int rc = check_create_args(code, nbytes, d)) return rc;
+  if (nderived > MLF_MAX_DIM - d) return fail_arg(MLF_E_DIM, "user model: parameters and derived parameters above MLF_MAX_DIM");
+  return load_model(code, d, 0, MLF_USERMODEL_DERIVED, 0, aux, naux, out, nderived);
+}
+
+int mlf_usermodel_derive_lds_bytes(size_t d, size_t nderived) {
+  if (d == 0 || nderived == 0 || d > MLF_MAX_DIM || nderived > MLF_MAX_DIM) return 0;
+  return (int)mlf_user_rows_derive_lds_bytes((int)d, (int)nderived);   // (at most MLF_USER_ROWS_LDS_BUDGET)
+}
+
 int mlf_usermodel_destroy(mlf_usermodel *m) {
   if (!m) return 0;
   // the model's last launches may still be queued (the library's stream, or a caller's stream of eval_dev)
@@ -339,6 +381,7 @@ int mlf_usermodel_destroy(mlf_usermodel *m) {
 
 int mlf_usermodel_eval(mlf_usermodel *m, const double *u, size_t n, double *p_out, double *L_out) {
   if (!m || !u || (!p_out && !L_out)) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (m->nderived) return fail_arg(MLF_E_STATE, "a derive handle (mlf_usermodel_create_derived) evaluates nothing");
   if (n == 0) return 0;
   if (n > 0x7fffffffffffull / (size_t)m->d) return fail_arg(MLF_E_BADARG, "batch too large");
   hipStream_t s = ctx_stream();
@@ -354,6 +397,35 @@ int mlf_usermodel_eval(mlf_usermodel *m, const double *u, size_t n, double *p_ou
   if (p_out) CK(hipMemcpyAsync(p_out, m->hp.p, rows, hipMemcpyDeviceToHost, s));
   if (L_out) CK(hipMemcpyAsync(L_out, m->hL.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
   CK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mlf_usermodel_derive(mlf_usermodel *m, const double *p, size_t n, double *out) {
+  if (!m) return fail_arg(MLF_E_BADARG, "null model");
+  if (!m->nderived) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+  if (n == 0) return 0;
+  if (!p || !out) return fail_arg(MLF_E_BADARG, "null pointer");
+  const size_t w = (size_t)m->d + (size_t)m->nderived;
+  if (n > 0x7fffffffffffull / w) return fail_arg(MLF_E_BADARG, "batch too large");
+  hipStream_t s = ctx_stream();
+  const size_t in_bytes = n * (size_t)m->d * sizeof(double), out_bytes = n * w * sizeof(double);
+  CK(m->hu.reserve(in_bytes));
+  CK(m->hp.reserve(out_bytes));
+  CK(hipMemcpyAsync(m->hu.p, p, in_bytes, hipMemcpyHostToDevice, s));
+  if (int rc = usermodel_derive_rows(m, m->hu.as<double>(), (long long)n, m->hp.as<double>(), s)) return rc;
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(out, m->hp.p, out_bytes, hipMemcpyDeviceToHost, s));
+  CK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mlf_usermodel_derive_dev(mlf_usermodel *m, const double *d_p, size_t n, double *d_out, void *stream) {
+  if (!m) return fail_arg(MLF_E_BADARG, "null model");
+  if (!m->nderived) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+  if (n == 0) return 0;
+  if (!d_p || !d_out) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (int rc = usermodel_derive_rows(m, d_p, (long long)n, d_out, (hipStream_t)stream)) return rc;
+  CK(hipGetLastError());
   return 0;
 }
 

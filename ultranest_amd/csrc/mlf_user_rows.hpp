@@ -75,6 +75,24 @@
 //   not called    a row outside the membership mask, or one that fails the t-region gate, calls neither function: L = -inf.
 // A NaN term of accumulator j reaches finish as NaN in s[j] only.  The accumulators and t live in registers (M is a constant and
 // every loop over j is unrolled).
+//
+// Derived parameters (MLF_USER_DERIVED=1, its own code object with mlf_user_derive_rows as its only kernel; compiled from the
+// model's source followed by the derived source, so the model's helper functions are visible; nothing of this header refers to
+// mlf_user_loglike* or mlf_user_transform in this mode).  The derived source defines
+//
+//   __device__ void mlf_user_derived(const double *p, int d, double *q, int nq, const double *aux, long long naux);
+//
+// which writes all of q[0..nq) from the row's p (the d transformed parameters); a pure function of its arguments.
+//
+// mlf_user_derive_rows(p, n, d, nq, aux, naux, out): p holds n rows of d doubles, out n rows of d + nq doubles,
+// out_i = [p_i | q_i]; p and out must not overlap.  No membership mask: the kernel runs on compacted rows, after a route has
+// finished with them (no route's own rows change their width).  Rows beyond n are neither read nor written.  Two forms, chosen
+// from d and nq (mlf_user_rows_derive_lds_bytes):
+//   staged  one wave per workgroup copies its 64 rows of p into LDS (stage_in, pitch d + 1), each lane runs mlf_user_derived from
+//           its LDS row into a second LDS area of pitch nq + 1 (lane = row accesses conflict-free in both), and the [p | q] rows
+//           leave with coalesced stores of (d + nq)-wide rows.  LDS per wave: 64 * (d + 1 + nq + 1) * 8 bytes.
+//   direct  one thread per row from and to global memory, where the staging would exceed MLF_USER_ROWS_LDS_BUDGET
+//           (d + nq >= 127).
 #pragma once
 
 #define MLF_USER_ROWS_LDS_BUDGET 65536
@@ -90,6 +108,13 @@ __host__ __device__ inline unsigned mlf_user_rows_sum_lds_bytes(int d, bool has_
   return (unsigned)((has_p_buffer ? 2u : 1u) * (unsigned)d * 8u);
 }
 
+// bytes of dynamic LDS a launch of mlf_user_derive_rows needs (0: the direct form): 64 p rows of pitch d + 1 and 64 q rows of
+// pitch nq + 1
+__host__ __device__ inline unsigned mlf_user_rows_derive_lds_bytes(int d, int nq) {
+  const unsigned long long bytes = 64ull * (unsigned long long)(d + 1 + nq + 1) * 8ull;
+  return bytes <= MLF_USER_ROWS_LDS_BUDGET ? (unsigned)bytes : 0u;
+}
+
 #ifndef MLF_USER_ROWS_HOST
 
 #ifndef MLF_USER_HAS_TRANSFORM
@@ -100,6 +125,9 @@ __host__ __device__ inline unsigned mlf_user_rows_sum_lds_bytes(int d, bool has_
 #endif
 #ifndef MLF_USER_SUM
 #define MLF_USER_SUM 0
+#endif
+#ifndef MLF_USER_DERIVED
+#define MLF_USER_DERIVED 0
 #endif
 #if MLF_USER_TREGION
 #include "mlf_tregion_dev.hpp"
@@ -172,7 +200,49 @@ __device__ inline void transform_row(const double *x, double *y, int d, const do
 
 }  // namespace mlf_user_detail
 
-#if !MLF_USER_SUM
+#if MLF_USER_DERIVED
+
+extern "C" __global__ __launch_bounds__(64) void mlf_user_derive_rows(const double *__restrict__ p, long long n, int d, int nq,
+                                                                 const double *aux, long long naux, double *__restrict__ out) {
+  using namespace mlf_user_detail;
+  const int lane = threadIdx.x;
+  const long long j0 = (long long)blockIdx.x * 64;
+  if (j0 >= n) return;
+  const long long left = n - j0;
+  const int nrows = left >= 64 ? 64 : (int)left;
+  const int w = d + nq;   // an output row: [p | q]
+  if (mlf_user_rows_derive_lds_bytes(d, nq) != 0) {
+    extern __shared__ __attribute__((aligned(16))) double mlf_user_lds[];
+    const int ds = d + 1, qs = nq + 1;
+    double *a = mlf_user_lds;        // 64 rows of p
+    double *b = a + 64 * ds;         // 64 rows of q
+    stage_in(p + j0 * d, nrows * d, d, a, lane);
+    __syncthreads();
+    if (lane < nrows) mlf_user_derived(a + lane * ds, d, b + lane * qs, nq, aux, naux);
+    __syncthreads();
+    // element e = row * w + col of the wave's output block, stepped by 64 elements at a time as in stage_out
+    double *dst = out + j0 * w;
+    const int total = nrows * w;
+    const int qstep = 64 / w, rstep = 64 % w;
+    int row = lane / w, col = lane % w;
+    for (int e = lane; e < total; e += 64) {
+      dst[e] = col < d ? a[row * ds + col] : b[row * qs + (col - d)];
+      row += qstep;
+      col += rstep;
+      if (col >= w) {
+        col -= w;
+        row += 1;
+      }
+    }
+  } else if (lane < nrows) {
+    const double *x = p + (j0 + lane) * d;
+    double *y = out + (j0 + lane) * w;
+    for (int k = 0; k < d; ++k) y[k] = x[k];
+    mlf_user_derived(x, d, y + d, nq, aux, naux);
+  }
+}
+
+#elif !MLF_USER_SUM
 
 extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const double *u, long long n, int d, const unsigned char *member,
                                                                 const double *aux, long long naux, double *p, double *L

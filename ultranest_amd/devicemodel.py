@@ -5,9 +5,12 @@ The GPU counterpart of the reference's compiled-language likelihoods (reference 
 device functions, the package compiles them at run time for gfx950 (hiprtc) around one wrapper kernel
 (``csrc/mlf_user_rows.hpp``) and hands back a pair of vectorized callbacks::
 
-    model = DeviceModel(ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None)
+    model = DeviceModel(ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None,
+                        nderived=None, derived_source=None)
     model.loglike(theta)    # (n, ndim) -> (n,)       vectorized callback, evaluated on the GPU
     model.transform(u)      # (n, ndim) -> (n, ndim)  vectorized callback (identity without a transform source)
+
+(with ``nderived=Q`` the transform returns ``(n, ndim + Q)`` and the likelihood accepts either width: "Derived parameters" below)
 
 The sources define::
 
@@ -41,7 +44,42 @@ Not covered (a user model then runs on the per-step route, which returns the sam
 * the single-launch multi-round kernel (``max_rounds > 1``): ``k_walk_rounds`` inlines the built-in likelihoods, and
   compiling it per model is a later step.
 
-Derived parameters (``num_params != x_dim``) keep the host route: a model has ``nparams == ndim``.
+Derived parameters (``nderived=Q``)
+-----------------------------------
+Output columns computed from the parameters -- a flux from an amplitude and a width, a mass ratio, a radius: the reference
+driver's ``derived_param_names``, ``num_params = x_dim + Q``.  With ``nderived=Q`` (a Python int, ``Q >= 1`` and
+``ndim + Q <= MLF_MAX_DIM``; ``nderived`` and ``derived_source`` are given together) the derived source defines::
+
+    __device__ void mlf_user_derived(const double *p, int d, double *q, int nq, const double *aux, long long naux);
+
+It writes all of ``q[0..nq)`` from the row's ``p`` -- the ``d`` transformed parameters, or the cube coordinates of a model
+without a transform -- and is a pure function of its arguments, compiled under the contract of everything else (``-O3
+-std=c++17 -ffp-contract=off``, no inline assembly, reads of ``aux`` within ``naux``).  Then:
+
+* ``model.nparams == ndim + Q`` (``ndim`` without ``nderived``) and ``model.nderived`` is ``Q`` (or None);
+* ``model.transform(u)`` returns ``(n, ndim + Q)``: columns ``[0, ndim)`` are what the model without ``nderived`` returns, bit
+  for bit, columns ``[ndim, ndim + Q)`` are ``q``;
+* ``model.loglike(theta)`` accepts ``(n, ndim + Q)`` or ``(n, ndim)`` and reads the first ``ndim`` columns only.  THE LIKELIHOOD
+  DOES NOT SEE THE DERIVED COLUMNS (a stated restriction): a likelihood that needs such a quantity computes it itself;
+* ``model.derive(p)`` turns host rows ``(n, ndim)`` into ``(n, ndim + Q)``; ``model.derive_dev(d_p, n, d_out, stream=0)`` does
+  the same on device pointers, as ``eval_dev`` does (the two arrays must not overlap).
+
+Inside every device route a p row stays ``ndim`` wide: transform, t-region gate, likelihood, compaction and walker state are
+those of the model without ``nderived``, and its main programs are compiled from exactly that model's source string (the same
+cache keys and code objects: one compile serves both).  The derived columns come from ONE more program, compiled from
+``source + "\n" + derived_source`` with ``-DMLF_USER_DERIVED=1`` under its own cache key (the model's helper functions are
+visible to it), whose only kernel ``mlf_user_derive_rows`` (``csrc/mlf_user_rows.hpp``) runs on the rows a route hands out,
+after the route has finished with them -- in the reference's routes the derived columns are consumed only when a point is
+handed to the driver, so the rows are the same: the kept rows of a region refill (on the device, inside
+``mlf_region_refill_user_derived``), the prepared samples of ``PopulationRandomWalkSampler`` / ``PopulationSimpleSliceSampler``
+once per refill, the harvested point of ``PopulationSliceSampler``.  It combines with ``nterms`` / ``nsums`` without more programs.
+With ``identity_transform`` paired to the model's likelihood the host route yields no derived columns, so the device route
+yields none either (``device_route`` returns ``(model, False)`` and ``p`` is ``ndim`` wide).
+
+Not covered: a t-region (the driver's parameter-space wrapping ellipsoid) together with derived parameters -- the reference
+builds it over all ``num_params`` columns, so the gate would need ``q`` before the likelihood; ``refill(..., tregion=)`` returns
+None for such a model and the batch takes the host sequence through the callbacks above, which is correct -- and likelihoods
+that read derived columns.
 
 Likelihoods summed over data terms (``nterms=K``)
 -------------------------------------------------
@@ -143,7 +181,9 @@ HEADER = os.path.join(INCLUDE_DIR, "mlf_user_rows.hpp")
 GATE_HEADER = os.path.join(INCLUDE_DIR, "mlf_tregion_dev.hpp")      # included by the gated variant only
 VARIANT_DEFAULT, VARIANT_TREGION, VARIANT_SUM, VARIANT_SUM_TREGION = 0, 1, 2, 3     # MLF_USERMODEL_* of include/mlfriends_hip.h
 VARIANT_SUMS, VARIANT_SUMS_TREGION = 4, 5
+VARIANT_DERIVED = 6
 MAX_SUMS = 8                                                                        # MLF_USERMODEL_MAX_SUMS
+MAX_DIM = 1024                                                                      # MLF_MAX_DIM
 # what mlf_usermodel_compile passes to hiprtc besides -I, -DMLF_USER_HAS_TRANSFORM, -DMLF_USER_TREGION, -DMLF_USER_SUM and (with
 # nsums) -DMLF_USER_NSUMS (part of the cache key)
 COMPILE_OPTIONS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off")
@@ -172,6 +212,34 @@ def _check_nsums(nsums, summed):
     if not summed:
         raise ValueError("nsums needs the summed form: give nterms (the number of data terms) as well")
     return int(nsums)
+
+
+def _check_nderived(ndim, nderived, derived_source):
+    """nderived as an int (None stays None); ValueError naming the argument otherwise.  No library call."""
+    if nderived is None:
+        if derived_source is not None:
+            raise ValueError("derived_source needs nderived (the number of derived parameters it writes)")
+        return None
+    if isinstance(nderived, bool) or not isinstance(nderived, (int, np.integer)):
+        raise ValueError("nderived must be an integer (the number of derived parameters), got %r" % (nderived,))
+    if nderived < 1:
+        raise ValueError("nderived must be at least 1, got %d" % nderived)
+    if ndim + nderived > MAX_DIM:
+        raise ValueError("ndim + nderived must be at most %d (MLF_MAX_DIM), got %d + %d" % (MAX_DIM, ndim, nderived))
+    if derived_source is None:
+        raise ValueError("nderived needs derived_source (the source that defines mlf_user_derived)")
+    return int(nderived)
+
+
+def _derive_cache_key(source):
+    """the key of a derive program: that of a program without a transform, with " derived" among its options"""
+    h = hashlib.sha256()
+    with open(HEADER, "rb") as fh:
+        header = fh.read()
+    options = repr((COMPILE_OPTIONS, False)) + " derived"
+    for part in (source.encode(), b"\0", options.encode(), b"\0", header):
+        h.update(part)
+    return h.hexdigest()
 
 
 def _cache_key(source, has_transform, gated=False, summed=False, nsums=None):
@@ -227,6 +295,35 @@ def compile_model(source, has_transform, gated=False, summed=False, nsums=None):
         if rc == MLF_E_COMPILE:
             raise DeviceModelCompileError(log.value.decode(errors="replace"))
         if rc != 0 and size.value > cap:      # code object larger than the buffer: once more with its size
+            cap = size.value
+            continue
+        check(rc)
+        break
+    code = buf.raw[:size.value]
+    _code_cache[key] = code
+    return code
+
+
+def compile_derived(source):
+    """The gfx950 code object of the derive program of `source` (a model's source followed by its derived source): the
+    wrapper compiled with ``-DMLF_USER_DERIVED=1``, ``mlf_user_derive_rows`` its only kernel; cached per process."""
+    global compile_calls
+    key = _derive_cache_key(source)
+    code = _code_cache.get(key)
+    if code is not None:
+        return code
+    L = _lib.lib()
+    size = ctypes.c_size_t(0)
+    log = ctypes.create_string_buffer(1 << 16)
+    cap = 1 << 20
+    for _ in range(2):
+        buf = ctypes.create_string_buffer(cap)
+        compile_calls += 1
+        rc = L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), 0, VARIANT_DERIVED, buf, cap,
+                                             ctypes.byref(size), log, len(log))
+        if rc == MLF_E_COMPILE:
+            raise DeviceModelCompileError(log.value.decode(errors="replace"))
+        if rc != 0 and size.value > cap:
             cap = size.value
             continue
         check(rc)
@@ -294,18 +391,34 @@ class _Handle(object):
             pass
 
 
+class _DeriveHandle(_Handle):
+    """The loaded derive program of a model (``mlf_usermodel_create_derived``)."""
+
+    def __init__(self, code, ndim, nderived, aux):
+        h = ctypes.c_void_p()
+        check(_lib.lib().mlf_usermodel_create_derived(code, len(code), int(ndim), int(nderived), ptr(aux), len(aux),
+                                                      ctypes.byref(h)))
+        self._h = h
+        self.has_transform = False
+
+
 class DeviceModel(object):
     """A likelihood (and optional prior transform) written as HIP device functions (module docstring).  nterms=K: the
     summed form, whose likelihood source defines ``mlf_user_loglike_term`` and whose L is the sum of its K terms in the
     documented order.  nterms=K, nsums=M (1 <= M <= 8): the source defines ``mlf_user_loglike_terms`` (M terms per data
-    index) and ``mlf_user_loglike_finish`` (L from the M sums) instead; each sum follows that order."""
+    index) and ``mlf_user_loglike_finish`` (L from the M sums) instead; each sum follows that order.  nderived=Q with
+    derived_source (``mlf_user_derived``): Q derived columns behind the parameters, ``nparams == ndim + Q``; every route keeps
+    its ndim-wide rows and the derive program extends the rows that are handed out."""
 
     _count = 0
 
-    def __init__(self, ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None):
+    def __init__(self, ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None,
+                 nderived=None, derived_source=None):
         self.ndim = int(ndim)
         if self.ndim <= 0:
             raise ValueError("ndim must be positive")
+        self.nderived = _check_nderived(self.ndim, nderived, derived_source)
+        self.nparams = self.ndim + (self.nderived or 0)
         if nterms is not None:
             if isinstance(nterms, bool) or not isinstance(nterms, (int, np.integer)):
                 raise ValueError("nterms must be an integer (the number of terms of the summed form), got %r" % (nterms,))
@@ -320,6 +433,9 @@ class DeviceModel(object):
         DeviceModel._count += 1
         self.name = name or "DeviceModel%d" % DeviceModel._count
         self.code = self._compile(self.has_transform, False)
+        # the derive program: the model's source (helpers included) followed by the derived source; the main programs above
+        # are compiled from self.source alone, as those of the model without nderived
+        self.derive_code = None if self.nderived is None else compile_derived(self.source + "\n" + derived_source)
         self._handles = {}
         self.loglike = _Callback(self, "loglike")
         self.transform = _Callback(self, "transform")
@@ -357,6 +473,15 @@ class DeviceModel(object):
             self._handles[key] = h
         return h.handle
 
+    def derive_handle(self):
+        """The loaded derive program (created on first use: needs the GPU); cached with the model's other handles."""
+        if self.nderived is None:
+            raise ValueError("%s has no derived parameters (nderived)" % self.name)
+        h = self._handles.get("derived")
+        if h is None:
+            h = self._handles["derived"] = _DeriveHandle(self.derive_code, self.ndim, self.nderived, self.aux)
+        return h.handle
+
     def close(self):
         """Unload the model now (after the library's stream has finished with it)."""
         for h in self._handles.values():
@@ -370,6 +495,8 @@ class DeviceModel(object):
         return a
 
     def _loglike(self, theta):
+        if self.nderived is not None and np.ndim(theta) == 2 and np.shape(theta)[1] == self.nparams:
+            theta = np.asarray(theta)[:, :self.ndim]      # the likelihood does not see the derived columns
         p = self._rows(theta)
         out = np.empty(p.shape[0])
         if p.shape[0]:
@@ -381,7 +508,23 @@ class DeviceModel(object):
         out = np.empty_like(x)
         if x.shape[0]:
             check(_lib.lib().mlf_usermodel_eval(self.handle(), ptr(x), x.shape[0], ptr(out), None))
+        return out if self.nderived is None else self.derive(out)
+
+    def derive(self, p):
+        """Host rows ``(n, ndim)`` of parameters -> ``(n, ndim + nderived)``: ``[p | q]`` with q from ``mlf_user_derived``."""
+        if self.nderived is None:
+            raise ValueError("%s has no derived parameters (nderived)" % self.name)
+        x = self._rows(p)
+        out = np.empty((x.shape[0], self.nparams))
+        if x.shape[0]:
+            check(_lib.lib().mlf_usermodel_derive(self.derive_handle(), ptr(x), x.shape[0], ptr(out)))
         return out
+
+    def derive_dev(self, d_p, n, d_out, stream=0):
+        """`derive` on device pointers: d_p (n, ndim) -> d_out (n, ndim + nderived), which must not overlap.  Enqueued on
+        `stream`."""
+        check(_lib.lib().mlf_usermodel_derive_dev(self.derive_handle(), ctypes.c_void_p(d_p), int(n), ctypes.c_void_p(d_out),
+                                                  ctypes.c_void_p(stream)))
 
     def eval_dev(self, d_u, n, d_p=None, d_L=None, d_member=None, stream=0):
         """Device pointers (e.g. ``tensor.data_ptr()``): p = transform(u) when d_p is given, L = loglike(p or u) when d_L
@@ -402,7 +545,7 @@ def device_route(transform, loglike):
     if not isinstance(lspec, UserModelSpec) or lspec.role != "loglike":
         return None
     model = lspec.model
-    if transform is identity_transform:
+    if transform is identity_transform:      # (the host route then yields no derived columns: neither does the device route)
         return model, False
     tspec = getattr(transform, "device_spec", None)
     if isinstance(tspec, UserModelSpec) and tspec.role == "transform" and tspec.model is model:
@@ -410,4 +553,15 @@ def device_route(transform, loglike):
     return None
 
 
-__all__ = ["DeviceModel", "DeviceModelCompileError", "UserModelSpec", "compile_model", "device_route"]
+def extend_derived(user, p):
+    """The p rows ``(n, ndim)`` (or one row ``(ndim,)``) a device route hands out for ``user = (model, with_transform)``,
+    with the model's derived columns where the host route would yield them: a model with ``nderived`` paired with its own
+    transform.  Every other `p` comes back as it is."""
+    if user is None or not user[1] or user[0].nderived is None:
+        return p
+    p = np.asarray(p)
+    return user[0].derive(p[None, :])[0] if p.ndim == 1 else user[0].derive(p)
+
+
+__all__ = ["DeviceModel", "DeviceModelCompileError", "UserModelSpec", "compile_model", "compile_derived", "device_route",
+           "extend_derived"]

@@ -412,12 +412,18 @@ class DeviceRegion(object):
         transform / likelihood kinds."""
         return self._refill(_lib.lib().mlf_region_refill_user, method, nsamples, seed, offset, Lmin, capacity, model)
 
-    def _refill(self, fn, method, nsamples, seed, offset, Lmin, capacity, *evaluation):
+    def refill_user_derived(self, method, nsamples, seed, offset, Lmin, model, derive, nderived, capacity=None):
+        """`refill_user` with the model's derive handle: the kept rows come back as ``[p | q]``, d + nderived wide
+        (``mlf_region_refill_user_derived``); u, L, the count and the offset are those of `refill_user`."""
+        return self._refill(_lib.lib().mlf_region_refill_user_derived, method, nsamples, seed, offset, Lmin, capacity, model, derive,
+                            pwidth=self._d + int(nderived))
+
+    def _refill(self, fn, method, nsamples, seed, offset, Lmin, capacity, *evaluation, pwidth=None):
         """The call of `fn` (mlf_region_refill or its user variant) that `evaluation`, its arguments between Lmin and
-        the output arrays, completes."""
+        the output arrays, completes.  pwidth: the width of a p row where it is not d (derived parameters)."""
         d = self._d
         cap = int(nsamples if capacity is None else capacity)
-        u, p, L = np.empty((cap, d)), np.empty((cap, d)), np.empty(cap)
+        u, p, L = np.empty((cap, d)), np.empty((cap, d if pwidth is None else pwidth)), np.empty(cap)
         nev, nkept, nxt = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
         check(fn(self._h, int(method), int(nsamples), ctypes.c_uint64(int(seed)), ctypes.c_uint64(int(offset)), float(Lmin),
                  *evaluation, ptr(u), ptr(p), ptr(L), cap, ctypes.byref(nev), ctypes.byref(nkept), ctypes.byref(nxt)))

@@ -270,6 +270,7 @@ class PopulationRandomWalkSampler(_BatchedPopulationSampler):
         w.set_live(us, Ls)
         rejects_before = self.nrejects
         out = w.refill(Lmin, device_kind, self.scale, self.device_rng, tspec, lspec, user, force_chain=self.force_chain_form)
+        out["p"] = devicemodel.extend_derived(user, out["p"])      # derived parameters: once per refill, on the rows handed out
         self.last_refill = out
         self.nrejects += out["nrejects"]
         assert out["nnever"] == 0, 'some walkers never moved! Double nsteps of PopulationRandomWalkSampler.'
@@ -375,6 +376,7 @@ class PopulationSimpleSliceSampler(_BatchedPopulationSampler):
         dirscale = np.array([self.scale * self.scale_jitter_func() for _ in range(self.nsteps)], dtype=float)
         out = w.refill(Lmin, device_kind, dirscale, limit, self.shrink_factor, self.device_rng, tspec, lspec, user,
                        slots_per_poll=self.force_slots_per_poll)
+        out["p"] = devicemodel.extend_derived(user, out["p"])      # derived parameters: once per refill, on the rows handed out
         self.last_refill = out
         nc = P * out["niter"]
         width_sum = 0.
@@ -675,13 +677,21 @@ class _Walkers(object):
         rec = np.empty(9 + 2 * self.ndim)
         check(_lib.lib().mlf_walkers_finish_user(self._h, float(Lmin), model.handle(with_transform), int(ringindex),
                                                  ptr(rec)))
-        return self._record(rec, self.ndim)
+        return self._harvest_derived(self._record(rec, self.ndim), model, with_transform)
 
     def step_user(self, Lmin, scale, kind, dirscale, rng, model, with_transform):
         """`step_dev` (graph=False) with a user model."""
         rec = self._whole_step(_lib.lib().mlf_walkers_step_user, Lmin, scale, kind, dirscale, rng,
                                (model.handle(with_transform),))
-        return self._record(rec, self.ndim)
+        return self._harvest_derived(self._record(rec, self.ndim), model, with_transform)
+
+    @staticmethod
+    def _harvest_derived(out, model, with_transform):
+        """Derived parameters of a user model: the walker state and the record keep nparams == d; the harvested point's p is
+        extended when a point is harvested, and only then."""
+        if out["found"]:
+            out["p"] = devicemodel.extend_derived((model, with_transform), out["p"])
+        return out
 
     def set_live(self, us, Ls):
         us, Ls = f64(us), f64(Ls)

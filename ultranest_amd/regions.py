@@ -398,6 +398,12 @@ class _DeviceState(object):
         handle = model.handle(with_transform) if tregion is None else model.handle(with_transform, gated=True)
         return self._draw(region, use_scan, method, "refill_user", nsamples, Lmin, handle, tregion=tregion)
 
+    def refill_user_derived(self, region, use_scan, method, nsamples, Lmin, model):
+        """`refill_user` for a model with derived parameters and its own transform: the same batch, and the rows that are
+        kept come back as ``[p | q]`` (the model's derive kernel runs on them alone; never with a t-region)."""
+        return self._draw(region, use_scan, method, "refill_user_derived", nsamples, Lmin, model.handle(True),
+                          model.derive_handle(), model.nderived)
+
     def sample(self, region, use_scan, method, nsamples):
         """Device-side draw + membership + compaction with the region's ``device_rng``."""
         return self._draw(region, use_scan, method, "sample", nsamples)[0]
@@ -839,7 +845,10 @@ class MLFriends(_LivePoints):
         `tregion`: the driver's parameter-space ``WrappingEllipsoid`` (integrator.py:1789-1804).  Its ``inside`` test then
         runs on the device between transform and likelihood, in the arithmetic of the host test; the likelihood counts
         only for the rows of the region that pass, and ``nc`` is their number.  None is returned for a tregion that cannot
-        go to the device (``tregion_on_device``)."""
+        go to the device (``tregion_on_device``), and for any tregion together with a user model's derived parameters.
+
+        A user model with derived parameters (``DeviceModel(..., nderived=Q)``) paired with its own transform returns ``p`` of
+        shape ``(nkept, ndim + Q)``: the batch runs ``ndim`` wide and the derive kernel extends the kept rows."""
         tspec, lspec = getattr(transform, "device_spec", None), getattr(loglike, "device_spec", None)
         method = self._DEVICE_METHOD.get(getattr(self.current_sampling_method, "__name__", ""), None)
         user = devicemodel.device_route(transform, loglike)
@@ -857,7 +866,12 @@ class MLFriends(_LivePoints):
             if not tregion_on_device(tregion, self.u.shape[1]):
                 return None
             gate = dict(tregion=tregion)
-        if user is not None:
+        derived = user is not None and user[1] and user[0].nderived is not None
+        if derived and tregion is not None:
+            return None     # the tregion spans the derived columns too: the gate would need them (host sequence)
+        if derived:
+            u, p, L, nc = self._dev.refill_user_derived(self, self._uses_scan(), method, nsamples, Lmin, user[0])
+        elif user is not None:
             u, p, L, nc = self._dev.refill_user(self, self._uses_scan(), method, nsamples, Lmin, *user, **gate)
         else:
             u, p, L, nc = self._dev.refill(self, self._uses_scan(), method, nsamples, Lmin, tspec, lspec, **gate)

@@ -6,6 +6,9 @@
   funnel      examples/testfunnel.py: theta0 = log10 sigma with its own prior (x * 6 - 3), the rest x * 20 - 10; the data vector
               is the model's aux array
   gauss       docs/gauss.py:25-27 with the centres in aux (identity transform there; an affine one optionally)
+  gauss_derived  gauss with three derived parameters (``DeviceModel(..., nderived=3)``) whose arithmetic numpy reproduces bit for
+              bit: q0 = p[0] + p[1], q1 = p[0] * p[1], q2 = the sum of p[k] in ascending k from 0.0
+              (``np.cumsum(p, axis=1)[:, -1]``); no log or exp
 
 Likelihoods summed over data terms (``DeviceModel(..., nterms=K)``: one wave per row, the lanes split the terms), each with a
 default-form twin that computes the same terms in a serial loop k = 0..K-1 inside ``mlf_user_loglike``:
@@ -113,6 +116,31 @@ def gauss_centers(ndim, sigma=0.1):
 def gauss(ndim, sigma=0.1, affine=False):
     return DeviceModel(ndim, GAUSS_LOGLIKE % float(sigma), AFFINE_TRANSFORM if affine else None,
                        aux=gauss_centers(ndim, sigma), name="gauss%d" % ndim)
+
+
+GAUSS_DERIVED = r"""
+__device__ void mlf_user_derived(const double *p, int d, double *q, int nq, const double *aux, long long naux) {
+  q[0] = p[0] + p[1];
+  q[1] = p[0] * p[1];
+  double s = 0.0;
+  for (int k = 0; k < d; ++k) s = s + p[k];
+  q[2] = s;
+}
+"""
+
+
+def gauss_derived(ndim, sigma=0.1, affine=False):
+    """`gauss` with the derived columns p0 + p1, p0 * p1 and sum_k p_k (ndim >= 2); `gauss_derived_columns` restates them"""
+    if ndim < 2:
+        raise ValueError("gauss_derived reads p[0] and p[1]: ndim must be at least 2")
+    return DeviceModel(ndim, GAUSS_LOGLIKE % float(sigma), AFFINE_TRANSFORM if affine else None,
+                       aux=gauss_centers(ndim, sigma), name="gauss_derived%d" % ndim, nderived=3, derived_source=GAUSS_DERIVED)
+
+
+def gauss_derived_columns(p):
+    """the three derived columns of `gauss_derived` in numpy, bit for bit (cumsum adds sequentially; np.sum is pairwise)"""
+    p = np.asarray(p, dtype=float)
+    return np.column_stack([p[:, 0] + p[:, 1], p[:, 0] * p[:, 1], np.cumsum(p, axis=1)[:, -1]])
 
 
 LINEAR_TERM = r"""
