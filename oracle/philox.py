@@ -67,7 +67,8 @@ def cube_points(seed, offset, nsamples, ndim):
 def ball_points(seed, offset, nsamples, ndim, enlarge):
     """Method 1's draw before the axes rotation: uniform in the ball of radius sqrt(enlarge)
     (Box-Muller pairs + one radial uniform per point).  libm on the host and the device's
-    log/sin/cos/pow differ by a few ULP, so this is compared with a tolerance."""
+    log/sin/cos/pow differ by a few ULP: this binary64 form and the device are both held to the
+    high-precision restatement of tests/sampling_reference.py (1e-13 and 1e-12 of its scale)."""
     npairs = (ndim + 1) // 2
     per = npairs + 1
     base = np.uint64(offset) + np.arange(nsamples, dtype=np.uint64) * np.uint64(per)
@@ -100,7 +101,8 @@ def tbox_points(seed, offset, nsamples, ndim, lo, hi, pad):
 
 def around_points(seed, offset, nsamples, ndim, unormed, r2):
     """Method 3's draw: (t-space proposals, thinning uniforms, chosen live indices, next offset);
-    stream 6, (npairs + 2) blocks per proposal.  libm tolerance like ball_points."""
+    stream 6, (npairs + 2) blocks per proposal.  Held to tests/sampling_reference.py like
+    ball_points."""
     npairs = (ndim + 1) // 2
     per = npairs + 2
     base = np.uint64(offset) + np.arange(nsamples, dtype=np.uint64) * np.uint64(per)
