@@ -726,10 +726,11 @@ int mlf_allreduce_max(double *values, size_t count);
 int mlf_comm_destroy(void);
 
 /* Diagnostic counters of the LAST filtered batch of this region (synchronises the device): out[0] proposals the
- * bounded ellipsoid form could not decide (decided in binary64 by the tail of the re-check launch), out[1] reserved
- * (0), out[2] uncertain pairs listed by the pre-filter, out[3] largest list segment, out[4]
+ * bounded ellipsoid form could not decide (decided in binary64 by the tail of the re-check launch), out[1] above 128
+ * dimensions the queries the pre-filter left to the exact scan (guard cases and out[6]; else 0), out[2] uncertain pairs listed by the pre-filter, out[3] largest list segment, out[4]
  * list segments, out[5] 32-query groups left for the second live-point range, out[6] (cap > 6) queries whose minimum
- * over all live points ended in the band (the set the min-only sweep hands to its listing pass), out[7] (cap > 7)
+ * over all live points ended in the band (the set the min-only sweep hands to its listing pass; above 128 dimensions: to the
+ * exact scan), out[7] (cap > 7)
  * 32-query groups left for the third range ("filter_second_range_pct"), out[8 ... 15] (cap >= 16) shader-clock stamps of the
  * stage boundaries of one workgroup of the last launch that records them, out[16], out[17] (cap >= 18) the tile cuts of the last
  * min-only batch (the second is 0 with two ranges), out[18] (cap >= 19) 1 if the last fused first launch read the ellipsoid's

@@ -153,7 +153,12 @@ int mlf_region_debug_stats(mlf_region *r, unsigned long long *out, int cap) {
     unsigned g[6];
     CK(hipMemcpy(g, f.png.p, sizeof g, hipMemcpyDeviceToHost));
     out[5] = g[0];
-    if (cap > 6) out[6] = g[1];   // queries of the last min-only batch whose minimum ended in the band (uncertain set)
+    if (cap > 6) out[6] = g[1];   // queries of the last min-only batch whose minimum ended in the band (uncertain set; above 128 dimensions: left to the exact scan)
+    if (f.last.wide) {   // above 128 dimensions: every query the pre-filter left to the exact scan (guard cases + band)
+      unsigned w[8];
+      CK(hipMemcpy(w, f.png.p, sizeof w, hipMemcpyDeviceToHost));
+      out[1] = w[6];
+    }
     if (cap > 7) out[7] = g[5];   // three ranges: groups that entered the third
   }
   if (cap > 17) {

@@ -9,6 +9,7 @@
 #include "mlf_filter.hpp"
 #include "mlf_misc.hpp"
 #include "mlf_small.hpp"
+#include "mlf_wide_filter.hpp"
 
 namespace mlf {
 
@@ -76,6 +77,7 @@ struct BatchPlan {
   bool host_refs = false;       // BATCH_HOST: quantise the live points for the filter, then plan the batch again
   Stage stage = STAGE_NONE;
   bool mid = false;             // stage, sweep, re-check and answers in one launch (k_inside_mid)
+  bool wide = false;            // 129 ... 1024 dimensions: the run-time-dimension pre-filter (mlf_wide_filter.hip), mask mode only
   bool time_launches = false;   // "time_filter_launches": event pairs around the matrix launches, k_inside_mid's stamps
   bool ordered = false;         // sweep the centre-first copy of the live points (refFm / refRm)
   int nphase = 1;               // live-point ranges of the sweep
@@ -97,6 +99,7 @@ struct FilterCtx {
   bool refs_dirty = false;   // a live point was replaced since: requantise before the next batch that uses the operands
   bool usable = false;       // statistics are finite and the dimensionality is covered
   int ks = 0, ntiles32 = 0;
+  bool wide = false;         // the operands are those of mlf_wide_filter.hip (ks > 9): mask mode only, storage order only
   double sigma = 1.0, amax = 0.0;
   DevBuf stats, statscratch, refF, qF, tlo, thi, route, best, counters, list, segcnt, gate2;
   // mask-mode operand: the live points nearest to the centre first (launch_ref_order): binary16 fragments, the rows the exact
@@ -108,6 +111,7 @@ struct FilterCtx {
   DevBuf pqF[2], ptlo[2], pthi[2], pmap[2], png, pmin, pmin2;
   DevBuf mid_rec, mid_meta, mid_arrive;   // one-launch path (mlf_mid.hip): records of the tile ranges, arrival counters
   bool mid_dirty = false;                 // a launch of that path failed: its self-resetting counters are zeroed before the next batch
+  DevBuf wstatscratch;                    // statistics scratch of the wide operands (its own layout: 1024 columns)
   DevBuf fstamps;                         // diagnostics: stage stamps of one k_prep_sweep wave
   int stamp_block = -1;
   bool png_dirty = false;                 // a phased batch did not reach its scan launch (whose tail returns the slot counters to zero)
@@ -127,9 +131,9 @@ struct FilterCtx {
   void release() {
     DevBuf *b[] = {&stats, &statscratch, &refF, &qF, &tlo, &thi, &route, &best, &counters, &list, &segcnt, &gate2, &refFm, &refRm, &okeys, &operm,
                    &pqF[0], &pqF[1], &ptlo[0], &ptlo[1], &pthi[0], &pthi[1], &pmap[0], &pmap[1], &png, &pmin, &pmin2, &mid_rec, &mid_meta, &mid_arrive,
-                   &ell_list, &misc, &fstamps};
+                   &ell_list, &misc, &fstamps, &wstatscratch};
     for (DevBuf *x : b) x->release();
-    refs_ready = usable = ordered = false;
+    refs_ready = usable = ordered = wide = false;
     order_n = -1;
   }
 };
@@ -289,7 +293,7 @@ int stage_live_points(const double *pts, size_t n, size_t d, int dp, int npad, b
 int prep_consts(DevBuf &ctr_b, DevBuf &mat_b, const double *ctr, const double *mat, int d, int dp, bool transpose, hipStream_t s);
 
 // ---- mlf_route.hip: one membership batch along its plan ------------------------------------------------------------
-int filter_prepare_refs(FilterCtx &f, const double *refR, int n, int d, int dp, hipStream_t s, bool host_sync);
+int filter_prepare_refs(FilterCtx &f, const double *refR, int n, int d, int dp, hipStream_t s, bool host_sync, bool mask_mode = true);
 int filter_refresh_refs(FilterCtx &f, const double *refR, int n, int d, int dp, hipStream_t s);
 int misc_reserve(FilterCtx &f);
 BatchPlan plan_batch(const FilterCtx &f, const mlf_region *r, BatchKind kind, long long nq, double r2, bool first_index = false,

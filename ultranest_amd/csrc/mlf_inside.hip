@@ -278,7 +278,12 @@ int region_inside_enqueue(mlf_region *r, const double *d_pts, size_t np, uint8_t
       pa.t_out = r->tq.as<double>();
       pa.ldt = r->d;
     }
-    CK(launch_prep64(pa, s));
+    if (prep64_wide_usable(r->d)) {   // above 128 dimensions: the run-time-dimension form with its own band (2^-28 |A|_F, mlf_prep64.hip)
+      pa.ell_eps_scale = 64.0 * r->ell_eps_scale;
+      CK(launch_prep64_wide(pa, s));
+    } else {
+      CK(launch_prep64(pa, s));
+    }
   } else {
     PrepArgs pa{};
     pa.pts = d_pts;

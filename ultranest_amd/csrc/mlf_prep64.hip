@@ -177,7 +177,134 @@ __global__ __launch_bounds__(64 * kP64Waves, 2) void k_prep_mfma64(Prep64Args a)
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same stage for 129 ... 1024 dimensions, the dimensionality at run time (the per-proposal stage of the batches that take
+// the pre-filter of mlf_wide_filter.hip; k_prep_wide -- one thread per proposal, a 64-lane workgroup per CU -- was 91-100 % of
+// such a call).  A wave takes 16 proposals.  Nothing is staged: a lane's operand of a k-step is one coordinate of its
+// proposal, read from the row as handed over (L1 / L2 hits from the second pass on), and the accumulators hold kW64CT output
+// tiles (128 columns) at a time -- the k-loop runs once per chunk of columns.  The whitened coordinates leave straight from
+// the accumulator registers.  Arithmetic as above: whitening = the k-ascending FMA chain bit for bit, the quadratic form
+// bounded, proposals inside the band evaluated in the einsum order by their first lane.
+// The band: eps = 2^-28 |A|_F |delta|^2 (the caller's scale).  Up to 1024 dimensions three errors of up to d^2 2^-53 = 2^-33
+// each (same units) meet: the reference's own sequential sum of d^2 terms, the backward error of the host Cholesky factor,
+// and the chains of y = L^T delta and |y|^2; 2^-28 leaves a factor of ten above their sum (k_prep3's 2^-34 is stated for
+// d <= 128, where they are 2^-39).
+constexpr int kW64CT = 8;
+__global__ __launch_bounds__(64 * kP64Waves) void k_prep_mfma64_wide(Prep64Args a) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int q = lane & 15, kq = lane >> 4;
+  const int d = a.d, dp = a.dp;
+  const int nk = dp / 4, nct = dp / 16;   // dp is a multiple of 16
+  const long long ntiles = (a.np + 15) / 16;
+  for (long long tile = (long long)blockIdx.x * kP64Waves + wv; tile < ntiles; tile += (long long)gridDim.x * kP64Waves) {
+    const long long p = tile * 16 + q;
+    const bool live = p < a.np;
+    const double *row = a.pts + (live ? p : 0) * (long long)d;
+    // ---- H3 bound: y = L^T delta, qt = |y|^2
+    double qt = 0.0, nrm2 = 0.0;
+    for (int c0 = 0; c0 < nct; c0 += kW64CT) {
+      double4m y[kW64CT];
+#pragma unroll
+      for (int ct = 0; ct < kW64CT; ++ct) y[ct] = (double4m){0.0, 0.0, 0.0, 0.0};
+      // L[k][c] = 0 for c > k: k-steps in front of the chunk's first column contribute nothing (the first chunk starts at 0)
+#pragma unroll 2
+      for (int ks = 4 * c0; ks < nk; ++ks) {
+        const int k = 4 * ks + kq;
+        const double dl = (live && k < d) ? row[k] - a.ell_ctr[k] : 0.0;
+        if (c0 == 0) nrm2 = __builtin_fma(dl, dl, nrm2);
+        double afr[kW64CT];
+#pragma unroll
+        for (int ct = 0; ct < kW64CT; ++ct) {
+          const int c = 16 * (c0 + ct) + q;
+          afr[ct] = (c0 + ct < nct && 16 * (c0 + ct) <= 4 * ks + 3 && k < d && c < d) ? a.ell_L[(size_t)k * dp + c] : 0.0;
+        }
+#pragma unroll
+        for (int ct = 0; ct < kW64CT; ++ct)
+          if (c0 + ct < nct && 16 * (c0 + ct) <= 4 * ks + 3) y[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[ct], dl, y[ct], 0, 0, 0);
+      }
+#pragma unroll
+      for (int ct = 0; ct < kW64CT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) qt = __builtin_fma(y[ct][r], y[ct][r], qt);
+    }
+    qt = quad_sum64(qt);
+    nrm2 = quad_sum64(nrm2);
+    const double eps = a.ell_eps_scale * nrm2;
+    const bool sure_in = a.chol_ok && (qt + eps < a.enlarge);
+    const bool sure_out = a.chol_ok && (qt - eps > a.enlarge);
+    bool inside = sure_in;
+    const bool need_exact = live && !sure_in && !sure_out;   // also every NaN
+    if (__any(need_exact)) {
+      // the reference's arithmetic: one accumulator, j outer, (d_j A_jk) d_k, no fma; by the proposal's first lane
+      double acc = 0.0;
+      if (need_exact && kq == 0) {
+        for (int j = 0; j < d; ++j) {
+          const double dj = row[j] - a.ell_ctr[j];
+          const double *arow = a.ell_A + (size_t)j * a.lda;
+          for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * (row[k] - a.ell_ctr[k]);
+        }
+      }
+      acc = __shfl(acc, q, 64);
+      if (need_exact) inside = acc <= a.enlarge;
+    }
+    inside = inside && live;
+    if (live && kq == 0) a.gate[p] = inside ? 1 : 0;
+    if (!a.do_tr || !__any(inside)) continue;
+    // ---- T1: t = delta_w T, k ascending, one fma per term
+    for (int c0 = 0; c0 < nct; c0 += kW64CT) {
+      double4m t[kW64CT];
+#pragma unroll
+      for (int ct = 0; ct < kW64CT; ++ct) t[ct] = (double4m){0.0, 0.0, 0.0, 0.0};
+#pragma unroll 2
+      for (int ks = 0; ks < nk; ++ks) {
+        const int k = 4 * ks + kq;
+        double dw = 0.0;
+        if (live && k < d) {
+          double w = row[k];
+          if (a.wrap_shift) {
+            const double sh = a.wrap_shift[k];
+            if (sh == sh) {   // NaN marks an unwrapped dimension
+              const double xs = w + sh;
+              w = (xs >= 0.0 && xs < 2.0) ? (xs >= 1.0 ? xs - 1.0 : xs) : wrap_coordinate64(w, sh);
+            }
+          }
+          dw = w - a.lay_ctr[k];
+        }
+        double afr[kW64CT];
+#pragma unroll
+        for (int ct = 0; ct < kW64CT; ++ct) {
+          const int c = 16 * (c0 + ct) + q;
+          afr[ct] = (c0 + ct < nct && c < d) ? a.T8[(size_t)k * a.ldt8 + c] : 0.0;   // k < dp: rows past d are zero
+        }
+#pragma unroll
+        for (int ct = 0; ct < kW64CT; ++ct)
+          if (c0 + ct < nct) t[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[ct], dw, t[ct], 0, 0, 0);
+      }
+      if (inside)
+#pragma unroll
+        for (int ct = 0; ct < kW64CT; ++ct)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = 16 * (c0 + ct) + kq + 4 * r;   // output row of the accumulator register (mlf_prep3.hip)
+            if (c0 + ct < nct && c < d) a.t_out[p * a.ldt + c] = t[ct][r];
+          }
+    }
+  }
+}
+
 }  // namespace
+
+bool prep64_wide_usable(int d) { return d > 128 && d <= 1024; }
+
+hipError_t launch_prep64_wide(const Prep64Args &a, hipStream_t s) {
+  if (a.np <= 0) return hipSuccess;
+  if (!prep64_wide_usable(a.d) || (a.dp & 15) || a.dp < a.d || a.ldt8 < a.dp) return hipErrorInvalidValue;
+  const long long ntiles = (a.np + 15) / 16;
+  long long wgs = (ntiles + kP64Waves - 1) / kP64Waves;
+  if (wgs > 256 * 8) wgs = 256 * 8;
+  hipLaunchKernelGGL(k_prep_mfma64_wide, dim3((unsigned)wgs), dim3(64 * kP64Waves), 0, s, a);
+  return hipGetLastError();
+}
 
 bool prep64_usable(int d) { return d > 64 && d <= 128; }
 

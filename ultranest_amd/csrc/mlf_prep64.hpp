@@ -27,5 +27,8 @@ struct Prep64Args {
 
 bool prep64_usable(int d);
 hipError_t launch_prep64(const Prep64Args &a, hipStream_t s);
+// 129 ... 1024 dimensions (the dimensionality at run time); ell_eps_scale = 2^-28 |A|_F up here
+bool prep64_wide_usable(int d);
+hipError_t launch_prep64_wide(const Prep64Args &a, hipStream_t s);
 
 }  // namespace mlf

@@ -325,7 +325,7 @@ int mlf_region_set(mlf_region *r, const double *unormed, size_t n, size_t d, int
     r->chol_ok = ok && std::isfinite(fro);
     r->ell_eps_scale = std::ldexp(1.0, -34) * std::sqrt(fro);
     if (int rc = upload(r->ell_Lt, Lt.data(), Lt.size() * sizeof(double), c.stream)) return rc;
-    if (prep64_usable((int)d) && ok) {   // 65 ... 128 dimensions: the factor itself, row-major (mlf_prep64.hip reads its rows)
+    if ((prep64_usable((int)d) || prep64_wide_usable((int)d)) && ok) {   // 65 ... 1024 dimensions: the factor itself, row-major (mlf_prep64.hip reads its rows)
       std::vector<double> lrm((size_t)dp * dp, 0.0);
       for (size_t j = 0; j < d; ++j)
         for (size_t k = 0; k <= j; ++k) lrm[j * dp + k] = L[j * d + k];

@@ -14,16 +14,46 @@ namespace mlf {
 // Quantise the live points for the filter.  host_sync = true also fetches the statistics that the
 // host-side eligibility test uses (done when the live set is installed, not per batch).
 int filter_prepare_refs(FilterCtx &f, const double *refR, int n, int d, int dp, hipStream_t s,
-                        bool host_sync) {
+                        bool host_sync, bool mask_mode) {
   f.refs_ready = false;
+  f.wide = false;
   const int ks = (dp + 6 + 15) / 16;   // filter dimensionality = padded DP (zero columns are harmless)
-  if (ks > 9 || n < 1 || (long long)round_up(n, 32) / 32 * ks * 1024 >= (1ll << 31)) {   // k_sweep addresses the tiles with 32-bit buffer offsets
+  // above 9 k-steps (128 dimensions): the run-time-dimension operands of mlf_wide_filter.hip, which serve mask mode only
+  const bool wide = ks > 9;
+  if ((wide && (!mask_mode || ks > kWideFilterMaxKs)) || n < 1 ||
+      (long long)round_up(n, 32) / 32 * ks * 1024 >= (1ll << 31)) {   // k_sweep addresses the tiles with 32-bit buffer offsets
     f.usable = false;
     return 0;
   }
   f.ks = ks;
   const int npad32 = round_up(n, 32);
   f.ntiles32 = npad32 / 32;
+  if (wide) {   // storage order only: no centre-first copy up here
+    CK(f.stats.reserve((8 + kWideStatCols) * sizeof(double)));
+    CK(f.refF.reserve((size_t)npad32 * ks * 16 * 2));
+    {
+      const void *before = f.wstatscratch.p;
+      CK(f.wstatscratch.reserve(wide_stat_scratch_bytes()));
+      if (f.wstatscratch.p != before) CK(hipMemsetAsync(f.wstatscratch.p, 0, wide_stat_scratch_bytes(), s));   // running maxima start at zero
+    }
+    launch_wide_ref_stats(refR, n, dp, f.stats.as<double>(), f.wstatscratch.as<double>(), s);
+    launch_wide_quant_refs(refR, n, npad32, dp, ks, f.stats.as<double>(), f.refF.p, s);
+    CK(hipGetLastError());
+    f.ordered = false;
+    if (host_sync) {
+      f.order_n = -1;
+      double h[4];
+      CK(hipMemcpyAsync(h, f.stats.p, sizeof h, hipMemcpyDeviceToHost, s));
+      CK(hipStreamSynchronize(s));
+      f.sigma = h[0];
+      f.amax = h[2];
+      f.usable = h[3] == 1.0 && h[2] > 0.0 && h[2] < 1e150;
+    }
+    f.wide = true;
+    f.refs_ready = true;
+    f.refs_dirty = false;
+    return 0;
+  }
   CK(f.stats.reserve((8 + MLF_FILTER_MAXD) * sizeof(double)));
   CK(f.refF.reserve((size_t)npad32 * ks * 16 * 2));
   (void)d;
@@ -102,6 +132,8 @@ BatchPlan plan_batch(const FilterCtx &f, const mlf_region *r, BatchKind kind, lo
   if (opt(f, OPT_MIN_QUERIES) == kFilterMinQueriesDefault && nq < 2048 && (long long)f.ntiles32 * 32 * f.ks * 16 < 40000) eligible = false;
   const double sr2 = f.sigma * f.sigma * r2;
   eligible = eligible && r2 > 0.0 && r2 < 1e150 && sr2 < 4096.0 && sr2 > 1e-30;
+  // 129 ... 1024 dimensions: the operands serve the mask-mode sweep of mlf_wide_filter.hip; first-index batches keep the exact scan
+  if (f.wide) eligible = eligible && !first_index && kind != BATCH_HOST;
   if (kind == BATCH_HOST) {
     // The stateless call pays the filter's live-point preparation every time and first-index mode keeps sweeping after
     // a hit, so the pre-filter only pays for larger batches than in the resident mask path (measured at N = 4000,
@@ -125,10 +157,19 @@ BatchPlan plan_batch(const FilterCtx &f, const mlf_region *r, BatchKind kind, lo
       p.stage = STAGE_PREP3;
     else if (r->layer_kind == 0 && prep64_usable(r->d) && r->chol_ready && r->chol_ok && opt(f, OPT_FUSED_PREP))
       p.stage = STAGE_PREP64;
+    // 129 ... 1024 dimensions: the run-time-dimension form of that stage comes with the pre-filter ("filter" = 0 stays the
+    // exact route throughout: k_prep_wide + k_scan_wide)
+    else if (r->layer_kind == 0 && prep64_wide_usable(r->d) && p.filter && f.wide && kind == BATCH_INSIDE && r->chol_ready && r->chol_ok &&
+             opt(f, OPT_FUSED_PREP))
+      p.stage = STAGE_PREP64;
     else
       p.stage = STAGE_PREP;
   }
   if (!p.filter) return p;
+  if (f.wide) {   // quantise, one min-only sweep, exact tail over the list of the proposals left: nothing else to choose
+    p.wide = true;
+    return p;
+  }
   // mask mode sweeps the centre-first copy of the live points (any hit decides); the first-index mode keeps storage order
   p.ordered = !first_index && f.ordered && opt(f, OPT_ORDER);
   const bool bounded = p.stage == STAGE_PREP4;
@@ -549,12 +590,76 @@ int filter_scan_tail(const FilterBatch &b) {
   return 0;
 }
 
+// 129 ... 1024 dimensions, mask mode (mlf_wide_filter.hip): the whitened rows are quantised and routed, one min-only sweep
+// answers every query whose minimum is outside its band, and the exact scan takes what is left (route 2)
+int filter_run_wide(const FilterBatch &b) {
+  FilterCtx &f = b.f;
+  if (b.out_idx || !b.out_mask || b.xs || b.ldk > 1) return fail_arg(MLF_E_STATE, "wide pre-filter: mask mode on row-major whitened rows only");
+  const long long nqpad = b.ngroups() * 32;
+  f.last = b.p;
+  CK(f.qF.reserve((size_t)nqpad * f.ks * 16 * 2));
+  CK(f.tlo.reserve((size_t)nqpad * sizeof(float)));
+  CK(f.thi.reserve((size_t)nqpad * sizeof(float)));
+  CK(f.route.reserve((size_t)b.nq));
+  CK(f.best.reserve((size_t)b.nq * sizeof(int)));   // the list of the route-2 queries
+  // png[1]: queries whose minimum ended in the band, png[6]: length of the route-2 list (mlf_region_debug_stats reads both).
+  // The list counter is cleared in front of every batch: a batch that failed between its quantiser and its tail leaves nothing
+  // behind that the next tail could take for query numbers
+  if (!f.png.p) {
+    CK(f.png.reserve(8 * sizeof(unsigned)));
+    CK(hipMemset(f.png.p, 0, 8 * sizeof(unsigned)));
+  }
+  WideQuantArgs qa{};
+  qa.q = b.q;
+  qa.ldq = b.ldq;
+  qa.nq = b.nq;
+  qa.nqpad = nqpad;
+  qa.d_src = b.L.d;
+  qa.d = b.L.dp;
+  qa.ks = f.ks;
+  qa.stats = f.stats.as<double>();
+  qa.r2 = b.L.r2;
+  qa.gate = b.gate;
+  qa.qF = f.qF.p;
+  qa.tlo = f.tlo.as<float>();
+  qa.thi = f.thi.as<float>();
+  qa.route = f.route.as<uint8_t>();
+  qa.out_mask = b.out_mask;
+  unsigned *qcount = f.png.as<unsigned>() + 6;
+  CK(hipMemsetAsync(qcount, 0, sizeof(unsigned), b.s));
+  qa.band_count = f.png.as<unsigned>() + 1;
+  qa.qlist = f.best.as<int>();
+  qa.qcount = qcount;
+  if (int rc = timed_launch(b, [&] { return launch_wide_quant_queries(qa, b.s); })) return rc;
+  WideSweepArgs sa{};
+  sa.refF = f.refF.p;
+  sa.ntiles32 = f.ntiles32;
+  sa.ks = f.ks;
+  sa.qF = f.qF.p;
+  sa.tlo = f.tlo.as<float>();
+  sa.thi = f.thi.as<float>();
+  sa.ngroups = b.ngroups();
+  sa.nq = b.nq;
+  sa.route = f.route.as<uint8_t>();
+  sa.out_mask = b.out_mask;
+  sa.band_count = f.png.as<unsigned>() + 1;
+  sa.qlist = f.best.as<int>();
+  sa.qcount = qcount;
+  if (int rc = timed_launch(b, [&] { return launch_wide_sweep(sa, b.s); })) return rc;
+  if (b.ev_after) CK(hipEventRecord(b.ev_after, b.s));
+  ScanArgs a = scan_args(b.L, b.q, b.ldq, b.ldk, b.nq, SCAN_MASK);
+  a.out_mask = b.out_mask;
+  CK(launch_scan_wide_list(b.L.dp, a, f.best.as<int>(), qcount, b.s));
+  return 0;
+}
+
 }  // namespace
 
 // Filter pipeline on device data along the plan's route
 int filter_run(const FilterBatch &b) {
   FilterCtx &f = b.f;
   const BatchPlan &p = b.p;
+  if (p.wide) return filter_run_wide(b);
   const long long nqpad = b.ngroups() * 32;
   f.last = p;
   if (p.min_path) f.last_min = p;

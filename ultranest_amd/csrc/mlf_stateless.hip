@@ -33,7 +33,7 @@ int scan_host(const double *apts, size_t na, const double *bpts, size_t nb, size
   const LiveSet live{c.refT.as<double>(), c.refR.as<double>(), (int)na, npad, (int)d, dp, r2};
   BatchPlan p = plan_batch(c.filter, nullptr, BATCH_HOST, (long long)nb, r2, mode == SCAN_FIRST, false, nullptr, na);
   if (p.host_refs) {   // quantise the live points, then route with their statistics
-    if (int rc = filter_prepare_refs(c.filter, c.refR.as<double>(), (int)na, (int)d, dp, c.stream, true)) return rc;
+    if (int rc = filter_prepare_refs(c.filter, c.refR.as<double>(), (int)na, (int)d, dp, c.stream, true, false)) return rc;   // first-index mode only
     p = plan_batch(c.filter, nullptr, BATCH_HOST, (long long)nb, r2, mode == SCAN_FIRST, false, nullptr, na);
   }
   if (p.filter) {

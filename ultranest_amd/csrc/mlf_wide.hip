@@ -11,6 +11,7 @@
 //
 //   k_scan_wide        K1 / K2 / K3 pass 1 / the scan of R3 (find_nearby :143-183, count_nearby :31-68): lane = live point,
 //                      16 queries of the workgroup in LDS, 16 coordinates of the live tile in registers at a time
+//   k_scan_wide_list   the same scan, mask mode, over a LIST of queries: the exact tail of the pre-filter of mlf_wide_filter.hip
 //   k_boot_wide        K4 (compute_maxradiussq :188-224) for up to 32 bootstrap rounds: lane = row j, four live points i
 //                      at a time, masked minima, the same M as k_boot
 //   k_prep_wide        H3 + T1 (_inside_ellipsoid :882-912 in numpy's einsum order, AffineLayer.transform :737-743 as a
@@ -118,6 +119,70 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_wide(ScanArgs a, int dpw)
       a.out_idx[q0 + tid] = (long long)cnt[tid];
     else if (mode == SCAN_MASK)
       a.out_mask[q0 + tid] = found ? 1 : 0;
+  }
+}
+
+// The exact tail behind the mask-mode pre-filter (mlf_wide_filter.hip): k_scan_wide's mask mode over the *qcount queries listed in
+// qlist (the proposals the filter left to the exact scan, in any order) -- the same staging, the same sums in the same order,
+// the same ballots.  A bounded grid strides over the list's blocks of 16, so the tail costs what its list holds.  A twin and not a mode of k_scan_wide: the list's indirection and the
+// block loop cost that kernel 14 VGPRs and its fourth wave per SIMD (137 against 123).
+__global__ __launch_bounds__(kScanThreads) void k_scan_wide_list(ScanArgs a, int dpw, const int *__restrict__ qlist,
+                                                                 const unsigned *__restrict__ qcount) {
+  extern __shared__ __attribute__((aligned(16))) double qs[];   // [kWideQB][dpw]
+  __shared__ int hit[kWideQB];
+  __shared__ long long qi[kWideQB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long nq = (long long)*qcount;
+  for (long long q0 = (long long)blockIdx.x * kWideQB; q0 < nq; q0 += (long long)gridDim.x * kWideQB) {
+    const long long left = nq - q0;
+    const int nqb = left < kWideQB ? (int)left : kWideQB;
+    if (tid < kWideQB) {
+      qi[tid] = tid < nqb ? (long long)qlist[q0 + tid] : 0;
+      hit[tid] = 0;
+    }
+    __syncthreads();
+    for (int e = tid; e < kWideQB * dpw; e += kScanThreads) {
+      const int qq = e / dpw, k = e - qq * dpw;
+      double v = 0.0;
+      if (qq < nqb && k < a.d) v = a.q[qi[qq] * a.ldq + k];
+      qs[e] = v;
+    }
+    __syncthreads();
+    for (int t = wave; t < a.ntiles; t += kScanThreads / kWave) {
+      const int base = t * kWave;
+      bool need = false;   // a tile none of the block's queries still needs is skipped (wave-uniform)
+      for (int qq = 0; qq < nqb; ++qq) need |= *(volatile int *)&hit[qq] == 0;
+      if (!need) continue;
+      double acc[kWideQB];
+#pragma unroll
+      for (int qq = 0; qq < kWideQB; ++qq) acc[qq] = 0.0;
+      for (int c0 = 0; c0 < dpw; c0 += kWideKC) {   // k ascending across the chunks: each sum continues where it stopped
+        double r[kWideKC];
+#pragma unroll
+        for (int k = 0; k < kWideKC; ++k) r[k] = a.refT[(size_t)(c0 + k) * a.npad + base + lane];   // rows past d are zero
+#pragma unroll
+        for (int qq = 0; qq < kWideQB; ++qq) {
+          const double2 *qrow = reinterpret_cast<const double2 *>(qs + qq * dpw + c0);
+#pragma unroll
+          for (int k = 0; k < kWideKC; k += 2) {
+            const double2 v = qrow[k >> 1];
+            const double d0 = r[k] - v.x;
+            acc[qq] += d0 * d0;
+            const double d1 = r[k + 1] - v.y;
+            acc[qq] += d1 * d1;
+          }
+        }
+      }
+      const bool valid = base + lane < a.n;
+#pragma unroll
+      for (int qq = 0; qq < kWideQB; ++qq) {
+        const unsigned long long m = __ballot(valid && acc[qq] <= a.r2);
+        if (m != 0ull && lane == 0 && qq < nqb) hit[qq] = 1;
+      }
+    }
+    __syncthreads();
+    if (tid < nqb) a.out_mask[qi[tid]] = hit[tid] ? 1 : 0;
+    __syncthreads();   // the staged queries are reused by this workgroup's next block
   }
 }
 
@@ -347,6 +412,18 @@ hipError_t launch_scan_wide(int dp, const ScanArgs &a, hipStream_t s) {
   if (hipError_t e = allow_lds(grant_k_scan_wide, reinterpret_cast<const void *>(&k_scan_wide), lds)) return e;
   const unsigned grid = (unsigned)((a.nq + kWideQB - 1) / kWideQB);
   hipLaunchKernelGGL(k_scan_wide, dim3(grid), dim3(kScanThreads), lds, s, a, dp);
+  return hipGetLastError();
+}
+
+// mask-mode scan of the *qcount queries listed in qlist (a.nq = the most the list can hold)
+hipError_t launch_scan_wide_list(int dp, const ScanArgs &a, const int *qlist, const unsigned *qcount, hipStream_t s) {
+  if (a.nq <= 0) return hipSuccess;
+  if (a.mode != SCAN_MASK || a.ldk > 1 || !a.out_mask || !qlist || !qcount) return hipErrorInvalidValue;
+  const size_t lds = (size_t)kWideQB * dp * sizeof(double);
+  static DeviceGrant grant_k_scan_wide_list;
+  if (hipError_t e = allow_lds(grant_k_scan_wide_list, reinterpret_cast<const void *>(&k_scan_wide_list), lds)) return e;
+  const long long blocks = (a.nq + kWideQB - 1) / kWideQB;
+  hipLaunchKernelGGL(k_scan_wide_list, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kScanThreads), lds, s, a, dp, qlist, qcount);
   return hipGetLastError();
 }
 

@@ -468,7 +468,7 @@ class DeviceRegion(object):
         """Counters of the last filtered batch (see mlf_region_debug_stats in include/mlfriends_hip.h)."""
         out = np.zeros(19, dtype=np.uint64)
         check(_lib.lib().mlf_region_debug_stats(self._h, ptr(out), 19))
-        keys = ("ellipsoid_band", None, "uncertain_pairs", "largest_segment", "segments", "second_range_groups",
+        keys = ("ellipsoid_band", "exact_scan_queries", "uncertain_pairs", "largest_segment", "segments", "second_range_groups",
                 "uncertain_queries", "third_range_groups")
         stats = {k: int(v) for k, v in zip(keys, out[:8]) if k}
         stats["range_cuts"] = [int(out[16]), int(out[17])]      # tile cuts of the last min-only batch (second: 0 = two ranges)
