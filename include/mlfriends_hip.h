@@ -307,8 +307,15 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
  *               (d is the region's); a later mlf_region_set with another d clears it.
  *   set_center  the centre alone (the driver re-centres on every live-point replacement, integrator.py:2757-2758).
  *   clear       back to the ungated refill.
+ *   set_wide    the same over w columns, d <= w <= MLF_MAX_DIM (else MLF_E_BADARG / MLF_E_DIM): A is w x w, ctr and fixed_val
+ *               hold w values -- the t-region over the d parameters AND the w - d derived parameters of a user model, as the
+ *               driver builds it.  The handle keeps the width (set is set_wide with w = d; set_center uploads `width`
+ *               values).  While w != d only mlf_region_refill_user_derived_gated runs: mlf_region_refill and
+ *               mlf_region_refill_user return MLF_E_STATE (their kernels would read the w x w matrix as d x d).
  * mlf_region_refill_user with a t-region set needs a model created as MLF_USERMODEL_TREGION (else MLF_E_STATE). */
 int mlf_region_set_tregion(mlf_region *r, const double *A, const double *ctr, const double *fixed_val, double enlarge);
+int mlf_region_set_tregion_wide(mlf_region *r, size_t w, const double *A, const double *ctr, const double *fixed_val,
+                                double enlarge);
 int mlf_region_set_tregion_center(mlf_region *r, const double *ctr);
 int mlf_region_clear_tregion(mlf_region *r);
 /* raw Philox blocks (counter = (i, 0, stream, 0), key = seed) for known-answer tests */
@@ -639,7 +646,29 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
  *                   and compaction: out_p has room for capacity rows of d + nderived doubles and receives [p | q]; draws,
  *                   counts, u, L and the offset are those of mlf_region_refill_user with `model`.  No row inside the refill
  *                   changes its width.  A region with a t-region set returns MLF_E_STATE (the reference's t-region spans all
- *                   nparams columns, so its gate would need q before the likelihood: such a batch takes the host sequence). */
+ *                   nparams columns, so its gate would need q before the likelihood: that is the entry below).
+ *
+ * The t-region gate over derived parameters (MLF_USERMODEL_TREGION_DERIVED, _SUM_TREGION_DERIVED, _SUMS_TREGION_DERIVED: the three
+ * gated variants with -DMLF_USER_GATE_DERIVED=1, each its own code object).  The reference driver builds its t-region over all
+ * nparams = d + nderived columns, so the gate needs q BEFORE the likelihood: these programs are compiled, like the derive program,
+ * from the model's source followed by the derived source, and run per member row transform, mlf_user_derived, the gate over
+ * [p | q] (w = d + nderived columns, the arithmetic of mlf_region_set_tregion) and, only if it passes, the likelihood on the
+ * d-wide p row, in one launch.  AN OPT-IN ABOUT COST: mlf_user_derived then runs on every member row of the batch, not only on
+ * the kept rows.  Entries mlf_user_rows_tregion_derived / mlf_user_rows_sum_tregion_derived / mlf_user_rows_sums_tregion_derived:
+ * the parameters of their gated sibling, then (int nq, double *q_scratch).
+ *   compile_gate_derived  nsums = M for _SUMS_TREGION_DERIVED, 0 for the other two (else MLF_E_BADARG; compile_variant and
+ *                   compile_sums return MLF_E_BADARG for these variants).
+ *   create_gate_derived   records nderived (>= 1, d + nderived <= MLF_MAX_DIM, else MLF_E_DIM) and nterms (>= 1 for the summed
+ *                   variants, 0 for MLF_USERMODEL_TREGION_DERIVED); MLF_E_BADARG for a code object without the variant's entry.
+ *                   Such a handle runs in mlf_region_refill_user_derived_gated ONLY: every other evaluating entry (eval,
+ *                   eval_dev, the other refills, the walkers) returns MLF_E_STATE.
+ *   gate_derived_lds_bytes  introspection only: the dynamic LDS of one launch of mlf_user_rows_tregion_derived
+ *                   (mlf_user_rows_gate_derived_lds_bytes of the header); 0 means the direct form, or invalid arguments.
+ *   mlf_region_refill_user_derived_gated  mlf_region_refill_user_derived on a region whose t-region is d + nderived wide
+ *                   (mlf_region_set_tregion_wide): draws, counts, compaction and offsets are those of the gated
+ *                   mlf_region_refill_user, *nevaluated = count(accepted && gate), the rows stay d wide and the derive program
+ *                   extends the kept rows.  MLF_E_STATE without a t-region or for a model of another variant; MLF_E_BADARG
+ *                   where the t-region's width is not d + nderived or model and derive handle differ in nderived. */
 #define MLF_USERMODEL_DEFAULT 0
 #define MLF_USERMODEL_TREGION 1
 #define MLF_USERMODEL_SUM 2
@@ -647,6 +676,9 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
 #define MLF_USERMODEL_SUMS 4
 #define MLF_USERMODEL_SUMS_TREGION 5
 #define MLF_USERMODEL_DERIVED 6
+#define MLF_USERMODEL_TREGION_DERIVED 7
+#define MLF_USERMODEL_SUM_TREGION_DERIVED 8
+#define MLF_USERMODEL_SUMS_TREGION_DERIVED 9
 #define MLF_USERMODEL_MAX_SUMS 8
 int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant,
                                   void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap);
@@ -658,6 +690,11 @@ int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_
                              const double *aux, size_t naux, mlf_usermodel **out);
 int mlf_usermodel_create_derived(const void *code, size_t nbytes, size_t d, size_t nderived, const double *aux, size_t naux,
                                  mlf_usermodel **out);
+int mlf_usermodel_compile_gate_derived(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
+                                       void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap);
+int mlf_usermodel_create_gate_derived(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
+                                      size_t nderived, const double *aux, size_t naux, mlf_usermodel **out);
+int mlf_usermodel_gate_derived_lds_bytes(size_t d, size_t nderived, int has_p_buffer);
 int mlf_usermodel_derive(mlf_usermodel *derive, const double *p, size_t n, double *out);
 int mlf_usermodel_derive_dev(mlf_usermodel *derive, const double *d_p, size_t n, double *d_out, void *stream);
 int mlf_usermodel_derive_lds_bytes(size_t d, size_t nderived);
@@ -671,6 +708,9 @@ int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t 
 int mlf_region_refill_user_derived(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
                                    mlf_usermodel *model, mlf_usermodel *derive, double *out_u, double *out_p, double *out_L,
                                    size_t capacity, size_t *nevaluated, size_t *nkept, uint64_t *next_offset);
+int mlf_region_refill_user_derived_gated(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
+                                         mlf_usermodel *model, mlf_usermodel *derive, double *out_u, double *out_p, double *out_L,
+                                         size_t capacity, size_t *nevaluated, size_t *nkept, uint64_t *next_offset);
 int mlf_walkers_finish_user(mlf_walkers *w, double Lmin, mlf_usermodel *model, int64_t ringindex, double *rec);
 int mlf_walkers_step_user(mlf_walkers *w, double Lmin, double scale, int dirkind, double dirscale, uint64_t seed,
                           uint64_t offset, mlf_usermodel *model, double *rec, uint64_t *next_offset);

@@ -134,6 +134,7 @@ SIGNATURES = {
     "mlf_region_set_tregion": [_vp, _vp, _vp, _vp, _dbl],
     "mlf_region_set_tregion_center": [_vp, _vp],
     "mlf_region_clear_tregion": [_vp],
+    "mlf_region_set_tregion_wide": [_vp, _sz, _vp, _vp, _vp, _dbl],
     "mlf_usermodel_compile_variant": [ctypes.c_char_p, ctypes.c_char_p, _int, _int, _vp, _sz, _vp, _vp, _sz],
     "mlf_usermodel_compile_sums": [ctypes.c_char_p, ctypes.c_char_p, _int, _int, _int, _vp, _sz, _vp, _vp, _sz],
     "mlf_usermodel_create_variant": [_vp, _sz, _sz, _int, _int, _vp, _sz, _vp],
@@ -144,6 +145,11 @@ SIGNATURES = {
     "mlf_usermodel_derive_lds_bytes": [_sz, _sz],
     "mlf_region_refill_user_derived": [_vp, _int, _sz, ctypes.c_uint64, ctypes.c_uint64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp,
                                        _vp],
+    "mlf_usermodel_compile_gate_derived": [ctypes.c_char_p, ctypes.c_char_p, _int, _int, _int, _vp, _sz, _vp, _vp, _sz],
+    "mlf_usermodel_create_gate_derived": [_vp, _sz, _sz, _int, _int, _sz, _sz, _vp, _sz, _vp],
+    "mlf_usermodel_gate_derived_lds_bytes": [_sz, _sz, _int],
+    "mlf_region_refill_user_derived_gated": [_vp, _int, _sz, ctypes.c_uint64, ctypes.c_uint64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                             _vp, _vp],
     "mlf_walkers_finish_user": [_vp, _dbl, _vp, ctypes.c_int64, _vp],
     "mlf_walkers_step_user": [_vp, _dbl, _dbl, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp],
     "mlf_rwalk_create": [_vp, _sz, _sz, _sz],

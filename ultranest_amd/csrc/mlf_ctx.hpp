@@ -55,6 +55,10 @@ struct TregionGate {
   const double *A, *ctr, *fixed_val;
   double enlarge;
   uint8_t *member2;
+  // a gate over parameters AND derived parameters (the _TREGION_DERIVED variants): the width w = d + nderived of matrix, centre
+  // and fixed values (0: the model's d), and n rows of nderived doubles for the direct form's q rows
+  int width = 0;
+  double *q_scratch = nullptr;
 };
 bool usermodel_gated(const mlf_usermodel *m);   // loaded as the MLF_USERMODEL_TREGION variant: launches with a gate only
 int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
@@ -62,6 +66,9 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
 // a derive handle (MLF_USERMODEL_DERIVED): its number of derived columns (0 for every other handle) and one launch of its
 // mlf_user_derive_rows kernel on `s`: p (n, d) -> out (n, d + nderived), which must not overlap
 int usermodel_nderived(const mlf_usermodel *m);
+// a handle of a _TREGION_DERIVED variant: the number of derived columns its gate spans (0 for every other handle); it launches only
+// with a gate of width d + that number and a q_scratch
+int usermodel_gate_nderived(const mlf_usermodel *m);
 int usermodel_derive_rows(const mlf_usermodel *m, const double *p, long long n, double *out, hipStream_t s);
 
 }  // namespace mlf

@@ -227,11 +227,14 @@ struct mlf_region {
   mlf::DevBuf s_invT, s_lo, s_hi, s_thin, s_count, rf_p, rf_L, rf_out, rf_aux, rf_keep;
   mlf::DevBuf s_invT_pad, s_tc, s_wc, s_thc, s_gate;   // t-space sampling: padded invT, survivors of the cheap tests (rows, cube rows, thinning draws)
   bool axes_ready = false, sampling_ready = false;
-  // the driver's parameter-space wrapping ellipsoid (mlf_region_set_tregion): dense d x d matrix, centre, fixed values; the
-  // refill calls gate on it while tr_on.  rf_member2: accepted && gate of the batch under evaluation
+  // the driver's parameter-space wrapping ellipsoid (mlf_region_set_tregion / _wide): dense tr_w x tr_w matrix, centre, fixed
+  // values; the refill calls gate on it while tr_on.  tr_w is d, or d + nderived for the gate over a user model's derived
+  // parameters (mlf_region_refill_user_derived_gated alone runs then).  rf_member2: accepted && gate of the batch under evaluation
   mlf::DevBuf tr_A, tr_ctr, tr_fixed, rf_member2;
   mlf::DevBuf rf_wide;   // the kept rows as [p | q] of a refill with derived parameters (mlf_region_refill_user_derived)
+  mlf::DevBuf rf_q;      // the q rows of the batch under evaluation (mlf_region_refill_user_derived_gated, direct form)
   bool tr_on = false;
+  int tr_w = 0;
   double tr_enlarge = 0.0;
   std::vector<hipEvent_t> events;  // 4 per timed call
   size_t events_used = 0;

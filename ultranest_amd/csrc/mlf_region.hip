@@ -240,7 +240,7 @@ int mlf_region_destroy(mlf_region *r) {
                     &r->gen, &r->gen2, &r->cube, &r->smask, &r->blk, &r->sout, &r->ax_zero, &r->ax_mat,
                     &r->s_invT, &r->s_lo, &r->s_hi, &r->s_thin, &r->s_count, &r->rf_p, &r->rf_L, &r->rf_out, &r->rf_aux,
                     &r->rf_keep, &r->ax_pad, &r->s_invT_pad, &r->s_tc, &r->s_wc, &r->s_thc, &r->s_gate,
-                    &r->tr_A, &r->tr_ctr, &r->tr_fixed, &r->rf_member2, &r->rf_wide};
+                    &r->tr_A, &r->tr_ctr, &r->tr_fixed, &r->rf_member2, &r->rf_wide, &r->rf_q};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : r->events) (void)hipEventDestroy(e);
   r->filter.release();

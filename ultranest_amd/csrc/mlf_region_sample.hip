@@ -160,7 +160,8 @@ TregionGate region_tregion(const mlf_region *r) {
 // transform and the likelihood of the n rows (p into p_buf, or *prow = rows for the identity; L into L_buf).  With a t-region on
 // the handle, evaluate also fills r->rf_member2 = member && inside(p) (region_tregion): that mask replaces the membership
 // mask from there on and its count is *nevaluated; the choice between the two routes keeps using the region's count.
-// derive (a derive handle, or none): out_p receives the kept rows as [p | q], d + nderived wide (mlf_region_refill_user_derived).
+// derive (a derive handle, or none): out_p receives the kept rows as [p | q], d + nderived wide (mlf_region_refill_user_derived,
+// mlf_region_refill_user_derived_gated).
 template <class Evaluate>
 int region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin, Evaluate evaluate,
                   double *out_u, double *out_p, double *out_L, size_t capacity, size_t *nevaluated, size_t *nkept,
@@ -264,6 +265,8 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
   if (!r || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
     return fail_arg(MLF_E_BADARG, "null pointer");
   if (tkind < 0 || tkind > 2 || lkind < 0 || lkind > 3) return fail_arg(MLF_E_BADARG, "unknown transform / likelihood kind");
+  if (r->tr_on && r->tr_w != r->d)   // (the gate kernel would read the w x w matrix as d x d)
+    return fail_arg(MLF_E_STATE, "the region's t-region spans d + nderived columns: it gates mlf_region_refill_user_derived_gated only");
   if (lkind == 0 && !aux) return fail_arg(MLF_E_BADARG, "the Gaussian likelihood needs its centres");
   auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
                       const double **prow) -> int {
@@ -291,16 +294,25 @@ int mlf_region_refill(mlf_region *r, int method, size_t nsamples, uint64_t seed,
 int mlf_region_set_tregion(mlf_region *r, const double *A, const double *ctr, const double *fixed_val, double enlarge) {
   if (!r || !A || !ctr) return fail_arg(MLF_E_BADARG, "null pointer");
   if (!r->ready) return fail_arg(MLF_E_STATE, "region not set");
+  return mlf_region_set_tregion_wide(r, (size_t)r->d, A, ctr, fixed_val, enlarge);
+}
+
+int mlf_region_set_tregion_wide(mlf_region *r, size_t w, const double *A, const double *ctr, const double *fixed_val,
+                                double enlarge) {
+  if (!r || !A || !ctr) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!r->ready) return fail_arg(MLF_E_STATE, "region not set");
+  if (w < (size_t)r->d) return fail_arg(MLF_E_BADARG, "a t-region is at least as wide as the region (d <= w)");
+  if (w > MLF_MAX_DIM) return fail_arg(MLF_E_DIM, "t-region: width above MLF_MAX_DIM");
   hipStream_t s = g_ctx.stream;
-  const size_t d = (size_t)r->d;
   r->tr_on = false;
-  std::vector<double> fixed(d, NAN);
-  if (fixed_val) fixed.assign(fixed_val, fixed_val + d);
-  if (int rc = upload(r->tr_A, A, d * d * sizeof(double), s)) return rc;
-  if (int rc = upload(r->tr_ctr, ctr, d * sizeof(double), s)) return rc;
-  if (int rc = upload(r->tr_fixed, fixed.data(), d * sizeof(double), s)) return rc;
+  std::vector<double> fixed(w, NAN);
+  if (fixed_val) fixed.assign(fixed_val, fixed_val + w);
+  if (int rc = upload(r->tr_A, A, w * w * sizeof(double), s)) return rc;
+  if (int rc = upload(r->tr_ctr, ctr, w * sizeof(double), s)) return rc;
+  if (int rc = upload(r->tr_fixed, fixed.data(), w * sizeof(double), s)) return rc;
   CK(hipStreamSynchronize(s));
   r->tr_enlarge = enlarge;
+  r->tr_w = (int)w;
   r->tr_on = true;
   return 0;
 }
@@ -309,7 +321,7 @@ int mlf_region_set_tregion_center(mlf_region *r, const double *ctr) {
   if (!r || !ctr) return fail_arg(MLF_E_BADARG, "null pointer");
   if (!r->ready || !r->tr_on) return fail_arg(MLF_E_STATE, "no t-region set (mlf_region_set_tregion)");
   hipStream_t s = g_ctx.stream;
-  if (int rc = upload(r->tr_ctr, ctr, (size_t)r->d * sizeof(double), s)) return rc;
+  if (int rc = upload(r->tr_ctr, ctr, (size_t)r->tr_w * sizeof(double), s)) return rc;
   CK(hipStreamSynchronize(s));
   return 0;
 }
@@ -326,6 +338,8 @@ int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t 
   if (!r || !model || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
     return fail_arg(MLF_E_BADARG, "null pointer");
   if (r->ready && usermodel_dim(model) != r->d) return fail_arg(MLF_E_BADARG, "user model and region differ in dimensionality");
+  if (r->tr_on && r->tr_w != r->d)   // (the kernel would read the w x w matrix as d x d)
+    return fail_arg(MLF_E_STATE, "the region's t-region spans d + nderived columns: it gates mlf_region_refill_user_derived_gated only");
   if (r->tr_on != usermodel_gated(model))
     return fail_arg(MLF_E_STATE, r->tr_on ? "the region has a t-region: the user model must be loaded as MLF_USERMODEL_TREGION"
                                           : "user model loaded as MLF_USERMODEL_TREGION, but the region has no t-region");
@@ -362,6 +376,39 @@ int mlf_region_refill_user_derived(mlf_region *r, int method, size_t nsamples, u
     double *p = usermodel_has_transform(model) ? pbuf : nullptr;
     if (p) *prow = p;
     return usermodel_rows(model, rows, n, member, p, Lbuf, s);
+  };
+  return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
+                       next_offset, derive);
+}
+
+int mlf_region_refill_user_derived_gated(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
+                                         mlf_usermodel *model, mlf_usermodel *derive, double *out_u, double *out_p, double *out_L,
+                                         size_t capacity, size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
+  if (!r || !model || !derive || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
+    return fail_arg(MLF_E_BADARG, "null pointer");
+  const int nq = usermodel_gate_nderived(model);
+  if (nq == 0)
+    return fail_arg(MLF_E_STATE, "the user model is not of a _TREGION_DERIVED variant (mlf_usermodel_create_gate_derived)");
+  if (usermodel_nderived(derive) == 0) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+  if (usermodel_nderived(derive) != nq)
+    return fail_arg(MLF_E_BADARG, "user model and its derive program differ in the number of derived parameters");
+  if (usermodel_dim(derive) != usermodel_dim(model))
+    return fail_arg(MLF_E_BADARG, "user model and its derive program differ in dimensionality");
+  if (r->ready && usermodel_dim(model) != r->d) return fail_arg(MLF_E_BADARG, "user model and region differ in dimensionality");
+  if (!r->tr_on) return fail_arg(MLF_E_STATE, "no t-region set: the gated derived refill needs mlf_region_set_tregion_wide");
+  if (r->tr_w != r->d + nq)
+    return fail_arg(MLF_E_BADARG, "the t-region's width is not d + nderived (mlf_region_set_tregion_wide)");
+  // mlf_region_refill_user's evaluation with the gate over [p | q]: one launch computes p, q, the gate and the likelihood; the rows
+  // stay d wide, and region_refill widens the kept rows alone with the derive program, as without a t-region
+  auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
+                      const double **prow) -> int {
+    double *p = usermodel_has_transform(model) ? pbuf : nullptr;
+    if (p) *prow = p;
+    CK(r->rf_q.reserve((size_t)n * (size_t)nq * sizeof(double)));   // the direct form's q rows (the staged form keeps them in LDS)
+    TregionGate g = region_tregion(r);
+    g.width = r->tr_w;
+    g.q_scratch = r->rf_q.as<double>();
+    return usermodel_rows(model, rows, n, member, p, Lbuf, s, &g);
   };
   return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
                        next_offset, derive);

@@ -57,3 +57,21 @@ __device__ inline bool mlf_tregion_inside(const double *p, int d, const double *
   const double q = mlf_tregion_q<0>(d, delta, delta, [&](int j, int k) { return A[j * d + k]; });
   return ok && q <= enlarge;
 }
+
+#ifdef MLF_TREGION_SPLIT_ROW
+// The same test of a row that lies in two pieces: [p | q], p of d and q of nq doubles (unit stride each), against a matrix, centre
+// and fixed values over all w = d + nq columns (the t-region over a model's parameters and derived parameters, mlf_user_rows.hpp
+// with MLF_USER_GATE_DERIVED).  The arithmetic is mlf_tregion_q's, reached through an accessor: nothing is copied together first.
+// (Only for includers that ask for it: the text the others compile is what it was.)
+__device__ inline bool mlf_tregion_inside_split(const double *p, int d, const double *q, int nq, const double *__restrict__ A,
+                                                const double *__restrict__ ctr, const double *__restrict__ fixed_val,
+                                                double enlarge) {
+  const int w = d + nq;
+  bool ok = true;
+  for (int k = 0; k < d; ++k) ok = ok && mlf_tregion_fixed_ok(p[k], fixed_val[k]);
+  for (int k = 0; k < nq; ++k) ok = ok && mlf_tregion_fixed_ok(q[k], fixed_val[d + k]);
+  const auto delta = [&](int k) { return (k < d ? p[k] : q[k - d]) - ctr[k]; };   // k is a loop counter: a wave-uniform choice
+  const double form = mlf_tregion_q<0>(w, delta, delta, [&](int j, int k) { return A[j * w + k]; });
+  return ok && form <= enlarge;
+}
+#endif

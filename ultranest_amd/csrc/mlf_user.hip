@@ -35,6 +35,9 @@ struct mlf_usermodel {
   long long nterms = 0;
   int nderived = 0;     // the MLF_USERMODEL_DERIVED variant: fn is mlf_user_derive_rows, p (n, d) -> [p | q] (n, d + nderived); such a
                         // handle runs in the derive entries only
+  int gate_nq = 0;      // the _TREGION_DERIVED variants (gated is set too): the kernel computes this many derived columns per member
+                        // row, gates over d + gate_nq columns and takes (nq, q_scratch) behind the gate's five parameters; such a
+                        // handle runs in mlf_region_refill_user_derived_gated only
   long long naux = 0;
   DevBuf aux;
   DevBuf hu, hp, hL;   // staging of mlf_usermodel_eval (host arrays)
@@ -110,6 +113,7 @@ int usermodel_dim(const mlf_usermodel *m) { return m->d; }
 bool usermodel_has_transform(const mlf_usermodel *m) { return m->has_transform; }
 bool usermodel_gated(const mlf_usermodel *m) { return m->gated; }
 int usermodel_nderived(const mlf_usermodel *m) { return m->nderived; }
+int usermodel_gate_nderived(const mlf_usermodel *m) { return m->gate_nq; }
 
 int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
                    hipStream_t s, const TregionGate *gate) {
@@ -118,12 +122,21 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
   if (m->gated != (gate != nullptr))
     return fail_arg(MLF_E_STATE, m->gated ? "user model loaded as the t-region variant: it runs only in a refill with a t-region set"
                                           : "user model not loaded as the t-region variant (mlf_usermodel_create_variant)");
+  // a gate over derived columns is w = d + gate_nq wide and brings the q rows' scratch; every other gate is d wide
+  if (m->gate_nq ? (gate->width != m->d + m->gate_nq || gate->q_scratch == nullptr) : (gate != nullptr && gate->width != 0))
+    return fail_arg(MLF_E_STATE, m->gate_nq ? "user model loaded as a _TREGION_DERIVED variant: it runs only in "
+                                              "mlf_region_refill_user_derived_gated, with a t-region over d + nderived columns"
+                                            : "a t-region over d + nderived columns needs a user model loaded as a _TREGION_DERIVED "
+                                              "variant (mlf_usermodel_create_gate_derived)");
   if (n <= 0) return 0;
   // default form: one thread per row, 64 rows per workgroup; summed form: one wave (= one workgroup) per row
   const long long blocks = m->summed ? n : (n + 63) / 64;
   if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
   const bool p_buffer = p != nullptr && m->has_transform;
-  const unsigned lds = m->summed ? mlf_user_rows_sum_lds_bytes(m->d, p_buffer) : mlf_user_rows_lds_bytes(m->d, p_buffer);
+  const unsigned lds = m->gate_nq ? (m->summed ? mlf_user_rows_sum_gate_derived_lds_bytes(m->d, m->gate_nq, p_buffer)
+                                               : mlf_user_rows_gate_derived_lds_bytes(m->d, m->gate_nq, p_buffer))
+                       : m->summed ? mlf_user_rows_sum_lds_bytes(m->d, p_buffer)
+                                   : mlf_user_rows_lds_bytes(m->d, p_buffer);
   // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
   const double *a_u = u;
   long long a_n = n;
@@ -141,13 +154,20 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
     g_enlarge = gate->enlarge;
     g_member2 = gate->member2;
   }
-  // the first eight, nterms in the ninth place of a summed model, the gate's five behind them when gated
-  void *args[14] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
+  int g_nq = m->gate_nq;
+  double *g_scratch = gate ? gate->q_scratch : nullptr;
+  // the first eight, nterms in the ninth place of a summed model, the gate's five behind them when gated, (nq, q_scratch) behind
+  // those in a _TREGION_DERIVED variant
+  void *args[16] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
   int na = 8;
   if (m->summed) args[na++] = &a_nterms;
   if (gate) {
     void *g[] = {&g_A, &g_ctr, &g_fixed, &g_enlarge, &g_member2};
     for (void *x : g) args[na++] = x;
+  }
+  if (m->gate_nq) {
+    args[na++] = &g_nq;
+    args[na++] = &g_scratch;
   }
   CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
   return 0;
@@ -175,9 +195,17 @@ int usermodel_derive_rows(const mlf_usermodel *m, const double *p, long long n, 
 
 namespace {
 
-bool variant_gated(int v) { return v == MLF_USERMODEL_TREGION || v == MLF_USERMODEL_SUM_TREGION || v == MLF_USERMODEL_SUMS_TREGION; }
-bool variant_multi(int v) { return v == MLF_USERMODEL_SUMS || v == MLF_USERMODEL_SUMS_TREGION; }
-bool variant_summed(int v) { return v == MLF_USERMODEL_SUM || v == MLF_USERMODEL_SUM_TREGION || variant_multi(v); }
+// the gate over derived columns: the gated variants with MLF_USER_GATE_DERIVED=1
+bool variant_gate_derived(int v) {
+  return v == MLF_USERMODEL_TREGION_DERIVED || v == MLF_USERMODEL_SUM_TREGION_DERIVED || v == MLF_USERMODEL_SUMS_TREGION_DERIVED;
+}
+bool variant_gated(int v) {
+  return v == MLF_USERMODEL_TREGION || v == MLF_USERMODEL_SUM_TREGION || v == MLF_USERMODEL_SUMS_TREGION || variant_gate_derived(v);
+}
+bool variant_multi(int v) { return v == MLF_USERMODEL_SUMS || v == MLF_USERMODEL_SUMS_TREGION || v == MLF_USERMODEL_SUMS_TREGION_DERIVED; }
+bool variant_summed(int v) {
+  return v == MLF_USERMODEL_SUM || v == MLF_USERMODEL_SUM_TREGION || v == MLF_USERMODEL_SUM_TREGION_DERIVED || variant_multi(v);
+}
 
 // the checks every create entry makes before it touches the device
 int check_create_args(const void *code, size_t nbytes, size_t d) {
@@ -188,7 +216,7 @@ int check_create_args(const void *code, size_t nbytes, size_t d) {
 }
 
 // loads the code object as `variant` (arguments checked by the caller); nterms: 0 unless the variant is a summed one; nderived:
-// 0 unless the variant is MLF_USERMODEL_DERIVED
+// 0 unless the variant is MLF_USERMODEL_DERIVED (a derive handle) or a _TREGION_DERIVED one (the columns its gate spans)
 int load_model(const void *code, size_t d, int has_transform, int variant, size_t nterms, const double *aux, size_t naux,
                mlf_usermodel **out, size_t nderived = 0) {
   if (int rc = ensure_ctx()) return rc;
@@ -199,9 +227,13 @@ int load_model(const void *code, size_t d, int has_transform, int variant, size_
   m->gated = variant_gated(variant);
   m->summed = variant_summed(variant);
   m->nterms = (long long)nterms;
-  m->nderived = (int)nderived;
+  m->nderived = variant == MLF_USERMODEL_DERIVED ? (int)nderived : 0;
+  m->gate_nq = variant_gate_derived(variant) ? (int)nderived : 0;
   m->naux = (long long)naux;
   const char *entry = variant == MLF_USERMODEL_DERIVED ? "mlf_user_derive_rows"
+                      : variant == MLF_USERMODEL_TREGION_DERIVED      ? "mlf_user_rows_tregion_derived"
+                      : variant == MLF_USERMODEL_SUM_TREGION_DERIVED  ? "mlf_user_rows_sum_tregion_derived"
+                      : variant == MLF_USERMODEL_SUMS_TREGION_DERIVED ? "mlf_user_rows_sums_tregion_derived"
                       : variant_multi(variant) ? (m->gated ? "mlf_user_rows_sums_tregion" : "mlf_user_rows_sums")
                       : m->summed            ? (m->gated ? "mlf_user_rows_sum_tregion" : "mlf_user_rows_sum")
                                              : (m->gated ? "mlf_user_rows_tregion" : "mlf_user_rows");
@@ -232,6 +264,7 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
   const bool v_gated = variant_gated(variant);
   const bool v_summed = variant_summed(variant);
   const bool v_derived = variant == MLF_USERMODEL_DERIVED;
+  const bool v_gate_derived = variant_gate_derived(variant);
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
@@ -245,11 +278,12 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
   const std::string sums = "-DMLF_USER_NSUMS=" + std::to_string(nsums);
   // (a _SUMS variant adds its one option behind the others, and so does the derive program, which never calls the transform:
   // the other variants' programs are compiled as they were)
-  const char *opts[9] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
-                         has_transform && !v_derived ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
-                         v_gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
-                         v_summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0", v_derived ? "-DMLF_USER_DERIVED=1" : sums.c_str()};
-  const int nopts = variant_multi(variant) || v_derived ? 9 : 8;
+  const char *opts[10] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
+                          has_transform && !v_derived ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
+                          v_gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
+                          v_summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0", v_derived ? "-DMLF_USER_DERIVED=1" : sums.c_str()};
+  int nopts = variant_multi(variant) || v_derived ? 9 : 8;
+  if (v_gate_derived) opts[nopts++] = "-DMLF_USER_GATE_DERIVED=1";   // (behind whatever its gated sibling is compiled with)
   hiprtcProgram prog = nullptr;
   hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
   if (res != HIPRTC_SUCCESS) {
@@ -301,6 +335,8 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
 int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant, void *code_out,
                                   size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
   if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (variant_gate_derived(variant))
+    return fail_arg(MLF_E_BADARG, "a _TREGION_DERIVED variant is compiled with mlf_usermodel_compile_gate_derived");
   if (variant_multi(variant))
     return fail_arg(MLF_E_BADARG, "a user-model variant with several sums needs their number: mlf_usermodel_compile_sums");
   if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION && variant != MLF_USERMODEL_SUM &&
@@ -312,10 +348,21 @@ int mlf_usermodel_compile_variant(const char *source, const char *include_dir, i
 int mlf_usermodel_compile_sums(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
                                void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
   if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (!variant_multi(variant))
+  if (!variant_multi(variant) || variant_gate_derived(variant))
     return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_sums: the variant must be MLF_USERMODEL_SUMS or MLF_USERMODEL_SUMS_TREGION");
   if (nsums < 1 || nsums > MLF_USERMODEL_MAX_SUMS)
     return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_sums: nsums must be 1 to 8");
+  return compile_program(source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log, log_cap);
+}
+
+int mlf_usermodel_compile_gate_derived(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
+                                       void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
+  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!variant_gate_derived(variant))
+    return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_gate_derived: the variant must be MLF_USERMODEL_TREGION_DERIVED, "
+                                  "_SUM_TREGION_DERIVED or _SUMS_TREGION_DERIVED");
+  if (variant_multi(variant) ? (nsums < 1 || nsums > MLF_USERMODEL_MAX_SUMS) : nsums != 0)
+    return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_gate_derived: nsums must be 1 to 8 for _SUMS_TREGION_DERIVED, else 0");
   return compile_program(source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log, log_cap);
 }
 
@@ -328,6 +375,8 @@ int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int 
                                  size_t naux, mlf_usermodel **out) {
   if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
+  if (variant_gate_derived(variant))
+    return fail_arg(MLF_E_BADARG, "a _TREGION_DERIVED variant is loaded with mlf_usermodel_create_gate_derived");
   if (variant_summed(variant))
     return fail_arg(MLF_E_BADARG, "a summed user-model variant needs its number of terms: mlf_usermodel_create_sum");
   if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION)
@@ -340,7 +389,7 @@ int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_
                              const double *aux, size_t naux, mlf_usermodel **out) {
   if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
-  if (!variant_summed(variant))
+  if (!variant_summed(variant) || variant_gate_derived(variant))
     return fail_arg(MLF_E_BADARG, "mlf_usermodel_create_sum: the variant must be MLF_USERMODEL_SUM, _SUM_TREGION, _SUMS or _SUMS_TREGION");
   if (nterms == 0 || nterms > 0x7fffffffffffffffull) return fail_arg(MLF_E_BADARG, "a summed user model has at least one term");
   if (int rc = check_create_args(code, nbytes, d)) return rc;
@@ -355,6 +404,26 @@ int mlf_usermodel_create_derived(const void *code, size_t nbytes, size_t d, size
   if (int rc = check_create_args(code, nbytes, d)) return rc;
   if (nderived > MLF_MAX_DIM - d) return fail_arg(MLF_E_DIM, "user model: parameters and derived parameters above MLF_MAX_DIM");
   return load_model(code, d, 0, MLF_USERMODEL_DERIVED, 0, aux, naux, out, nderived);
+}
+
+int mlf_usermodel_create_gate_derived(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
+                                      size_t nderived, const double *aux, size_t naux, mlf_usermodel **out) {
+  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
+  *out = nullptr;
+  if (!variant_gate_derived(variant))
+    return fail_arg(MLF_E_BADARG, "mlf_usermodel_create_gate_derived: the variant must be MLF_USERMODEL_TREGION_DERIVED, "
+                                  "_SUM_TREGION_DERIVED or _SUMS_TREGION_DERIVED");
+  if (nderived == 0) return fail_arg(MLF_E_BADARG, "a gate over derived parameters has at least one derived parameter");
+  if (variant_summed(variant) ? (nterms == 0 || nterms > 0x7fffffffffffffffull) : nterms != 0)
+    return fail_arg(MLF_E_BADARG, "nterms: at least one term for a summed variant, 0 for MLF_USERMODEL_TREGION_DERIVED");
+  if (int rc = check_create_args(code, nbytes, d)) return rc;
+  if (nderived > MLF_MAX_DIM - d) return fail_arg(MLF_E_DIM, "user model: parameters and derived parameters above MLF_MAX_DIM");
+  return load_model(code, d, has_transform, variant, nterms, aux, naux, out, nderived);
+}
+
+int mlf_usermodel_gate_derived_lds_bytes(size_t d, size_t nderived, int has_p_buffer) {
+  if (d == 0 || nderived == 0 || d > MLF_MAX_DIM || nderived > MLF_MAX_DIM) return 0;
+  return (int)mlf_user_rows_gate_derived_lds_bytes((int)d, (int)nderived, has_p_buffer != 0);   // (at most MLF_USER_ROWS_LDS_BUDGET)
 }
 
 int mlf_usermodel_derive_lds_bytes(size_t d, size_t nderived) {

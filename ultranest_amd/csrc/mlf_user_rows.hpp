@@ -93,6 +93,26 @@
 //           leave with coalesced stores of (d + nq)-wide rows.  LDS per wave: 64 * (d + 1 + nq + 1) * 8 bytes.
 //   direct  one thread per row from and to global memory, where the staging would exceed MLF_USER_ROWS_LDS_BUDGET
 //           (d + nq >= 127).
+//
+// Gate over derived parameters (MLF_USER_TREGION=1 with MLF_USER_GATE_DERIVED=1, its own code objects, compiled like the derive
+// program from the model's source followed by the derived source: mlf_user_rows_tregion_derived, and with MLF_USER_SUM=1
+// mlf_user_rows_sum_tregion_derived / mlf_user_rows_sums_tregion_derived, each the only kernel of its program).  The driver's
+// t-region spans all w = d + nq columns of a model with derived parameters, so the gate needs q BEFORE the likelihood.  The entries
+// take the parameter list of their gated sibling, then `int nq, double *q_scratch`; tr_A is w x w, tr_ctr and tr_fixed hold w
+// values.  Per member row: transform_row writes the d-wide p row, mlf_user_derived(p, d, q, nq, aux, naux) writes q, the gate runs
+// over [p | q] (mlf_tregion_inside_split: the arithmetic of mlf_tregion_inside through an accessor, the two pieces are not copied
+// together), the likelihood is called on the d-wide p row only if the gate passes, member2[i] as in the gated kernels.  THE COST:
+// mlf_user_derived runs on every member row of the batch, not only on the rows that are kept.  p leaves at pitch d; q serves
+// the gate alone and is not written out (the derive program extends the kept rows afterwards, as without a t-region).
+//   default form, staged  the u, p and q rows of the wave's 64 rows in LDS at pitches d | 1, d | 1 and nq | 1 doubles: an ODD
+//           pitch P puts lane l's 8-byte word on banks 2 P l mod 64, distinct over each 32-lane half, for every d (the d + 1 of
+//           the forms above is odd only for even d).  LDS per wave: 64 * ((p buffer ? 2 : 1) * (d | 1) + (nq | 1)) * 8 bytes
+//           (mlf_user_rows_gate_derived_lds_bytes), within MLF_USER_ROWS_LDS_BUDGET; q_scratch is not touched.
+//   default form, direct  one thread per row from global memory where that exceeds the budget; q in q_scratch (n rows of nq
+//           doubles, the caller's).
+//   summed forms  lane 0 runs transform, derived function and gate; q sits in LDS behind the p row (nq more doubles:
+//           mlf_user_rows_sum_gate_derived_lds_bytes); the verdict is made wave-uniform as in the gated entries; q_scratch is
+//           not touched.  The order contract of the sums is untouched.
 #pragma once
 
 #define MLF_USER_ROWS_LDS_BUDGET 65536
@@ -115,6 +135,22 @@ __host__ __device__ inline unsigned mlf_user_rows_derive_lds_bytes(int d, int nq
   return bytes <= MLF_USER_ROWS_LDS_BUDGET ? (unsigned)bytes : 0u;
 }
 
+#if defined(MLF_USER_ROWS_HOST) || (defined(MLF_USER_GATE_DERIVED) && MLF_USER_GATE_DERIVED)
+// (for the library and the gate-derived programs only: the text every other program compiles is what it was)
+// bytes of dynamic LDS a launch of mlf_user_rows_tregion_derived needs (0: the direct form): 64 u rows and, where a transform
+// writes p, 64 p rows of pitch d | 1, and 64 q rows of pitch nq | 1
+__host__ __device__ inline unsigned mlf_user_rows_gate_derived_lds_bytes(int d, int nq, bool has_p_buffer) {
+  const unsigned long long bytes =
+      64ull * ((has_p_buffer ? 2ull : 1ull) * (unsigned long long)(d | 1) + (unsigned long long)(nq | 1)) * 8ull;
+  return bytes <= MLF_USER_ROWS_LDS_BUDGET ? (unsigned)bytes : 0u;
+}
+
+// bytes of dynamic LDS a launch of the summed gate-derived entries needs: the rows of the summed form and the q row behind them
+__host__ __device__ inline unsigned mlf_user_rows_sum_gate_derived_lds_bytes(int d, int nq, bool has_p_buffer) {
+  return mlf_user_rows_sum_lds_bytes(d, has_p_buffer) + (unsigned)nq * 8u;
+}
+#endif
+
 #ifndef MLF_USER_ROWS_HOST
 
 #ifndef MLF_USER_HAS_TRANSFORM
@@ -128,6 +164,15 @@ __host__ __device__ inline unsigned mlf_user_rows_derive_lds_bytes(int d, int nq
 #endif
 #ifndef MLF_USER_DERIVED
 #define MLF_USER_DERIVED 0
+#endif
+#ifndef MLF_USER_GATE_DERIVED
+#define MLF_USER_GATE_DERIVED 0
+#endif
+#if MLF_USER_GATE_DERIVED && (!MLF_USER_TREGION || MLF_USER_DERIVED)
+#error "MLF_USER_GATE_DERIVED is a mode of the gated programs (MLF_USER_TREGION=1), not of the derive program"
+#endif
+#if MLF_USER_GATE_DERIVED
+#define MLF_TREGION_SPLIT_ROW
 #endif
 #if MLF_USER_TREGION
 #include "mlf_tregion_dev.hpp"
@@ -188,6 +233,48 @@ __device__ inline void stage_out(double *dst, int total, int d, const double *ld
   }
 }
 
+#if MLF_USER_GATE_DERIVED
+// stage_in / stage_out at the caller's row pitch ds >= d (the gate-derived form: an odd pitch for every d).  Functions of their
+// own, so that the text the other programs compile -- and with it their code objects -- stays what it was.
+__device__ inline void stage_in_pitch(const double *src, int total, int d, int ds, double *lds, int lane) {
+  const int qstep = 64 / d, rstep = 64 % d;
+  int row = lane / d, col = lane % d;
+  for (int e0 = 0; e0 < total; e0 += 64 * kLoads) {
+    double v[kLoads];
+#pragma unroll
+    for (int i = 0; i < kLoads; ++i) {
+      const int e = e0 + 64 * i + lane;
+      v[i] = e < total ? src[e] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < kLoads; ++i) {
+      const int e = e0 + 64 * i + lane;
+      if (e < total) lds[row * ds + col] = v[i];
+      row += qstep;
+      col += rstep;
+      if (col >= d) {
+        col -= d;
+        row += 1;
+      }
+    }
+  }
+}
+
+__device__ inline void stage_out_pitch(double *dst, int total, int d, int ds, const double *lds, unsigned long long rows, int lane) {
+  const int qstep = 64 / d, rstep = 64 % d;
+  int row = lane / d, col = lane % d;
+  for (int e = lane; e < total; e += 64) {
+    if ((rows >> row) & 1ull) dst[e] = lds[row * ds + col];
+    row += qstep;
+    col += rstep;
+    if (col >= d) {
+      col -= d;
+      row += 1;
+    }
+  }
+}
+#endif
+
 __device__ inline void transform_row(const double *x, double *y, int d, const double *aux, long long naux) {
 #if MLF_USER_HAS_TRANSFORM
   mlf_user_transform(x, y, d, aux, naux);
@@ -240,6 +327,69 @@ extern "C" __global__ __launch_bounds__(64) void mlf_user_derive_rows(const doub
     for (int k = 0; k < d; ++k) y[k] = x[k];
     mlf_user_derived(x, d, y + d, nq, aux, naux);
   }
+}
+
+#elif MLF_USER_GATE_DERIVED && !MLF_USER_SUM
+
+extern "C" __global__ __launch_bounds__(64) void mlf_user_rows_tregion_derived(
+    const double *u, long long n, int d, const unsigned char *member, const double *aux, long long naux, double *p, double *L,
+    const double *__restrict__ tr_A, const double *__restrict__ tr_ctr, const double *__restrict__ tr_fixed, double tr_enlarge,
+    unsigned char *member2, int nq, double *q_scratch) {
+  using namespace mlf_user_detail;
+  const int lane = threadIdx.x;
+  const long long j0 = (long long)blockIdx.x * 64;
+  if (j0 >= n) return;
+  const long long left = n - j0;
+  const int nrows = left >= 64 ? 64 : (int)left;
+  const long long i = j0 + lane;
+  const bool mine = lane < nrows && (member == nullptr || member[i] != 0);
+  const unsigned long long live = __ballot(mine);
+  if (live == 0) {   // no member row in this block: nothing is read
+    if (lane < nrows) {
+      if (L != nullptr) L[i] = neg_inf();
+      member2[i] = 0;
+    }
+    return;
+  }
+  double like = neg_inf();
+  bool pass = false;
+  const bool p_buffer = p != nullptr && MLF_USER_HAS_TRANSFORM;
+  if (mlf_user_rows_gate_derived_lds_bytes(d, nq, p_buffer) != 0) {
+    extern __shared__ __attribute__((aligned(16))) double mlf_user_lds[];
+    const int ds = d | 1, qs = nq | 1;              // odd pitches: lane = row accesses without bank conflicts
+    double *a = mlf_user_lds;                       // 64 rows of u
+    double *b = p_buffer ? a + 64 * ds : a;         // 64 rows of p (the u rows themselves without a transform)
+    double *c = b + 64 * ds;                        // 64 rows of q
+    stage_in_pitch(u + j0 * d, nrows * d, d, ds, a, lane);
+    __syncthreads();
+    if (mine) {
+      const double *x = a + lane * ds;
+      if (p_buffer) {
+        double *y = b + lane * ds;
+        transform_row(x, y, d, aux, naux);
+        x = y;
+      }
+      double *q = c + lane * qs;
+      mlf_user_derived(x, d, q, nq, aux, naux);
+      pass = mlf_tregion_inside_split(x, d, q, nq, tr_A, tr_ctr, tr_fixed, tr_enlarge);
+      if (L != nullptr && pass) like = mlf_user_loglike(x, d, aux, naux);
+    }
+    __syncthreads();
+    if (p != nullptr) stage_out_pitch(p + j0 * d, nrows * d, d, ds, b, live, lane);
+  } else if (mine) {
+    const double *x = u + i * d;
+    if (p != nullptr) {
+      double *y = p + i * d;
+      transform_row(x, y, d, aux, naux);
+      x = y;
+    }
+    double *q = q_scratch + i * nq;
+    mlf_user_derived(x, d, q, nq, aux, naux);
+    pass = mlf_tregion_inside_split(x, d, q, nq, tr_A, tr_ctr, tr_fixed, tr_enlarge);
+    if (L != nullptr && pass) like = mlf_user_loglike(x, d, aux, naux);
+  }
+  if (lane < nrows) member2[i] = pass ? 1 : 0;   // pass implies mine
+  if (L != nullptr && lane < nrows) L[i] = like;
 }
 
 #elif !MLF_USER_SUM
@@ -321,11 +471,15 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const doubl
 
 #ifdef MLF_USER_NSUMS
 static_assert(MLF_USER_NSUMS >= 1 && MLF_USER_NSUMS <= 8, "MLF_USER_NSUMS: 1 to 8 sums");
-#if MLF_USER_TREGION
+#if MLF_USER_GATE_DERIVED
+#define MLF_USER_SUM_ENTRY mlf_user_rows_sums_tregion_derived
+#elif MLF_USER_TREGION
 #define MLF_USER_SUM_ENTRY mlf_user_rows_sums_tregion
 #else
 #define MLF_USER_SUM_ENTRY mlf_user_rows_sums
 #endif
+#elif MLF_USER_GATE_DERIVED
+#define MLF_USER_SUM_ENTRY mlf_user_rows_sum_tregion_derived
 #elif MLF_USER_TREGION
 #define MLF_USER_SUM_ENTRY mlf_user_rows_sum_tregion
 #else
@@ -340,6 +494,10 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(const double
                                                                const double *__restrict__ tr_A, const double *__restrict__ tr_ctr,
                                                                const double *__restrict__ tr_fixed, double tr_enlarge,
                                                                unsigned char *member2
+#endif
+#if MLF_USER_GATE_DERIVED
+                                                               ,
+                                                               int nq, double *q_scratch
 #endif
 ) {
   using namespace mlf_user_detail;
@@ -368,7 +526,16 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(const double
     __syncthreads();   // the other lanes read lane 0's p row from LDS
   }
 #endif
-#if MLF_USER_TREGION
+#if MLF_USER_GATE_DERIVED
+  (void)q_scratch;       // (the direct default form's: here q lives in LDS)
+  double *q = b + d;     // the q row, behind the p row (behind the u row where no transform writes one)
+  int inside = 0;
+  if (lane == 0) {
+    mlf_user_derived(b, d, q, nq, aux, naux);
+    inside = mlf_tregion_inside_split(b, d, q, nq, tr_A, tr_ctr, tr_fixed, tr_enlarge) ? 1 : 0;
+  }
+  const bool pass = __builtin_amdgcn_readfirstlane(inside) != 0;   // all 64 lanes are active: lane 0 is the first
+#elif MLF_USER_TREGION
   int inside = 0;
   if (lane == 0) inside = mlf_tregion_inside(b, d, tr_A, tr_ctr, tr_fixed, tr_enlarge) ? 1 : 0;
   const bool pass = __builtin_amdgcn_readfirstlane(inside) != 0;   // all 64 lanes are active: lane 0 is the first

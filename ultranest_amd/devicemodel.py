@@ -6,7 +6,7 @@ device functions, the package compiles them at run time for gfx950 (hiprtc) arou
 (``csrc/mlf_user_rows.hpp``) and hands back a pair of vectorized callbacks::
 
     model = DeviceModel(ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None,
-                        nderived=None, derived_source=None)
+                        nderived=None, derived_source=None, gate_derived=False)
     model.loglike(theta)    # (n, ndim) -> (n,)       vectorized callback, evaluated on the GPU
     model.transform(u)      # (n, ndim) -> (n, ndim)  vectorized callback (identity without a transform source)
 
@@ -76,10 +76,19 @@ once per refill, the harvested point of ``PopulationSliceSampler``.  It combines
 With ``identity_transform`` paired to the model's likelihood the host route yields no derived columns, so the device route
 yields none either (``device_route`` returns ``(model, False)`` and ``p`` is ``ndim`` wide).
 
-Not covered: a t-region (the driver's parameter-space wrapping ellipsoid) together with derived parameters -- the reference
-builds it over all ``num_params`` columns, so the gate would need ``q`` before the likelihood; ``refill(..., tregion=)`` returns
-None for such a model and the batch takes the host sequence through the callbacks above, which is correct -- and likelihoods
-that read derived columns.
+A t-region together with derived parameters (``gate_derived=True``).  The reference builds the driver's parameter-space
+wrapping ellipsoid over all ``num_params`` columns whenever the prior transform is not affine, so its gate needs ``q`` BEFORE the
+likelihood.  By default ``refill(..., tregion=)`` returns None for a model with ``nderived`` and the batch takes the host sequence
+through the callbacks above, which is correct and slow.  With ``gate_derived=True`` (it needs ``nderived``) the model has one
+more program, compiled on first gated use from ``source + "\n" + derived_source`` with ``-DMLF_USER_TREGION=1
+-DMLF_USER_GATE_DERIVED=1`` under its own cache key (``handle(with_transform, gated=True, derived=True)``): per member row
+transform, ``mlf_user_derived``, the gate over ``[p | q]``, and the likelihood on the ``ndim``-wide row if the gate passes, in
+one launch (``mlf_region_refill_user_derived_gated``); the rows stay ``ndim`` wide and the derive program extends the kept rows as
+without a t-region.  The flag is an opt-in because it is a statement about COST: ``mlf_user_derived`` then runs on every member
+row of a gated batch, not only on the kept rows.  It applies where ``tregion_on_device(tregion, ndim + Q)`` holds and the model is
+paired with its own transform; without the flag every object, cache key, program and route is what it was.
+
+Not covered: likelihoods that read derived columns.
 
 Likelihoods summed over data terms (``nterms=K``)
 -------------------------------------------------
@@ -182,6 +191,7 @@ GATE_HEADER = os.path.join(INCLUDE_DIR, "mlf_tregion_dev.hpp")      # included b
 VARIANT_DEFAULT, VARIANT_TREGION, VARIANT_SUM, VARIANT_SUM_TREGION = 0, 1, 2, 3     # MLF_USERMODEL_* of include/mlfriends_hip.h
 VARIANT_SUMS, VARIANT_SUMS_TREGION = 4, 5
 VARIANT_DERIVED = 6
+VARIANT_TREGION_DERIVED, VARIANT_SUM_TREGION_DERIVED, VARIANT_SUMS_TREGION_DERIVED = 7, 8, 9
 MAX_SUMS = 8                                                                        # MLF_USERMODEL_MAX_SUMS
 MAX_DIM = 1024                                                                      # MLF_MAX_DIM
 # what mlf_usermodel_compile passes to hiprtc besides -I, -DMLF_USER_HAS_TRANSFORM, -DMLF_USER_TREGION, -DMLF_USER_SUM and (with
@@ -242,6 +252,24 @@ def _derive_cache_key(source):
     return h.hexdigest()
 
 
+def _gate_derived_cache_key(source, has_transform, summed=False, nsums=None):
+    """the key of a gate-derived program (`source`: the model's source followed by its derived source): that of its gated
+    sibling over that source, with " gate_derived" among its options"""
+    h = hashlib.sha256()
+    header = b""
+    for path in (HEADER, GATE_HEADER):
+        with open(path, "rb") as fh:
+            header += fh.read()
+    options = repr((COMPILE_OPTIONS, bool(has_transform))) + " tregion gate_derived"
+    if summed:
+        options += " sum"
+    if nsums is not None:
+        options += " sums=%d" % nsums
+    for part in (source.encode(), b"\0", options.encode(), b"\0", header):
+        h.update(part)
+    return h.hexdigest()
+
+
 def _cache_key(source, has_transform, gated=False, summed=False, nsums=None):
     h = hashlib.sha256()
     with open(HEADER, "rb") as fh:
@@ -260,19 +288,10 @@ def _cache_key(source, has_transform, gated=False, summed=False, nsums=None):
     return h.hexdigest()
 
 
-def compile_model(source, has_transform, gated=False, summed=False, nsums=None):
-    """The gfx950 code object (bytes) of `source` + the wrapper kernel; cached per process.  gated: the variant with the
-    t-region test between transform and likelihood (module docstring), another program under its own key.  summed: the
-    one-wave-per-row form around ``mlf_user_loglike_term`` (module docstring), two more programs under their own keys.
-    nsums=M (with summed): M sums and a final function (``mlf_user_loglike_terms`` / ``_finish``), two more programs per M."""
+def _compile_cached(key, call):
+    """The code object under `key`, from the cache or from ``call(library, buf, cap, size, log)`` (one of the library's compile
+    entries; once more with the reported size where the buffer was too small)."""
     global compile_calls
-    nsums = _check_nsums(nsums, summed)
-    if nsums is None:
-        key = _cache_key(source, has_transform, gated, summed)
-        variant = (VARIANT_TREGION if gated else VARIANT_DEFAULT) + (VARIANT_SUM if summed else 0)
-    else:
-        key = _cache_key(source, has_transform, gated, summed, nsums=nsums)
-        variant = VARIANT_SUMS_TREGION if gated else VARIANT_SUMS
     code = _code_cache.get(key)
     if code is not None:
         return code
@@ -283,15 +302,7 @@ def compile_model(source, has_transform, gated=False, summed=False, nsums=None):
     for _ in range(2):
         buf = ctypes.create_string_buffer(cap)
         compile_calls += 1
-        if nsums is not None:
-            rc = L.mlf_usermodel_compile_sums(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), variant, nsums,
-                                              buf, cap, ctypes.byref(size), log, len(log))
-        elif variant != VARIANT_DEFAULT:
-            rc = L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)),
-                                                 variant, buf, cap, ctypes.byref(size), log, len(log))
-        else:
-            rc = L.mlf_usermodel_compile(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), buf, cap,
-                                         ctypes.byref(size), log, len(log))
+        rc = call(L, buf, cap, size, log)
         if rc == MLF_E_COMPILE:
             raise DeviceModelCompileError(log.value.decode(errors="replace"))
         if rc != 0 and size.value > cap:      # code object larger than the buffer: once more with its size
@@ -304,33 +315,55 @@ def compile_model(source, has_transform, gated=False, summed=False, nsums=None):
     return code
 
 
+def compile_model(source, has_transform, gated=False, summed=False, nsums=None):
+    """The gfx950 code object (bytes) of `source` + the wrapper kernel; cached per process.  gated: the variant with the
+    t-region test between transform and likelihood (module docstring), another program under its own key.  summed: the
+    one-wave-per-row form around ``mlf_user_loglike_term`` (module docstring), two more programs under their own keys.
+    nsums=M (with summed): M sums and a final function (``mlf_user_loglike_terms`` / ``_finish``), two more programs per M."""
+    nsums = _check_nsums(nsums, summed)
+    if nsums is None:
+        key = _cache_key(source, has_transform, gated, summed)
+        variant = (VARIANT_TREGION if gated else VARIANT_DEFAULT) + (VARIANT_SUM if summed else 0)
+    else:
+        key = _cache_key(source, has_transform, gated, summed, nsums=nsums)
+        variant = VARIANT_SUMS_TREGION if gated else VARIANT_SUMS
+
+    def call(L, buf, cap, size, log):
+        if nsums is not None:
+            return L.mlf_usermodel_compile_sums(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), variant, nsums,
+                                                buf, cap, ctypes.byref(size), log, len(log))
+        if variant != VARIANT_DEFAULT:
+            return L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)),
+                                                   variant, buf, cap, ctypes.byref(size), log, len(log))
+        return L.mlf_usermodel_compile(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), buf, cap,
+                                       ctypes.byref(size), log, len(log))
+
+    return _compile_cached(key, call)
+
+
 def compile_derived(source):
     """The gfx950 code object of the derive program of `source` (a model's source followed by its derived source): the
     wrapper compiled with ``-DMLF_USER_DERIVED=1``, ``mlf_user_derive_rows`` its only kernel; cached per process."""
-    global compile_calls
-    key = _derive_cache_key(source)
-    code = _code_cache.get(key)
-    if code is not None:
-        return code
-    L = _lib.lib()
-    size = ctypes.c_size_t(0)
-    log = ctypes.create_string_buffer(1 << 16)
-    cap = 1 << 20
-    for _ in range(2):
-        buf = ctypes.create_string_buffer(cap)
-        compile_calls += 1
-        rc = L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), 0, VARIANT_DERIVED, buf, cap,
-                                             ctypes.byref(size), log, len(log))
-        if rc == MLF_E_COMPILE:
-            raise DeviceModelCompileError(log.value.decode(errors="replace"))
-        if rc != 0 and size.value > cap:
-            cap = size.value
-            continue
-        check(rc)
-        break
-    code = buf.raw[:size.value]
-    _code_cache[key] = code
-    return code
+    def call(L, buf, cap, size, log):
+        return L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), 0, VARIANT_DERIVED, buf, cap,
+                                               ctypes.byref(size), log, len(log))
+
+    return _compile_cached(_derive_cache_key(source), call)
+
+
+def compile_gate_derived(source, has_transform, summed=False, nsums=None):
+    """The gfx950 code object of the gate-derived program of `source` (a model's source followed by its derived source): the
+    gated wrapper compiled with ``-DMLF_USER_GATE_DERIVED=1`` as well, whose only kernel computes the derived columns of every
+    member row and gates over ``[p | q]`` (module docstring); cached per process under its own key."""
+    nsums = _check_nsums(nsums, summed)
+    variant = (VARIANT_SUMS_TREGION_DERIVED if nsums is not None else
+               VARIANT_SUM_TREGION_DERIVED if summed else VARIANT_TREGION_DERIVED)
+
+    def call(L, buf, cap, size, log):
+        return L.mlf_usermodel_compile_gate_derived(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), variant,
+                                                    nsums or 0, buf, cap, ctypes.byref(size), log, len(log))
+
+    return _compile_cached(_gate_derived_cache_key(source, has_transform, summed, nsums), call)
 
 
 class UserModelSpec(object):
@@ -402,22 +435,40 @@ class _DeriveHandle(_Handle):
         self.has_transform = False
 
 
+class _GateDerivedHandle(_Handle):
+    """The loaded gate-derived program of a model (``mlf_usermodel_create_gate_derived``)."""
+
+    def __init__(self, code, ndim, has_transform, aux, nderived, nterms=None, nsums=None):
+        h = ctypes.c_void_p()
+        variant = (VARIANT_SUMS_TREGION_DERIVED if nsums is not None else
+                   VARIANT_SUM_TREGION_DERIVED if nterms is not None else VARIANT_TREGION_DERIVED)
+        check(_lib.lib().mlf_usermodel_create_gate_derived(code, len(code), int(ndim), int(bool(has_transform)), variant,
+                                                           int(nterms or 0), int(nderived), ptr(aux), len(aux), ctypes.byref(h)))
+        self._h = h
+        self.has_transform = bool(has_transform)
+
+
 class DeviceModel(object):
     """A likelihood (and optional prior transform) written as HIP device functions (module docstring).  nterms=K: the
     summed form, whose likelihood source defines ``mlf_user_loglike_term`` and whose L is the sum of its K terms in the
     documented order.  nterms=K, nsums=M (1 <= M <= 8): the source defines ``mlf_user_loglike_terms`` (M terms per data
     index) and ``mlf_user_loglike_finish`` (L from the M sums) instead; each sum follows that order.  nderived=Q with
     derived_source (``mlf_user_derived``): Q derived columns behind the parameters, ``nparams == ndim + Q``; every route keeps
-    its ndim-wide rows and the derive program extends the rows that are handed out."""
+    its ndim-wide rows and the derive program extends the rows that are handed out.  gate_derived=True (with nderived): a region
+    refill with a t-region over all ``ndim + Q`` columns runs on the device, at the cost of ``mlf_user_derived`` on every member
+    row of such a batch (module docstring); without it such a refill returns None and the batch takes the host sequence."""
 
     _count = 0
 
     def __init__(self, ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None,
-                 nderived=None, derived_source=None):
+                 nderived=None, derived_source=None, gate_derived=False):
         self.ndim = int(ndim)
         if self.ndim <= 0:
             raise ValueError("ndim must be positive")
         self.nderived = _check_nderived(self.ndim, nderived, derived_source)
+        if gate_derived and self.nderived is None:
+            raise ValueError("gate_derived needs nderived and derived_source: it gates the t-region over the derived parameters")
+        self.gate_derived = bool(gate_derived)
         self.nparams = self.ndim + (self.nderived or 0)
         if nterms is not None:
             if isinstance(nterms, bool) or not isinstance(nterms, (int, np.integer)):
@@ -435,6 +486,7 @@ class DeviceModel(object):
         self.code = self._compile(self.has_transform, False)
         # the derive program: the model's source (helpers included) followed by the derived source; the main programs above
         # are compiled from self.source alone, as those of the model without nderived
+        self.derived_source = derived_source
         self.derive_code = None if self.nderived is None else compile_derived(self.source + "\n" + derived_source)
         self._handles = {}
         self.loglike = _Callback(self, "loglike")
@@ -449,12 +501,30 @@ class DeviceModel(object):
             return compile_model(self.source, tr, gated=gated, summed=True, nsums=self.nsums)
         return compile_model(self.source, tr, gated=gated, summed=self.summed)
 
-    def handle(self, with_transform=True, gated=False):
+    def compile_gate_derived(self, with_transform=True):
+        """The code object of the model's gate-derived program (needs no GPU; cached per process)."""
+        if self.nderived is None:
+            raise ValueError("%s has no derived parameters (nderived)" % self.name)
+        return compile_gate_derived(self.source + "\n" + self.derived_source, bool(with_transform and self.has_transform),
+                                    summed=self.summed, nsums=self.nsums)
+
+    def handle(self, with_transform=True, gated=False, derived=False):
         """The loaded model (created on first use: needs the GPU).  with_transform=False: the variant whose prior
         transform is the identity (a route that pairs this model's likelihood with ``identity_transform``).  gated=True:
         the variant with the t-region test (compiled and loaded on first gated use; it runs in a gated refill only).  A summed
-        model (``nterms``) loads its own programs under its own keys, and so does one of several sums (``nsums``)."""
+        model (``nterms``) loads its own programs under its own keys, and so does one of several sums (``nsums``).
+        gated=True, derived=True: the gate over ``[p | q]`` (a model with ``nderived``; compiled and loaded on first such use; it
+        runs in ``mlf_region_refill_user_derived_gated`` only)."""
         tr = bool(with_transform and self.has_transform)
+        if derived:
+            if not gated:
+                raise ValueError("derived=True names the gate over the derived parameters: it needs gated=True")
+            key = (tr, "gate_derived")
+            h = self._handles.get(key)
+            if h is None:
+                h = self._handles[key] = _GateDerivedHandle(self.compile_gate_derived(tr), self.ndim, tr, self.aux, self.nderived,
+                                                            nterms=self.nterms, nsums=self.nsums)
+            return h.handle
         key = (tr, True) if gated else tr
         if self.summed:
             key = (tr, bool(gated), "sum" if self.nsums is None else "sums")
@@ -563,5 +633,5 @@ def extend_derived(user, p):
     return user[0].derive(p[None, :])[0] if p.ndim == 1 else user[0].derive(p)
 
 
-__all__ = ["DeviceModel", "DeviceModelCompileError", "UserModelSpec", "compile_model", "compile_derived", "device_route",
-           "extend_derived"]
+__all__ = ["DeviceModel", "DeviceModelCompileError", "UserModelSpec", "compile_model", "compile_derived", "compile_gate_derived",
+           "device_route", "extend_derived"]

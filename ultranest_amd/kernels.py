@@ -369,20 +369,26 @@ class DeviceRegion(object):
     def set_sampling_data(self, invT, bbox_lo, bbox_hi):
         check(_lib.lib().mlf_region_set_sampling_data(self._h, ptr(f64(invT)), ptr(f64(bbox_lo)), ptr(f64(bbox_hi))))
 
-    def set_tregion(self, A, center, fixed_val, enlarge):
+    def set_tregion(self, A, center, fixed_val, enlarge, width=None):
         """The driver's parameter-space wrapping ellipsoid for the refill calls that follow (mlf_region_set_tregion): dense
-        (d, d) matrix, (d,) centre, (d,) fixed values (NaN = variable dimension) or None."""
-        d = self._d
+        (d, d) matrix, (d,) centre, (d,) fixed values (NaN = variable dimension) or None.  width=w > d: the t-region over the d
+        parameters and w - d derived parameters of a user model (mlf_region_set_tregion_wide), arrays of w."""
+        d = self._d if width is None else int(width)
         A, center = f64(A), f64(center)
         fixed_val = None if fixed_val is None else f64(fixed_val)
         if A.shape != (d, d) or center.shape != (d,) or (fixed_val is not None and fixed_val.shape != (d,)):
             raise ValueError("t-region arrays do not match the region's %d dimensions" % d)
-        check(_lib.lib().mlf_region_set_tregion(self._h, ptr(A), ptr(center), ptr(fixed_val), float(enlarge)))
+        if width is None:
+            check(_lib.lib().mlf_region_set_tregion(self._h, ptr(A), ptr(center), ptr(fixed_val), float(enlarge)))
+        else:
+            check(_lib.lib().mlf_region_set_tregion_wide(self._h, d, ptr(A), ptr(center), ptr(fixed_val), float(enlarge)))
+        self._tregion_width = d
 
     def set_tregion_center(self, center):
         center = f64(center)
-        if center.shape != (self._d,):
-            raise ValueError("t-region centre does not match the region's %d dimensions" % self._d)
+        width = getattr(self, "_tregion_width", self._d)      # the width of the last set_tregion
+        if center.shape != (width,):
+            raise ValueError("t-region centre does not match the t-region's %d dimensions" % width)
         check(_lib.lib().mlf_region_set_tregion_center(self._h, ptr(center)))
 
     def clear_tregion(self):
@@ -417,6 +423,13 @@ class DeviceRegion(object):
         (``mlf_region_refill_user_derived``); u, L, the count and the offset are those of `refill_user`."""
         return self._refill(_lib.lib().mlf_region_refill_user_derived, method, nsamples, seed, offset, Lmin, capacity, model, derive,
                             pwidth=self._d + int(nderived))
+
+    def refill_user_derived_gated(self, method, nsamples, seed, offset, Lmin, model, derive, nderived, capacity=None):
+        """`refill_user_derived` under a t-region over all d + nderived columns (set with ``set_tregion(..., width=)``): `model`
+        is the model's gate-derived handle, which computes the derived columns of every member row for the gate
+        (``mlf_region_refill_user_derived_gated``); the count is that of the rows that pass it."""
+        return self._refill(_lib.lib().mlf_region_refill_user_derived_gated, method, nsamples, seed, offset, Lmin, capacity, model,
+                            derive, pwidth=self._d + int(nderived))
 
     def _refill(self, fn, method, nsamples, seed, offset, Lmin, capacity, *evaluation, pwidth=None):
         """The call of `fn` (mlf_region_refill or its user variant) that `evaluation`, its arguments between Lmin and

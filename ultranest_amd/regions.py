@@ -404,25 +404,37 @@ class _DeviceState(object):
         return self._draw(region, use_scan, method, "refill_user_derived", nsamples, Lmin, model.handle(True),
                           model.derive_handle(), model.nderived)
 
+    def refill_user_derived_gated(self, region, use_scan, method, nsamples, Lmin, model, tregion):
+        """`refill_user_derived` under a `tregion` over all ``ndim + nderived`` columns, for a model that opted in with
+        ``gate_derived=True``: its gate-derived program computes the derived columns of every member row, gates over ``[p | q]``
+        and evaluates the rows that pass, in one launch; the kept rows come back as ``[p | q]``."""
+        return self._draw(region, use_scan, method, "refill_user_derived_gated", nsamples, Lmin,
+                          model.handle(True, gated=True, derived=True), model.derive_handle(), model.nderived,
+                          tregion=tregion, width=model.nparams)
+
     def sample(self, region, use_scan, method, nsamples):
         """Device-side draw + membership + compaction with the region's ``device_rng``."""
         return self._draw(region, use_scan, method, "sample", nsamples)[0]
 
-    def _draw(self, region, use_scan, method, call, nsamples, *args, tregion=None):
+    def _draw(self, region, use_scan, method, call, nsamples, *args, tregion=None, width=None):
         """handle.<call>(method, nsamples, seed, offset, *args) at the region's ``device_rng`` position, which moves on to the
         next offset; returns the call's results without that offset.  The refill calls run with the handle's t-region
-        brought to `tregion` (None: none)."""
+        brought to `tregion` (None: none); width: the number of columns it spans where that is not the region's (a user model's
+        parameters and derived parameters)."""
         handle = self._prepare_sampling(region, use_scan, method)
-        if call != "sample":
+        if call != "sample" and width is not None:
+            self.sync_tregion(handle, tregion, width, wide=True)
+        elif call != "sample":
             self.sync_tregion(handle, tregion, region.u.shape[1] if tregion is not None else 0)
         rng = region.device_rng
         *out, rng.offset = getattr(handle, call)(method, nsamples, rng.seed, rng.offset, *args)
         return tuple(out)
 
-    def sync_tregion(self, handle, tregion, ndim):
+    def sync_tregion(self, handle, tregion, ndim, wide=False):
         """Keep the handle's copy of the driver's t-region current: nothing for an unchanged one, the centre alone after
         ``update_center`` (every iteration of the driver), a full set for another object, matrix, enlargement or set of
-        fixed values, a clear for None."""
+        fixed values, a clear for None.  wide: `ndim` is the t-region's own width, which the handle is told
+        (``set_tregion(..., width=ndim)``: a user model's parameters and derived parameters)."""
         old = self.tregion
         if tregion is None:
             if old is not None:
@@ -436,7 +448,10 @@ class _DeviceState(object):
                 handle.set_tregion_center(ctr)
                 self.tregion = old[:2] + (ctr.copy(),) + old[3:]
             return
-        handle.set_tregion(A, ctr, fixed, enlarge)
+        if wide:
+            handle.set_tregion(A, ctr, fixed, enlarge, width=ndim)
+        else:
+            handle.set_tregion(A, ctr, fixed, enlarge)
         self.tregion = (tregion, A.copy(), ctr.copy(), fixed, enlarge)
 
     def _prepare_sampling(self, region, use_scan, method):
@@ -845,7 +860,10 @@ class MLFriends(_LivePoints):
         `tregion`: the driver's parameter-space ``WrappingEllipsoid`` (integrator.py:1789-1804).  Its ``inside`` test then
         runs on the device between transform and likelihood, in the arithmetic of the host test; the likelihood counts
         only for the rows of the region that pass, and ``nc`` is their number.  None is returned for a tregion that cannot
-        go to the device (``tregion_on_device``), and for any tregion together with a user model's derived parameters.
+        go to the device (``tregion_on_device``), and for any tregion together with a user model's derived parameters unless
+        the model opted in with ``DeviceModel(..., gate_derived=True)``: the tregion then has to span all ``ndim + Q`` columns
+        (the driver's does), the derived columns of every member row are computed for the gate inside the one launch
+        (``mlf_region_refill_user_derived_gated``), and a constant derived column is a fixed dimension of the tregion.
 
         A user model with derived parameters (``DeviceModel(..., nderived=Q)``) paired with its own transform returns ``p`` of
         shape ``(nkept, ndim + Q)``: the batch runs ``ndim`` wide and the derive kernel extends the kept rows."""
@@ -862,14 +880,17 @@ class MLFriends(_LivePoints):
         if method >= 2 and not self._device_tspace():
             return None
         gate = {}     # without a tregion the device calls keep their positional form
+        derived = user is not None and user[1] and user[0].nderived is not None
+        gate_derived = derived and user[0].gate_derived     # the model's opt-in: its tregion spans the derived columns too
         if tregion is not None:
-            if not tregion_on_device(tregion, self.u.shape[1]):
+            if not tregion_on_device(tregion, user[0].nparams if gate_derived else self.u.shape[1]):
                 return None
             gate = dict(tregion=tregion)
-        derived = user is not None and user[1] and user[0].nderived is not None
-        if derived and tregion is not None:
+        if derived and tregion is not None and not gate_derived:
             return None     # the tregion spans the derived columns too: the gate would need them (host sequence)
-        if derived:
+        if derived and tregion is not None:
+            u, p, L, nc = self._dev.refill_user_derived_gated(self, self._uses_scan(), method, nsamples, Lmin, user[0], tregion)
+        elif derived:
             u, p, L, nc = self._dev.refill_user_derived(self, self._uses_scan(), method, nsamples, Lmin, user[0])
         elif user is not None:
             u, p, L, nc = self._dev.refill_user(self, self._uses_scan(), method, nsamples, Lmin, *user, **gate)
@@ -1059,7 +1080,8 @@ class WrappingEllipsoid(object):
 
 def tregion_on_device(tregion, ndim):
     """Whether the device refill can apply `tregion` (``MLFriends.refill``): a ``WrappingEllipsoid`` with its own ``inside``,
-    its ellipsoid created and ``enlarge`` set, over `ndim` parameters (derived parameters keep the host route)."""
+    its ellipsoid created and ``enlarge`` set, over `ndim` columns (the cube's dimensionality; with a user model that opted
+    in with ``gate_derived=True``, its parameters and derived parameters)."""
     if not isinstance(tregion, WrappingEllipsoid) or type(tregion).inside is not WrappingEllipsoid.inside:
         return False
     inv, ctr = getattr(tregion, "ellipsoid_invcov", None), getattr(tregion, "ellipsoid_center", None)
