@@ -34,7 +34,8 @@ extern "C" {
 
 /* Largest dimensionality of the K1-K5 / H3 / T1 / R3 entry points.  Up to 128 the templated kernels; 129 ... 1024 the
  * run-time-dimensionality kernels (csrc/mlf_wide.hip: exact binary64 scan only, no matrix-core pre-filter).  Entry points
- * that stop earlier and say so with MLF_E_DIM: mlf_walkers_create (d <= 128: one wave per walker, lane = coordinate pair),
+ * that stop earlier and say so with MLF_E_DIM: mlf_rwalk_create and mlf_sslice_create (d <= 128: one wave per walker, lane =
+ * coordinate pair; mlf_walkers_create goes up to MLF_MAX_DIM, above 128 with the wide form of the direction draw),
  * mlf_col_extent (d <= 128), mlf_bootstrap_factor (d <= 64; above: mlf_bootstrap_moments + mlf_bootstrap_quadmax);
  * the single-launch small-batch path of mlf_region_inside (up to 256 host proposals) is used for d <= 128 and the batched
  * pipeline above. */

@@ -156,7 +156,8 @@ __global__ void k_walk_brackets(WalkState w, const long long *idx, int n, double
   }
 }
 
-// ---- wave-per-walker kernels: lane = coordinate (d <= 128: two coordinates per lane) ----------------
+// ---- wave-per-walker kernels: the lanes stride over the row (the direction draw up to 128 dimensions: two coordinates per
+// lane; above: its wide form, template parameter WIDE) ----------------
 // One thread per walker read its rows with a 8 d-byte stride between lanes (every load a different cache
 // line) and walked them serially: 0.93 ms per step at 10^5 walkers x 50, ~25 us of pure latency per kernel at
 // 100 walkers.  Here a wave owns one walker: rows are read coalesced, per-walker scalars are computed by all
@@ -166,21 +167,28 @@ __global__ void k_walk_brackets(WalkState w, const long long *idx, int n, double
 
 // setup_brackets with a device-side direction draw for a walker whose bracket is undefined (popstepsampler.py:483-505).
 // `t`, `left`, `right`, `sl`, `sr` are the wave's copies of the walker state (updated here); vr (optional) receives the
-// lane's coordinates of the new direction.
+// lane's coordinates of the new direction.  WIDE (d > kNarrowDirMaxDim, chosen by the launchers: wave-uniform): the row is
+// written by dw_direction_wide, which stages the normals of kinds 2 and 4 in the workgroup's LDS; there is no vr.
+template <bool WIDE>
 __device__ void dw_brackets_philox(const WalkState &w, int i, int lane, double scale, int kind, double dirscale,
                                    const WalkDirData &dd, unsigned long long seed, unsigned long long offset, double &t,
                                    double &left, double &right, bool &sl, bool &sr, double *vr_out = nullptr) {
   if (isfinite(t)) return;   // wave-uniform
   const int d = w.d;
   double *v = w.currentv + (size_t)i * d;
-  double vr[2];
-  dw_direction(w, i, lane, kind, dirscale, dd, seed, offset, vr);
+  if constexpr (WIDE) {
+    __shared__ double gs[kWideDirMaxDim];
+    dw_direction_wide(d, i, lane, kind, dirscale, dd, seed, offset, v, gs);
+  } else {
+    double vr[2];
+    dw_direction(w, i, lane, kind, dirscale, dd, seed, offset, vr);
 #pragma unroll
-  for (int h = 0; h < 2; ++h)
-    if (lane + 64 * h < d) v[lane + 64 * h] = vr[h];
-  if (vr_out) {
-    vr_out[0] = vr[0];
-    vr_out[1] = vr[1];
+    for (int h = 0; h < 2; ++h)
+      if (lane + 64 * h < d) v[lane + 64 * h] = vr[h];
+    if (vr_out) {
+      vr_out[0] = vr[0];
+      vr_out[1] = vr[1];
+    }
   }
   left = -scale;
   right = scale;
@@ -196,6 +204,7 @@ __device__ void dw_brackets_philox(const WalkState &w, int i, int lane, double s
   }
 }
 
+template <bool WIDE>
 __global__ __launch_bounds__(64) void k_walk_brackets_philox(WalkState w, double scale, int kind, double dirscale,
                                                              WalkDirData dd, unsigned long long seed,
                                                              unsigned long long offset, const StepParams *sp) {
@@ -209,7 +218,7 @@ __global__ __launch_bounds__(64) void k_walk_brackets_philox(WalkState w, double
   for (int i = blockIdx.x; i < w.P; i += gridDim.x) {   // several walkers per wave: 10^5 one-wave workgroups are dispatch bound
     double t = w.currentt[i], left = w.left[i], right = w.right[i];
     bool sl = w.sl[i] != 0, sr = w.sr[i] != 0;
-    dw_brackets_philox(w, i, lane, scale, kind, dirscale, dd, seed, offset, t, left, right, sl, sr);
+    dw_brackets_philox<WIDE>(w, i, lane, scale, kind, dirscale, dd, seed, offset, t, left, right, sl, sr);
   }
 }
 
@@ -538,6 +547,7 @@ __global__ __launch_bounds__(64) void k_walk_restart_philox(WalkState w, const d
 // proposal, prior transform.  was_starting feeds the ring-index shift in the harvest kernel.  step_back
 // looks at all G chain slots: slots past a walker's generation hold NaN, so this equals the reference's
 // window of max(generation) + 1 slots.
+template <bool WIDE>
 __device__ void dw_prologue(const WalkState &w, int i, int lane, const double *live, const double *Ls, int nlive, int dirkind,
                             const WalkDirData &dd, int tkind, double ta, double tb, uint8_t *was_starting, const StepParams &p) {
   long long gen = w.generation[i];
@@ -563,7 +573,7 @@ __device__ void dw_prologue(const WalkState &w, int i, int lane, const double *l
   gen = __shfl(gen, 0, 64);
   t = __shfl(t, 0, 64);
   dw_restart_philox(w, i, lane, live, Ls, nlive, p.Lmin, p.seed, p.offset, gen);
-  dw_brackets_philox(w, i, lane, p.scale, dirkind, p.dirscale, dd, p.seed, p.offset, t, left, right, sl, sr);
+  dw_brackets_philox<WIDE>(w, i, lane, p.scale, dirkind, p.dirscale, dd, p.seed, p.offset, t, left, right, sl, sr);
   // the rows written above (restart point, direction) are read back by other lanes of this wave
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -571,13 +581,14 @@ __device__ void dw_prologue(const WalkState &w, int i, int lane, const double *l
   dw_propose(w, i, lane, nullptr, p.seed, p.offset, gen, t, left, right, sl, sr, tkind, ta, tb);
 }
 
+template <bool WIDE>
 __global__ __launch_bounds__(64) void k_walk_prologue(WalkState w, const double *live, const double *Ls, int nlive,
                                                       int dirkind, WalkDirData dd, int tkind, double ta, double tb,
                                                       uint8_t *was_starting, StepParams p, const StepParams *sp) {
   const int lane = threadIdx.x;
   if (sp) p = *sp;
   for (int i = blockIdx.x; i < w.P; i += gridDim.x)
-    dw_prologue(w, i, lane, live, Ls, nlive, dirkind, dd, tkind, ta, tb, was_starting, p);
+    dw_prologue<WIDE>(w, i, lane, live, Ls, nlive, dirkind, dd, tkind, ta, tb, was_starting, p);
 }
 
 // ------------------------------------------------------------------ several rounds per launch ----
@@ -595,10 +606,11 @@ __global__ __launch_bounds__(64) void k_walk_prologue(WalkState w, const double 
 // Round r draws from the Philox counters of call r of the call-by-call path (offset + r * per_call), and every stage is
 // the same device function, so the state after the launch sequence is bit for bit the state after R calls of
 // mlf_walkers_step_dev (tests/test_popstepsampler.py::test_rounds_equal_single_steps).
+template <bool WIDE>
 __device__ void dw_round(const RoundsArgs &a, int i, int lane, int r, const StepParams &p0) {
   StepParams p = p0;
   p.offset = p0.offset + (unsigned long long)r * a.per_call;
-  dw_prologue(a.w, i, lane, a.live, a.Ls, a.nlive, a.dirkind, a.dd, a.tkind, a.ta, a.tb, a.was_starting, p);
+  dw_prologue<WIDE>(a.w, i, lane, a.live, a.Ls, a.nlive, a.dirkind, a.dd, a.tkind, a.ta, a.tb, a.was_starting, p);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -690,13 +702,13 @@ __device__ int dw_rounds_regs(const RoundsArgs &a, int i, int lane, int r0, int 
                                          // -- the memory form draws a direction for it all the same, which nothing ever reads)
       bool bsl = sl != 0, bsr = sr != 0;
       double vr[2];
-      dw_brackets_philox(w, i, lane, p0.scale, a.dirkind, p0.dirscale, a.dd, p0.seed, offset, tcur, left, right, bsl, bsr, vr);
+      dw_brackets_philox<false>(w, i, lane, p0.scale, a.dirkind, p0.dirscale, a.dd, p0.seed, offset, tcur, left, right, bsl, bsr, vr);
       sl = bsl ? 1 : 0;
       sr = bsr ? 1 : 0;
       v = vr[0];
     } else if (gen < 0 && !isfinite(tcur)) {
       bool bsl = sl != 0, bsr = sr != 0;
-      dw_brackets_philox(w, i, lane, p0.scale, a.dirkind, p0.dirscale, a.dd, p0.seed, offset, tcur, left, right, bsl, bsr, nullptr);
+      dw_brackets_philox<false>(w, i, lane, p0.scale, a.dirkind, p0.dirscale, a.dd, p0.seed, offset, tcur, left, right, bsl, bsr, nullptr);
       sl = bsl ? 1 : 0;
       sr = bsr ? 1 : 0;
     }
@@ -794,9 +806,10 @@ __device__ __forceinline__ bool rounds_in_registers(const RoundsArgs &a) {
   return !(a.w.d & 1) && a.w.d <= 64 && a.w.nparams == a.w.d && (a.ly.kind == 0 || a.ly.kind < 0) && !a.force_memory_form;
 }
 
+template <bool WIDE>
 __global__ __launch_bounds__(64) void k_walk_round0(RoundsArgs a) {
   const StepParams p = *a.sp;
-  for (int i = blockIdx.x; i < a.w.P; i += gridDim.x) dw_round(a, i, threadIdx.x, 0, p);
+  for (int i = blockIdx.x; i < a.w.P; i += gridDim.x) dw_round<WIDE>(a, i, threadIdx.x, 0, p);
 }
 
 // setup_start's ring shift (:456-462), as k_walk_harvest makes it, and the hand-shake words of the launch that follows
@@ -829,12 +842,14 @@ __global__ __launch_bounds__(256) void k_walk_pick(RoundsArgs a) {
 // index stays where round 0 left it.  Workgroups 1 ...: the other walkers, each making round r as soon as the ring walker has
 // committed to it (dw_rounds_regs, role 2).  Before: k_walk_ring (the ring walker alone, R rounds), THEN k_walk_rest (everybody else,
 // the same R rounds): 84 us median / 148 mean per call at C3's shape.
+// WIDE (d > kNarrowDirMaxDim): the memory form only -- the register form stays at even d <= 64.
+template <bool WIDE>
 __global__ __launch_bounds__(64) void k_walk_rounds(RoundsArgs a) {
   const WalkState &w = a.w;
   const StepParams p = *a.sp;
   const int lane = threadIdx.x;
   const int ring = a.ctl[1];
-  const bool regs = rounds_in_registers(a);
+  const bool regs = !WIDE && rounds_in_registers(a);
   __shared__ LayerLds lds;
   RoundsArgs al = a;
   if (blockIdx.x != 0 || a.phase == 2) {
@@ -855,14 +870,14 @@ __global__ __launch_bounds__(64) void k_walk_rounds(RoundsArgs a) {
         if (regs) {
           dw_rounds_regs(al, i, lane, 1, R, false, p, 0);
         } else {
-          for (int r = 1; r < R; ++r) dw_round(a, i, lane, r, p);
+          for (int r = 1; r < R; ++r) dw_round<WIDE>(a, i, lane, r, p);
         }
       } else if (regs) {
         dw_rounds_regs(al, i, lane, 1, a.max_rounds, false, p, 2);
       } else {
         for (int r = 1; r < a.max_rounds; ++r) {
           if (!follower_may_make(a.ctl, r, lane)) break;
-          dw_round(a, i, lane, r, p);
+          dw_round<WIDE>(a, i, lane, r, p);
         }
       }
     }
@@ -883,7 +898,7 @@ __global__ __launch_bounds__(64) void k_walk_rounds(RoundsArgs a) {
   } else {
     while (w.generation[ring] != (long long)(w.G - 1) && R < a.max_rounds) {
       ring_commits(a.ctl, R, lane);
-      dw_round(a, ring, lane, R, p);
+      dw_round<WIDE>(a, ring, lane, R, p);
       ++R;
     }
   }
@@ -1170,6 +1185,11 @@ static inline dim3 grid_for(long long n, int block = 256) { return dim3((unsigne
 // wave-per-walker kernels: one one-wave workgroup per walker (fewer, looping waves measured slower: 0.88 vs 0.71 ms
 // per step at 10^5 walkers); the loop in the kernels only matters beyond 4 M walkers
 static inline dim3 walker_grid(int P) { return dim3((unsigned)(P < (1 << 22) ? P : (1 << 22))); }
+// the wide kernels (d > kNarrowDirMaxDim): a walker is several passes of its wave over the row and up to d / 8 passes over the
+// axes matrix, and its workgroup holds 8 KiB of LDS: no more one-wave workgroups than the chip has wave slots (256 CUs x 4 SIMDs
+// x 8), each walking the population with that stride
+static inline dim3 wide_walker_grid(int P) { return dim3((unsigned)(P < (1 << 13) ? P : (1 << 13))); }
+static inline bool wide_walkers(const WalkState &w) { return w.d > kNarrowDirMaxDim; }
 
 void launch_walk_reset(const WalkState &w, hipStream_t s) {
   const long long n = (long long)w.P * w.G * w.d;
@@ -1193,8 +1213,12 @@ void launch_walk_restart_philox(const WalkState &w, const double *live, const do
 void launch_walk_prologue(const WalkState &w, const double *live, const double *Ls, int nlive, int dirkind, WalkDirData dd,
                           int tkind, double ta, double tb, uint8_t *was_starting, const StepParams &p, const StepParams *sp,
                           hipStream_t s) {
-  hipLaunchKernelGGL(k_walk_prologue, walker_grid(w.P), dim3(64), 0, s, w, live, Ls, nlive, dirkind, dd, tkind, ta, tb,
-                     was_starting, p, sp);
+  if (wide_walkers(w))
+    hipLaunchKernelGGL(k_walk_prologue<true>, wide_walker_grid(w.P), dim3(64), 0, s, w, live, Ls, nlive, dirkind, dd, tkind, ta,
+                       tb, was_starting, p, sp);
+  else
+    hipLaunchKernelGGL(k_walk_prologue<false>, walker_grid(w.P), dim3(64), 0, s, w, live, Ls, nlive, dirkind, dd, tkind, ta, tb,
+                       was_starting, p, sp);
 }
 
 void launch_walk_start(const WalkState &w, const long long *idx, int n, const double *rows, const double *L,
@@ -1216,8 +1240,12 @@ void launch_walk_brackets(const WalkState &w, const long long *idx, int n, doubl
 
 void launch_walk_brackets_philox(const WalkState &w, double scale, int kind, double dirscale, WalkDirData dd,
                                  unsigned long long seed, unsigned long long offset, hipStream_t s, const StepParams *sp) {
-  hipLaunchKernelGGL(k_walk_brackets_philox, walker_grid(w.P), dim3(64), 0, s, w, scale, kind, dirscale, dd, seed,
-                     offset, sp);
+  if (wide_walkers(w))
+    hipLaunchKernelGGL(k_walk_brackets_philox<true>, wide_walker_grid(w.P), dim3(64), 0, s, w, scale, kind, dirscale, dd, seed,
+                       offset, sp);
+  else
+    hipLaunchKernelGGL(k_walk_brackets_philox<false>, walker_grid(w.P), dim3(64), 0, s, w, scale, kind, dirscale, dd, seed,
+                       offset, sp);
 }
 
 void launch_walk_propose(const WalkState &w, const double *unif, unsigned long long seed, unsigned long long offset,
@@ -1252,8 +1280,9 @@ void launch_walk_scatter_live(const double *rows, const double *Ls, const long l
   hipLaunchKernelGGL(k_walk_scatter_live, grid_for((long long)n * d), dim3(256), 0, s, rows, Ls, idx, n, d, live, liveL);
 }
 
-void launch_walk_rounds(const RoundsArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_walk_round0, walker_grid(a.w.P), dim3(64), 0, s, a);
+template <bool WIDE>
+static void launch_walk_rounds_form(const RoundsArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_walk_round0<WIDE>, WIDE ? wide_walker_grid(a.w.P) : walker_grid(a.w.P), dim3(64), 0, s, a);
   hipLaunchKernelGGL(k_walk_pick, dim3(1), dim3(256), 0, s, a);
   // populations the chip holds at once: one launch, the followers trail the ring walker.  Larger ones are throughput-bound: the
   // ring walker first, alone (its rounds are quick with nobody next to it), then everybody else (popsize 100 000, d = 50:
@@ -1261,14 +1290,21 @@ void launch_walk_rounds(const RoundsArgs &a, hipStream_t s) {
   RoundsArgs b = a;
   if (a.w.P <= 4096) {
     b.phase = 0;
-    hipLaunchKernelGGL(k_walk_rounds, dim3(walker_grid(a.w.P).x + 1), dim3(64), 0, s, b);
+    hipLaunchKernelGGL(k_walk_rounds<WIDE>, dim3(walker_grid(a.w.P).x + 1), dim3(64), 0, s, b);
   } else {
     b.phase = 1;
-    hipLaunchKernelGGL(k_walk_rounds, dim3(1), dim3(64), 0, s, b);
+    hipLaunchKernelGGL(k_walk_rounds<WIDE>, dim3(1), dim3(64), 0, s, b);
     b.phase = 2;   // 2048 workgroups walk the population: the layer matrix is staged 2048 times, not once per walker, and a call
                    // without further rounds does not pay for 10^5 workgroups that start (33 KB of LDS each) only to leave
-    hipLaunchKernelGGL(k_walk_rounds, dim3(2048), dim3(64), 0, s, b);
+    hipLaunchKernelGGL(k_walk_rounds<WIDE>, dim3(2048), dim3(64), 0, s, b);
   }
+}
+
+void launch_walk_rounds(const RoundsArgs &a, hipStream_t s) {
+  if (wide_walkers(a.w))
+    launch_walk_rounds_form<true>(a, s);
+  else
+    launch_walk_rounds_form<false>(a, s);
   const int nchunks = (a.w.P + kStatsChunk - 1) / kStatsChunk;
   if (nchunks <= 1 || !a.rparts) {
     hipLaunchKernelGGL(k_walk_round_stats, dim3((unsigned)a.max_rounds), dim3(256), 0, s, a);

@@ -48,6 +48,13 @@ struct StepParams {
   unsigned long long seed, offset;
 };
 
+// Two forms of the device-side direction draw (mlf_walk_dev.hpp), chosen by the launchers on d: dw_direction holds two
+// coordinates per lane (the resident slice walkers up to kNarrowDirMaxDim dimensions, and the whole-population samplers of
+// mlf_rwalk.hip / mlf_sslice.hip, which stop there); dw_direction_wide strides over the row and stages kWideDirMaxDim normals
+// in LDS (the resident slice walkers above).
+constexpr int kNarrowDirMaxDim = 128;
+constexpr int kWideDirMaxDim = 1024;    // = MLF_MAX_DIM (mlf_walk_api.hip asserts it)
+
 // direction generators on the device (Philox); kinds follow the reference functions
 enum WalkDirection {
   DIR_CUBE_ORIENTED = 0,          // stepfuncs.pyx:348-370

@@ -18,6 +18,8 @@
 
 using namespace mlf;
 
+static_assert(kWideDirMaxDim == MLF_MAX_DIM, "dw_direction_wide stages MLF_MAX_DIM normals in LDS");
+
 // Device copies of what the region and the live points contribute, with the state of their setters: shared by the three
 // population handles (mlf_walkers, mlf_rwalk, mlf_sslice)
 struct RegionCopies {
@@ -621,7 +623,10 @@ int mlf_walkers_create(mlf_walkers **out, size_t popsize, size_t nsteps, size_t 
   *out = nullptr;
   if (popsize == 0 || nsteps == 0 || d == 0 || popsize > (1u << 24) || nsteps > 65535)
     return fail_arg(MLF_E_BADARG, "mlf_walkers_create: popsize, nsteps, d must be positive");
-  if (d > 128) return fail_arg(MLF_E_DIM, "the resident walkers (one wave per walker, lane = coordinate pair) cover up to 128 dimensions");
+  if (d > MLF_MAX_DIM)
+    return fail_arg(MLF_E_DIM, "the resident walkers (one wave per walker, the lanes striding over the row) cover up to MLF_MAX_DIM = 1024 dimensions");
+  // walker * d + coordinate is an int in the element-per-thread kernels (k_walk_start / points / brackets)
+  if (popsize * d > 0x7fffffffull) return fail_arg(MLF_E_BADARG, "mlf_walkers_create: population too large");
   if (int rc = ensure_ctx()) return rc;
   mlf_walkers *w = new mlf_walkers();
   w->P = (int)popsize;

@@ -159,6 +159,106 @@ __device__ inline void dw_direction(const WalkState &w, int i, int lane, int kin
   }
 }
 
+// ---- the wide form of dw_direction: kNarrowDirMaxDim < d <= kWideDirMaxDim (the resident slice walkers, mlf_walk.hip) ------
+// Same Philox layout, same kinds, one wave per walker; the row goes straight to v (the walker's row of currentv: d doubles in
+// global memory) instead of two registers per lane, lane l writing coordinates l, l + 64, ...  Kinds 0, 1, 3, 5 (and both
+// branches of 6) are dw_direction's selections, one multiplication, or one subtraction and one multiplication per coordinate:
+// the same doubles.  Kinds 2 and 4 stage the d normals in LDS (gs: kWideDirMaxDim doubles of the calling one-wave workgroup;
+// lane l draws the Box-Muller PAIRS p = l, l + 64, ... -- one Philox block, one logarithm and one square root per pair -- and
+// writes g[2 p], g[2 p + 1]).  SUMMATION ORDERS (no FMA; every wide caller goes through this one function, so the per-step
+// route, the graph replay and the memory form of the rounds agree bit for bit):
+//   squared norm   lane l adds g[2 p]^2, then g[2 p + 1]^2 (where 2 p + 1 < d), for p = l, l + 64, ... ascending, into one
+//                  partial starting at 0; the 64 partials are combined by wave_sum's xor tree (offsets 32, 16, 8, 4, 2, 1).
+//                  f = dirscale / sqrt(sum), g[c] <- g[c] * f.
+//   kind 4         v[r] = sum_c axes[r][c] * g[c]: lane l adds the products of c = l, l + 64, ... ascending into one partial
+//                  starting at 0 (a coalesced read of row r; eight rows in flight); the 64 partials of a row are combined by
+//                  the xor tree with offsets 32, 16, 8, 4, 2, 1, at every level own + partner's.  (For offsets 32, 16, 8 the
+//                  tree of eight rows is folded -- a lane keeps the half of the rows its bit selects and sends the other --
+//                  which changes who holds a sum, not the sum.)
+__device__ __forceinline__ void wave_lds_sync() {   // LDS written by some lanes of the wave, read by others
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ inline void dw_direction_wide(int d, int i, int lane, int kind, double dirscale, const WalkDirData &dd,
+                                         unsigned long long seed, unsigned long long offset, double *v, double *gs) {
+  const int npairs = (d + 1) / 2;
+  const unsigned long long base = offset + (unsigned long long)i * (unsigned long long)(npairs + 2);
+  unsigned pick[4];
+  philox_block(seed, 2u, base, pick);
+  int k = kind;
+  if (k == DIR_MIXTURE) k = (u01(pick[2], pick[3]) < 0.5) ? DIR_DIFFERENTIAL : DIR_REGION_ORIENTED;
+  if (k == DIR_CUBE_ORIENTED || k == DIR_CUBE_ORIENTED_SCALED) {
+    const int j = (int)below(pick[0], (unsigned)d);
+    const double x = (k == DIR_CUBE_ORIENTED) ? dirscale : dirscale * dd.std[j];
+    for (int c = lane; c < d; c += 64) v[c] = c == j ? x : 0.0;
+  } else if (k == DIR_REGION_ORIENTED) {
+    const int j = (int)below(pick[0], (unsigned)d);
+    const double *row = dd.axes + (size_t)j * d;
+    for (int c = lane; c < d; c += 64) v[c] = row[c] * dirscale;
+  } else if (k == DIR_DIFFERENTIAL) {
+    const unsigned a = below(pick[0], (unsigned)dd.nlive);
+    unsigned b = below(pick[1], (unsigned)(dd.nlive - 1));
+    if (b >= a) ++b;
+    const double *ra = dd.live + (size_t)a * d, *rb = dd.live + (size_t)b * d;
+    for (int c = lane; c < d; c += 64) v[c] = (ra[c] - rb[c]) * dirscale;
+  } else {   // DIR_RANDOM, DIR_REGION_RANDOM: isotropic unit vector of length dirscale
+    wave_lds_sync();   // (the walker this wave served before has read gs)
+    double part = 0.0;
+    for (int p = lane; p < npairs; p += 64) {   // (what is written lies below d <= kWideDirMaxDim: inside gs)
+      unsigned r4[4];
+      philox_block(seed, 2u, base + 1 + p, r4);
+      const double rad = sqrt(-2.0 * log(u01(r4[0], r4[1])));
+      const double ang = 2.0 * M_PI * u01(r4[2], r4[3]);
+      const double g0 = rad * cos(ang), g1 = rad * sin(ang);
+      gs[2 * p] = g0;
+      part += g0 * g0;
+      if (2 * p + 1 < d) {
+        gs[2 * p + 1] = g1;
+        part += g1 * g1;
+      }
+    }
+    const double f = dirscale / sqrt(wave_sum(part));
+    wave_lds_sync();
+    if (k == DIR_RANDOM) {
+      for (int c = lane; c < d; c += 64) v[c] = gs[c] * f;
+    } else {   // v[r] = sum_c axes[r][c] * v1[c]   (einsum 'ij,kj->ki', stepfuncs.pyx:476)
+      for (int c = lane; c < d; c += 64) gs[c] = gs[c] * f;   // (the lane that scales an element is the one that reads it below)
+      for (int r0 = 0; r0 < d; r0 += 8) {
+        double acc[8];
+        const double *rows[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          acc[j] = 0.0;
+          rows[j] = dd.axes + (size_t)(r0 + j < d ? r0 + j : d - 1) * d;   // past the last row: read it again, never written
+        }
+        for (int c = lane; c < d; c += 64) {
+          const double gc = gs[c];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] += rows[j][c] * gc;
+        }
+        // offsets 32, 16, 8: the lane keeps rows [0, n) of what it holds where its bit is clear, [n, 2 n) where it is set
+#pragma unroll
+        for (int level = 0; level < 3; ++level) {
+          const int n = 4 >> level, off = 32 >> level;
+          const bool upper = (lane & off) != 0;
+#pragma unroll
+          for (int j = 0; j < n; ++j) {
+            const double keep = upper ? acc[j + n] : acc[j];
+            const double send = upper ? acc[j] : acc[j + n];
+            acc[j] = keep + __shfl_xor(send, off, 64);
+          }
+        }
+        double s = acc[0];
+        for (int off = 4; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        const int r = r0 + ((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1);
+        if ((lane & 7) == 0 && r < d) v[r] = s;
+      }
+    }
+  }
+}
+
 // ---- a proposal on the line and its built-in prior transform (the whole-population samplers: mlf_rwalk.hip, mlf_sslice.hip)
 __device__ __forceinline__ double rwalk_move(double u, double v, double t) {
   const double step = v * t;

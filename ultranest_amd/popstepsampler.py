@@ -20,10 +20,11 @@ Likelihood: any ``loglike(p) -> L`` / ``transform(u) -> p`` numpy callbacks (the
 proposals then make one round trip), or the device likelihoods of ``ultranest_amd.likelihoods``
 (objects with ``device_spec``), which are evaluated in place on the device, or a user model's callbacks
 (``ultranest_amd.devicemodel.DeviceModel``: HIP device functions compiled at run time), which run per step on the
-device (no graph replay, no multi-round kernel).
+device (no graph replay, no multi-round kernel).  All of this holds up to 1024 dimensions (``MLF_MAX_DIM``): above 128 the
+kernels that draw directions run in their wide form (csrc/mlf_walk_dev.hpp, ``dw_direction_wide``), same Philox layout.
 
-``PopulationRandomWalkSampler`` takes the same ``device_rng=``: with a direction generator that has a ``device_kind`` and a
-resident model (device likelihoods, or a user model) a whole refill -- start rows, ``nsteps`` moves of every walker,
+``PopulationRandomWalkSampler`` takes the same ``device_rng=``: with a direction generator that has a ``device_kind``, a
+resident model (device likelihoods, or a user model) and at most 128 dimensions a whole refill -- start rows, ``nsteps`` moves of every walker,
 diagnostics, counts -- is one device call (csrc/mlf_rwalk.hip); otherwise its host loop runs as before.
 
 ``PopulationSimpleSliceSampler`` takes it too: with the same conditions and one of this module's two ``slice_limit``
@@ -563,7 +564,8 @@ class _SliceWalkers(object):
 
 
 class _Walkers(object):
-    """Owner of one ``mlf_walkers`` handle (include/mlfriends_hip.h)."""
+    """Owner of one ``mlf_walkers`` handle (include/mlfriends_hip.h): any `ndim` up to ``MLF_MAX_DIM`` = 1024 (above:
+    ``HipLibraryError``, MLF_E_DIM)."""
 
     def __init__(self, popsize, nsteps, ndim):
         self.popsize, self.nsteps, self.ndim = int(popsize), int(nsteps), int(ndim)
@@ -756,7 +758,8 @@ class _Walkers(object):
 
 class PopulationSliceSampler(GenericPopulationSampler):
     """Vectorized slice/HARM sampler over a device-resident walker population
-    (reference popstepsampler.py:347-697; same constructor and ``__next__`` contract)."""
+    (reference popstepsampler.py:347-697; same constructor and ``__next__`` contract), up to 1024 dimensions in both random
+    modes and for every kind of model."""
 
     def __init__(self, popsize, nsteps, generate_direction, scale=1.0, scale_adapt_factor=0.9, log=False,
                  logfile=None, device_rng=None):
