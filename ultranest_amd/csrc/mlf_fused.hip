@@ -28,6 +28,7 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef _Float16 half8v __attribute__((ext_vector_type(8)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
+typedef double double2v __attribute__((ext_vector_type(2)));
 
 #ifndef MLF_OPERAND_STEPS
 #define MLF_OPERAND_STEPS 4
@@ -120,9 +121,20 @@ __device__ __forceinline__ void pin_step() {
 // the ellipsoid form is read off the whitening chain's accumulators, the L^T chain (18 of 42 matrix instructions per group at
 // d = 50), its fragments and its start values are gone.  The host hands over the constants of THAT form (region_prep4_setup:
 // eta from the T chain's error model, eps enlarged by |E|_F); band proposals are decided by the exact einsum path as before.
-template <int DP, int NW, bool SQ>
+//
+// F (kFused...): what the launcher knows about the call, as compile-time facts of the instantiation.
+//   kFusedFull  d == DP (even d): the row pieces of a group, the padding of the operands and the row stride are constants
+//   kFusedPre   gate[] arrives holding a pre-gate (with kFusedFull; without it "fused_variant" bit 2 is read at run time)
+//   kFusedDiag  the diagnostic / A-B instantiation: stage stamps (mlf_region_debug_fused_stamps) and the load / store loop
+//               for the tables ("fused_variant" bit 0 clear), both decided at run time; every other instantiation has neither
+//   0           d < DP: d and the pre-gate are read at run time (the parent's path without its diagnostics)
+constexpr unsigned kFusedFull = 1u, kFusedPre = 2u, kFusedDiag = 4u;
+
+template <int DP, int NW, bool SQ, unsigned F>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedArgs a) {
   using C = F4<DP, NW>;
+  constexpr bool FULL = (F & kFusedFull) != 0u, DIAG = (F & kFusedDiag) != 0u;
+  static_assert(!(FULL && DIAG) && (FULL || !(F & kFusedPre)), "kFusedPre goes with kFusedFull; the diagnostic form is the general one");
   constexpr int NS = C::NS, NT = C::NT, NE = C::NE, KS = C::KS, QW = 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsf[];
   const uint4 *Th = reinterpret_cast<const uint4 *>(ldsf);
@@ -139,16 +151,19 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
   const int p32 = lane & 31, h = lane >> 5;
   unsigned char *area = ldsf + C::r16(C::FRAG) + (size_t)wv * C::WAVE;
   double *xs = reinterpret_cast<double *>(area);
-  const int d = a.p.d;
+  const int d = FULL ? DP : a.p.d;
+  const bool pregate = FULL ? (F & kFusedPre) != 0u : (a.variant & 4u) != 0u;
   constexpr float up = 1.0f + 0x1p-18f, dn = 1.0f - 0x1p-18f;
   unsigned *wg_keep = reinterpret_cast<unsigned *>(ldsf + C::r16(C::FRAG) + NW * C::WAVE);   // [NW] + base
   unsigned &wg_base = wg_keep[8];
   // diagnostics (mlf_region_debug_fused_stamps): shader-clock stamps of ONE wave's stage boundaries
-  const bool stamp_on = a.stamps != nullptr && blockIdx.x == a.stamp_block && wv == 0;
+  const bool stamp_on = DIAG && a.stamps != nullptr && blockIdx.x == a.stamp_block && wv == 0;
   auto stamp = [&](int k) __attribute__((always_inline)) {
-    if (stamp_on) {   // wave-uniform
-      const unsigned long long t = __builtin_readcyclecounter();
-      if (lane == 0) a.stamps[k] = t;
+    if constexpr (DIAG) {
+      if (stamp_on) {   // wave-uniform
+        const unsigned long long t = __builtin_readcyclecounter();
+        if (lane == 0) a.stamps[k] = t;
+      }
     }
   };
   stamp(0);
@@ -160,7 +175,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
     a.p.counters[0] = 0;
     a.p.counters[1] = 0;
   }
-  if (!(a.variant & 1u)) {
+  const bool dma = !DIAG || (a.variant & 1u) != 0u;
+  if (!dma) {
     uint4 *dst = reinterpret_cast<uint4 *>(ldsf);
     const uint4 *srcT = reinterpret_cast<const uint4 *>(a.p.TtF);
     const uint4 *srcL = reinterpret_cast<const uint4 *>(a.p.LtF);
@@ -213,8 +229,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
       const unsigned char *src = reinterpret_cast<const unsigned char *>(a.p.pts + base) + lane * 16;
       // the piece count through an opaque copy: compared again at every use (one s_cmp) -- seen as a loop invariant of the
       // unrolled groups, the 13 comparison results were kept as 64-bit masks, spilled, and read back lane by lane
+      // (kFusedFull: the count is a constant, the whole pieces go out unconditionally)
       int nf = nfull;
-      asm volatile("" : "+s"(nf));
+      if constexpr (!FULL) asm volatile("" : "+s"(nf));
 #pragma unroll
       for (int ib = 0; ib < C::NPC; ib += 4) {   // whole pieces: scalar conditions only (the immediate offset has to be a literal)
         gptr_t *gp = (gptr_t *)(src + ib * 1024);
@@ -224,8 +241,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
         if (ib + 2 < C::NPC && ib + 2 < nf) __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0);
         if (ib + 3 < C::NPC && ib + 3 < nf) __builtin_amdgcn_global_load_lds(gp, lp, 16, 3072, 0);
       }
-      if (lane < rem)   // the last, partial piece (one lane mask per group)
-        __builtin_amdgcn_global_load_lds((gptr_t *)(src + nf * 1024), (lptr_t *)(area + nf * 1024), 16, 0, 0);
+      if (!FULL || (16 * DP) % 64 != 0)
+        if (lane < rem)   // the last, partial piece (one lane mask per group)
+          __builtin_amdgcn_global_load_lds((gptr_t *)(src + nf * 1024), (lptr_t *)(area + nf * 1024), 16, 0, 0);
     } else {
 #pragma nounroll
       for (int e = lane; e < units; e += 64) {   // (at most one group per batch) plain loads, zero behind the batch
@@ -239,7 +257,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
     }
   };
   fetch_group(g0);
-  if (a.variant & 1u) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the tables (and its first rows) have landed
+  if (dma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the tables (and its first rows) have landed
   __syncthreads();   // fragments and constants are in LDS
   stamp(1);
 
@@ -266,6 +284,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
   // offset field (left to itself the compiler keeps 52 precomputed addresses in registers across the groups and reads four
   // values per LDS round trip for want of room)
   typedef __attribute__((address_space(3))) const double lds_cdouble;
+  typedef __attribute__((address_space(3))) const double2v lds_cdouble2;
+  const bool row16 = FULL || (d & 1) == 0;   // wave-uniform: the rows' pitch is a multiple of 16 bytes
   lds_cdouble *xrow = (lds_cdouble *)(xs + p32 * d + 8 * h);
   lds_cdouble *crow = (lds_cdouble *)(ctrl + 8 * h);
   asm volatile("" : "+v"(xrow), "+v"(crow));
@@ -277,14 +297,34 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
 #pragma unroll
     for (int sb = 0; sb < NS; sb += SB) {
       double xv[SB][8], cv[SB][8];
+      // A pair of coordinates is ONE 16-byte read (ds_read_b128: 4 LDS cycles per wave, banks counted mod 64) where its address
+      // is 16-byte aligned -- the centre always, the row at an even d.  As two 8-byte words the compiler pairs them into
+      // ds_read2_b64: 8 LDS cycles, banks counted mod 32, and the row pitch of d = 50 (100 dwords = 4 mod 32) puts lanes l and
+      // l + 8 of a 16-lane group on the same banks: 16 cycles per read, 26 of them per group and wave.  At 36 mod 64
+      // the sixteen lanes of a group of the 16-byte read cover the 64 banks once.
+      auto read_pairs = [&](auto ROW16) __attribute__((always_inline)) {
 #pragma unroll
-      for (int s = sb; s < sb + SB && s < NS; ++s)
+        for (int s = sb; s < sb + SB && s < NS; ++s)
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-          if (16 * s + (jj & ~1) >= DP) continue;   // (compile time) padding in both halves of the wave, see below
-          xv[s - sb][jj] = xrow[16 * s + jj];
-          cv[s - sb][jj] = crow[16 * s + jj];
-        }
+          for (int jj = 0; jj < 8; jj += 2) {
+            if (16 * s + jj >= DP) continue;   // (compile time) padding in both halves of the wave, see below
+            if constexpr (decltype(ROW16)::value) {
+              const double2v x2 = *reinterpret_cast<lds_cdouble2 *>(xrow + 16 * s + jj);
+              xv[s - sb][jj] = x2[0];
+              xv[s - sb][jj + 1] = x2[1];
+            } else {
+              xv[s - sb][jj] = xrow[16 * s + jj];
+              xv[s - sb][jj + 1] = xrow[16 * s + jj + 1];
+            }
+            const double2v c2 = *reinterpret_cast<lds_cdouble2 *>(crow + 16 * s + jj);
+            cv[s - sb][jj] = c2[0];
+            cv[s - sb][jj + 1] = c2[1];
+          }
+      };
+      if (row16)   // wave-uniform
+        read_pairs(std::true_type{});
+      else
+        read_pairs(std::false_type{});
 #pragma unroll
       for (int s = sb; s < sb + SB && s < NS; ++s)
 #pragma unroll
@@ -316,7 +356,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
           for (int e = 0; e < 2; ++e) {
             const int jj = 2 * j2 + e;
             const int k = 16 * s + 8 * h + jj;
-            const bool ok = 16 * s + 8 + jj < C::KMIN || k < d;
+            // kFusedFull: only the upper half of the wave can hold padding, and where it does is known per index
+            const bool ok = FULL ? (16 * s + 8 + jj < DP || h == 0) : (16 * s + 8 + jj < C::KMIN || k < d);
             const double x = __builtin_fma(xv[s - sb][jj], sxd, -cv[s - sb][jj]);
             x32[e] = ok ? (float)x : 0.0f;
             dn2 = __builtin_fmaf(x32[e], x32[e], dn2);
@@ -360,7 +401,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
       // variant bit 2: gate[] arrives holding a pre-gate (device-side sampling: "inside the unit cube") -- a proposal that failed
       // it is outside for certain, whatever the ellipsoid says; asked for here, needed after the chains
       unsigned char pre = 1;
-      if ((a.variant & 4u) && live) pre = a.p.gate[p];
+      if (pregate && live) pre = a.p.gate[p];
       float qs = 0.0f;
       float16v tt[NT];
       float cs[NT][16];
@@ -667,19 +708,30 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
 
 bool fused_usable(int dp) { return dp >= 2 && dp <= 56 && (dp & 1) == 0; }
 
-template <int D, int NW, bool SQ>
+template <int D, int NW, bool SQ, unsigned F>
 static hipError_t launch_prep_sweep_t(const FusedArgs &a, long long nsets, hipStream_t s) {
   constexpr size_t lds = F4<D, NW>::LDS;
   static_assert(lds <= 160 * 1024 - 64, "LDS budget");
   static DeviceGrant grant;
   if (hipError_t e = grant.ensure([] {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_prep_sweep<D, NW, SQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_prep_sweep<D, NW, SQ, F>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       }))
     return e;
   if (a.p.ks != F4<D, NW>::KS) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((nsets + NW - 1) / NW));
-  hipLaunchKernelGGL((k_prep_sweep<D, NW, SQ>), grid, dim3(64 * NW), lds, s, a);
+  hipLaunchKernelGGL((k_prep_sweep<D, NW, SQ, F>), grid, dim3(64 * NW), lds, s, a);
   return hipGetLastError();
+}
+
+// The instantiation of a call.  The diagnostic one where stamps are asked for or the tables are to take the load / store loop
+// ("fused_variant" bit 0 clear, A/B runs); d < DP (odd d, and an even d that has no instantiation of its own: 34 runs as 36)
+// the general one (F = 0: d and the pre-gate read at run time, no diagnostics); d == DP the ones that know it.
+template <int D, int NW, bool SQ>
+static hipError_t launch_prep_sweep_f(const FusedArgs &a, long long nsets, hipStream_t s) {
+  if (a.stamps != nullptr || !(a.variant & 1u)) return launch_prep_sweep_t<D, NW, SQ, kFusedDiag>(a, nsets, s);
+  if (a.p.d != D) return launch_prep_sweep_t<D, NW, SQ, 0u>(a, nsets, s);
+  return (a.variant & 4u) ? launch_prep_sweep_t<D, NW, SQ, kFusedFull | kFusedPre>(a, nsets, s)
+                          : launch_prep_sweep_t<D, NW, SQ, kFusedFull>(a, nsets, s);
 }
 
 // waves = 4 (default): workgroups of 4 waves, TWO per CU where the rows of four groups + the tables fit half the LDS (d <= 50:
@@ -694,9 +746,9 @@ hipError_t launch_prep_sweep(const FusedArgs &a, hipStream_t s, int waves) {
 #define X(D)                                                                                  \
   case D:                                                                                     \
     if constexpr (2 * F4<D, 4>::LDS <= 160 * 1024) {                                          \
-      if (waves == 4) return sq ? launch_prep_sweep_t<D, 4, true>(a, nsets, s) : launch_prep_sweep_t<D, 4, false>(a, nsets, s); \
+      if (waves == 4) return sq ? launch_prep_sweep_f<D, 4, true>(a, nsets, s) : launch_prep_sweep_f<D, 4, false>(a, nsets, s); \
     }                                                                                         \
-    return sq ? launch_prep_sweep_t<D, 8, true>(a, nsets, s) : launch_prep_sweep_t<D, 8, false>(a, nsets, s);
+    return sq ? launch_prep_sweep_f<D, 8, true>(a, nsets, s) : launch_prep_sweep_f<D, 8, false>(a, nsets, s);
     MLF_FOR_EACH_DP_MID(X)
 #undef X
     default:
