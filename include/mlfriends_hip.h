@@ -34,9 +34,9 @@ extern "C" {
 
 /* Largest dimensionality of the K1-K5 / H3 / T1 / R3 entry points.  Up to 128 the templated kernels; 129 ... 1024 the
  * run-time-dimensionality kernels (csrc/mlf_wide.hip: exact binary64 scan only, no matrix-core pre-filter).  Entry points
- * that stop earlier and say so with MLF_E_DIM: mlf_rwalk_create and mlf_sslice_create (d <= 128: one wave per walker, lane =
- * coordinate pair; mlf_walkers_create goes up to MLF_MAX_DIM, above 128 with the wide form of the direction draw),
- * mlf_col_extent (d <= 128), mlf_bootstrap_factor (d <= 64; above: mlf_bootstrap_moments + mlf_bootstrap_quadmax);
+ * that stop earlier and say so with MLF_E_DIM: mlf_col_extent (d <= 128; mlf_walkers_create, mlf_rwalk_create and
+ * mlf_sslice_create go up to MLF_MAX_DIM: up to 128 one wave per walker with lane = coordinate pair, above with the wide form
+ * of the direction draw and the lanes striding over the row; the random walk's one-launch form stays at even d <= 64), mlf_bootstrap_factor (d <= 64; above: mlf_bootstrap_moments + mlf_bootstrap_quadmax);
  * the single-launch small-batch path of mlf_region_inside (up to 256 host proposals) is used for d <= 128 and the batched
  * pipeline above. */
 #define MLF_MAX_DIM 1024

@@ -355,6 +355,7 @@ int filter_sweep_min(const FilterBatch &b) {
     fu.ccap = m.ccap;
     if (f.stamp_block >= 0 && f.stamp_block < 1000000) {   // diagnostics (mlf_region_debug_fused_stamps)
       CK(f.fstamps.reserve(16 * sizeof(unsigned long long)));
+      CK(hipMemsetAsync(f.fstamps.p, 0, 16 * sizeof(unsigned long long), b.s));   // (a stage the wave never reaches reads as 0)
       fu.stamps = f.fstamps.as<unsigned long long>();
       fu.stamp_block = (unsigned)f.stamp_block;
     }
@@ -388,6 +389,7 @@ int filter_sweep_min(const FilterBatch &b) {
     m.stamps = nullptr;
     if (f.stamp_block >= which * 1000000 && f.stamp_block < (which + 1) * 1000000) {
       CK(f.fstamps.reserve(16 * sizeof(unsigned long long)));
+      CK(hipMemsetAsync(f.fstamps.p, 0, 16 * sizeof(unsigned long long), b.s));
       m.stamps = f.fstamps.as<unsigned long long>();
       m.stamp_block = (unsigned)(f.stamp_block - which * 1000000);
     }

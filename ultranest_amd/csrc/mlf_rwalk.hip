@@ -5,7 +5,7 @@
 // standard normal t truncated to it, the proposal u + v t, prior transform, likelihood, accept iff inside and L > Lmin.
 //
 // Two forms with the same results, bit for bit (tests/test_randomwalk_device.py):
-//   chain   any d <= 128, any layer, user models.  Per step three launches: k_rwalk_propose, the evaluation (the user model's
+//   chain   any d <= kWideDirMaxDim (above 128: k_rwalk_propose_wide), any layer, user models.  Per step three launches: k_rwalk_propose, the evaluation (the user model's
 //           kernel with the cube flag as member mask; launch_loglike has no mask and evaluates every row -- the value of a
 //           proposal outside the cube is never read: k_rwalk_accept tests the flag first), k_rwalk_accept.  State in HBM.
 //   fused   built-in models, even d <= 64, affine layer or none: one launch, a wave owns a walker, (u, p, L, flags) stay in
@@ -109,6 +109,39 @@ __global__ __launch_bounds__(64) void k_rwalk_propose(RwalkArgs a, int step) {
         ok = ok && inside_open_unit(x);
         if (a.tkind >= 0) w.pnew[(size_t)i * d + c] = rwalk_transform(a.tkind, x, a.ta, a.tb);
       }
+    }
+    const bool all_ok = __all(ok);
+    if (lane == 0) {
+      w.inside[i] = all_ok ? 1 : 0;
+      w.tl[i] = lo;
+      w.tr[i] = hi;
+    }
+  }
+}
+
+// The wide form: kNarrowDirMaxDim < d <= kWideDirMaxDim (enforced by mlf_rwalk_create; every row and LDS access below is
+// bounded by it).  The lanes stride over the row, c = lane, lane + 64, ...  The direction goes through dw_direction_wide into
+// the walker's row of unew: kind 4 writes v[r] from other lanes than the ones that read it, hence the fence; after it lane l
+// reads v[c] and writes the proposal x over it at the SAME c, so no second fence is needed.  The other stages are the
+// device functions of the narrow form.  Launched with wide_rwalk_grid: the workgroups walk the population.
+__global__ __launch_bounds__(64) void k_rwalk_propose_wide(RwalkArgs a, int step) {
+  __shared__ double gs[kWideDirMaxDim];
+  const RwalkState &w = a.w;
+  const int lane = threadIdx.x, d = w.d;
+  for (int i = blockIdx.x; i < w.P; i += gridDim.x) {
+    const double *uo = w.u + (size_t)i * d;
+    double *v = w.unew + (size_t)i * d;
+    dw_direction_wide(d, i * w.nsteps + step, lane, a.dirkind, a.dirscale, a.dd, a.seed, a.offset, v, gs);
+    wave_lds_sync();   // (the direction row written above is read back by other lanes of this wave)
+    double lo, hi;
+    line_cube_wave_wide(uo, v, d, lane, lo, hi);
+    const double t = truncnorm_draw(lo, hi, rwalk_uniform(a, i, step));
+    bool ok = true;
+    for (int c = lane; c < d; c += 64) {
+      const double x = rwalk_move(uo[c], v[c], t);
+      v[c] = x;
+      ok = ok && inside_open_unit(x);
+      if (a.tkind >= 0) w.pnew[(size_t)i * d + c] = rwalk_transform(a.tkind, x, a.ta, a.tb);
     }
     const bool all_ok = __all(ok);
     if (lane == 0) {
@@ -269,6 +302,9 @@ __global__ __launch_bounds__(256) void k_rwalk_stats_sum(RwalkArgs a, int nchunk
 // one one-wave workgroup per walker (mlf_walk.hip: walker_grid)
 static inline dim3 rwalk_grid(int P) { return dim3((unsigned)(P < (1 << 22) ? P : (1 << 22))); }
 
+// the wide propose kernel: the grid of the wide slice walkers (mlf_walk.hip: wide_walker_grid), each workgroup 8 KiB of LDS
+static inline dim3 wide_rwalk_grid(int P) { return dim3((unsigned)(P < (1 << 13) ? P : (1 << 13))); }
+
 unsigned long long rwalk_philox_per_refill(int P, int nsteps, int d) {
   return (unsigned long long)P * (unsigned long long)nsteps * (unsigned long long)((d + 1) / 2 + 2);
 }
@@ -280,7 +316,10 @@ void launch_rwalk_start(const RwalkArgs &a, hipStream_t s) {
 }
 
 void launch_rwalk_propose(const RwalkArgs &a, int step, hipStream_t s) {
-  hipLaunchKernelGGL(k_rwalk_propose, rwalk_grid(a.w.P), dim3(64), 0, s, a, step);
+  if (a.w.d > kNarrowDirMaxDim)
+    hipLaunchKernelGGL(k_rwalk_propose_wide, wide_rwalk_grid(a.w.P), dim3(64), 0, s, a, step);
+  else
+    hipLaunchKernelGGL(k_rwalk_propose, rwalk_grid(a.w.P), dim3(64), 0, s, a, step);
 }
 
 void launch_rwalk_accept(const RwalkArgs &a, hipStream_t s) {

@@ -10,7 +10,8 @@
 // successor or after max_it iterations.
 //
 // How many iterations a step takes is known on the device only, so ONE launch sequence serves every iteration -- a slot:
-//   k_sslice_propose   wave per worker (lane = coordinate pair, the random walk's layout).  it == 0: worker j serves point j
+//   k_sslice_propose   wave per worker (lane = coordinate pair, the random walk's layout; above 128 dimensions
+//                      k_sslice_propose_wide, the lanes striding over the row).  it == 0: worker j serves point j
 //                      and first draws the step's direction and slice.  it > 0: worker j serves zlist[j % nz]
 //   evaluation         launch_loglike, or the user model's kernel with w.member as its mask
 //   k_sslice_update    wave per unfinished point.  The workers of the point at list position q are q, q + nz, q + 2 nz, ...
@@ -143,6 +144,60 @@ __global__ __launch_bounds__(64) void k_sslice_propose(SsliceArgs a) {
         w.unew[(size_t)j * d + cc] = x;
         if (a.tkind >= 0) w.pnew[(size_t)j * d + cc] = rwalk_transform(a.tkind, x, a.ta, a.tb);
       }
+    }
+    if (lane == 0) {
+      w.t[j] = t;
+      if (a.tkind < 0) w.member[j] = 1;
+    }
+  }
+}
+
+// The wide form: kNarrowDirMaxDim < d <= kWideDirMaxDim (enforced by mlf_sslice_create; every row and LDS access below is
+// bounded by it).  The lanes stride over the rows, c = lane, lane + 64, ...; at it == 0 the direction goes through
+// dw_direction_wide straight into the point's row of w.v (kind 4 writes v[r] from other lanes than the ones that read it,
+// hence the fence).  Everything else -- the control block, the member mask, the clip, the draw -- is the narrow form's.
+// Launched with wide_sslice_grid: the workgroups walk the workers.
+__global__ __launch_bounds__(64) void k_sslice_propose_wide(SsliceArgs a) {
+  __shared__ double gs[kWideDirMaxDim];
+  const SsliceState &w = a.w;
+  const SsliceCtl c = *w.ctl;
+  const int lane = threadIdx.x, d = w.d;
+  if (c.finished) {
+    if (a.tkind < 0)
+      for (long long j = (long long)blockIdx.x * 64 + lane; j < w.P; j += (long long)gridDim.x * 64) w.member[j] = 0;
+    return;
+  }
+  for (int j = blockIdx.x; j < w.P; j += gridDim.x) {
+    double lo, hi;
+    int k = j;
+    if (c.it > 0) k = w.zlist[j % c.nz];
+    const double *uo = w.u + (size_t)k * d;
+    double *v = w.v + (size_t)k * d;
+    if (c.it == 0) {   // (wave-uniform) the step's direction and slice of point j; no other wave reads them in this launch
+      dw_direction_wide(d, k * w.nsteps + c.step, lane, a.dirkind, a.dirscale[c.step], a.dd, a.seed, a.offset, v, gs);
+      wave_lds_sync();   // (the direction row written above is read back by other lanes of this wave)
+      line_cube_wave_wide(uo, v, d, lane, lo, hi);
+      if (a.limit == 1) {
+        lo = fmax(lo, -1.0);
+        hi = fmin(hi, 1.0);
+      }
+      if (lane == 0) {
+        w.tl[k] = lo;
+        w.tr[k] = hi;
+        w.status[k] = 0;
+        w.taken[k] = -1;
+        w.taken_it[k] = -1;
+      }
+    } else {
+      lo = w.tl[k];
+      hi = w.tr[k];
+    }
+    const double width = hi - lo;
+    const double t = lo + width * sslice_uniform(a, j, c.step, c.it);
+    for (int cc = lane; cc < d; cc += 64) {
+      const double x = rwalk_move(uo[cc], v[cc], t);
+      w.unew[(size_t)j * d + cc] = x;
+      if (a.tkind >= 0) w.pnew[(size_t)j * d + cc] = rwalk_transform(a.tkind, x, a.ta, a.tb);
     }
     if (lane == 0) {
       w.t[j] = t;
@@ -306,6 +361,9 @@ __global__ __launch_bounds__(1024) void k_sslice_stats(SsliceArgs a) {
 // one one-wave workgroup per worker / point (mlf_walk.hip: walker_grid)
 static inline dim3 sslice_grid(int P) { return dim3((unsigned)(P < (1 << 22) ? P : (1 << 22))); }
 
+// the wide propose kernel: the grid of the wide slice walkers (mlf_walk.hip: wide_walker_grid), each workgroup 8 KiB of LDS
+static inline dim3 wide_sslice_grid(int P) { return dim3((unsigned)(P < (1 << 13) ? P : (1 << 13))); }
+
 unsigned long long sslice_philox_per_refill(int P, int nsteps, int d, int max_it) {
   const unsigned long long dirs = (unsigned long long)P * (unsigned long long)nsteps * (unsigned long long)((d + 1) / 2 + 2);
   const unsigned long long mine = (unsigned long long)P * (1ull + (unsigned long long)nsteps * (unsigned long long)max_it);
@@ -317,7 +375,10 @@ void launch_sslice_start(const SsliceArgs &a, hipStream_t s) {
 }
 
 void launch_sslice_propose(const SsliceArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_sslice_propose, sslice_grid(a.w.P), dim3(64), 0, s, a);
+  if (a.w.d > kNarrowDirMaxDim)
+    hipLaunchKernelGGL(k_sslice_propose_wide, wide_sslice_grid(a.w.P), dim3(64), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_sslice_propose, sslice_grid(a.w.P), dim3(64), 0, s, a);
 }
 
 void launch_sslice_update(const SsliceArgs &a, hipStream_t s) {

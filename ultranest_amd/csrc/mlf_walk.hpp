@@ -49,9 +49,9 @@ struct StepParams {
 };
 
 // Two forms of the device-side direction draw (mlf_walk_dev.hpp), chosen by the launchers on d: dw_direction holds two
-// coordinates per lane (the resident slice walkers up to kNarrowDirMaxDim dimensions, and the whole-population samplers of
-// mlf_rwalk.hip / mlf_sslice.hip, which stop there); dw_direction_wide strides over the row and stages kWideDirMaxDim normals
-// in LDS (the resident slice walkers above).
+// coordinates per lane (the resident slice walkers and the whole-population samplers of mlf_rwalk.hip / mlf_sslice.hip up to
+// kNarrowDirMaxDim dimensions); dw_direction_wide strides over the row and stages kWideDirMaxDim normals in LDS (all three
+// above: k_walk_prologue<true>, k_rwalk_propose_wide, k_sslice_propose_wide).
 constexpr int kNarrowDirMaxDim = 128;
 constexpr int kWideDirMaxDim = 1024;    // = MLF_MAX_DIM (mlf_walk_api.hip asserts it)
 

@@ -18,6 +18,7 @@
 
 using namespace mlf;
 
+// (the bound of every wide kernel: the resident slice walkers, k_rwalk_propose_wide, k_sslice_propose_wide)
 static_assert(kWideDirMaxDim == MLF_MAX_DIM, "dw_direction_wide stages MLF_MAX_DIM normals in LDS");
 
 // Device copies of what the region and the live points contribute, with the state of their setters: shared by the three
@@ -1020,7 +1021,8 @@ int mlf_rwalk_create(mlf_rwalk **out, size_t popsize, size_t nsteps, size_t d) {
   if (!out) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
   if (popsize == 0 || nsteps == 0 || d == 0) return fail_arg(MLF_E_BADARG, "mlf_rwalk_create: popsize, nsteps, d must be positive");
-  if (d > 128) return fail_arg(MLF_E_DIM, "the random-walk population (one wave per walker, lane = coordinate pair) covers up to 128 dimensions");
+  if (d > MLF_MAX_DIM)
+    return fail_arg(MLF_E_DIM, "the random-walk population (one wave per walker, the lanes striding over the row) covers up to MLF_MAX_DIM = 1024 dimensions");
   // walker * nsteps + step and walker * d + coordinate are ints on the device
   if (popsize > (1u << 24) || nsteps > 65535 || popsize * nsteps > 0x7fffffffull || popsize * d > 0x7fffffffull)
     return fail_arg(MLF_E_BADARG, "mlf_rwalk_create: population too large");
@@ -1094,7 +1096,8 @@ int mlf_sslice_create(mlf_sslice **out, size_t popsize, size_t nsteps, size_t d,
   *out = nullptr;
   if (popsize == 0 || nsteps == 0 || d == 0 || max_it == 0)
     return fail_arg(MLF_E_BADARG, "mlf_sslice_create: popsize, nsteps, d, max_it must be positive");
-  if (d > 128) return fail_arg(MLF_E_DIM, "the simple slice population (one wave per worker, lane = coordinate pair) covers up to 128 dimensions");
+  if (d > MLF_MAX_DIM)
+    return fail_arg(MLF_E_DIM, "the simple slice population (one wave per worker, the lanes striding over the row) covers up to MLF_MAX_DIM = 1024 dimensions");
   // point * nsteps + step, point * d + coordinate and nsteps * max_it are ints on the device or the host
   if (popsize > (1u << 24) || nsteps > 65535 || max_it > 65535 || popsize * nsteps > 0x7fffffffull || popsize * d > 0x7fffffffull ||
       nsteps * max_it > 0x7fffffffull)

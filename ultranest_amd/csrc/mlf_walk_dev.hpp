@@ -259,6 +259,23 @@ __device__ inline void dw_direction_wide(int d, int i, int lane, int kind, doubl
   }
 }
 
+// one line by one wave, rows in memory of any d (the wide forms of the whole-population samplers): lane l combines the
+// coordinates c = l, l + 64, ... of o and v, then line_cube_wave's xor tree; every lane gets (lo, hi).  Max and min are exact,
+// so these are the two doubles of line_cube_row.  The rows must be visible to the lanes that read them (wave_lds_sync).
+__device__ __forceinline__ void line_cube_wave_wide(const double *o, const double *v, int d, int lane, double &lo, double &hi) {
+  lo = hi = qnan();
+  for (int c = lane; c < d; c += 64) {
+    double t1, t2;
+    line_cube_coord(o[c], v[c], t1, t2);
+    nan_skip_max(lo, t1);
+    nan_skip_min(hi, t2);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    nan_skip_max(lo, __shfl_xor(lo, off, 64));
+    nan_skip_min(hi, __shfl_xor(hi, off, 64));
+  }
+}
+
 // ---- a proposal on the line and its built-in prior transform (the whole-population samplers: mlf_rwalk.hip, mlf_sslice.hip)
 __device__ __forceinline__ double rwalk_move(double u, double v, double t) {
   const double step = v * t;

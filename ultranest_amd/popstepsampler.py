@@ -24,13 +24,18 @@ device (no graph replay, no multi-round kernel).  All of this holds up to 1024 d
 kernels that draw directions run in their wide form (csrc/mlf_walk_dev.hpp, ``dw_direction_wide``), same Philox layout.
 
 ``PopulationRandomWalkSampler`` takes the same ``device_rng=``: with a direction generator that has a ``device_kind``, a
-resident model (device likelihoods, or a user model) and at most 128 dimensions a whole refill -- start rows, ``nsteps`` moves of every walker,
-diagnostics, counts -- is one device call (csrc/mlf_rwalk.hip); otherwise its host loop runs as before.
+resident model (device likelihoods, or a user model) and at most ``device_max_dim`` dimensions a whole refill -- start rows,
+``nsteps`` moves of every walker, diagnostics, counts -- is one device call (csrc/mlf_rwalk.hip); otherwise its host loop runs
+as before.  ``device_max_dim`` is a constructor keyword, 128 by default and at most 1024 (``MLF_MAX_DIM``): above 128 the
+proposal kernel runs in its wide form (the lanes stride over the row, directions from ``dw_direction_wide``), same Philox
+layout.  The wide route is opt-in because a seeded run with ``device_rng`` above 128 dimensions has always taken the host loop
+and ``np.random``: routing it to the device without being asked would change its points.
 
 ``PopulationSimpleSliceSampler`` takes it too: with the same conditions and one of this module's two ``slice_limit``
 functions, a refill -- start rows, ``nsteps`` slice steps of the whole population (each as many shrinking iterations as its
 slowest point needs, up to ``max_it``), diagnostics, counts -- runs on the device (csrc/mlf_sslice.hip); the host takes the
-per-step median widths from one downloaded array and keeps its bookkeeping.  Otherwise its host loop runs as before.
+per-step median widths from one downloaded array and keeps its bookkeeping.  Otherwise its host loop runs as before.  The same
+``device_max_dim`` keyword (default 128, at most 1024) opts into the device route above 128 dimensions.
 """
 import ctypes
 
@@ -159,6 +164,13 @@ def _sync_region_copies(w, seen, region, ndim, device_kind, skip_live=False):
     seen["calls"] += 1
 
 
+def _checked_device_max_dim(value):
+    """The ``device_max_dim`` keyword of the two whole-population samplers: an integer in [1, 1024] (``MLF_MAX_DIM``)."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not 1 <= value <= 1024:
+        raise ValueError("device_max_dim must be an integer between 1 and 1024 (MLF_MAX_DIM), got %r" % (value,))
+    return int(value)
+
+
 class _BatchedPopulationSampler(GenericPopulationSampler):
     """The two samplers of the reference that advance the WHOLE population by `nsteps` moves in one call and then hand the
     walkers out one per call (reference popstepsampler.py:192-358 and :746-1001).  The moves themselves are the vectorised
@@ -183,10 +195,12 @@ class _BatchedPopulationSampler(GenericPopulationSampler):
 
 
 class PopulationRandomWalkSampler(_BatchedPopulationSampler):
-    """Vectorized Gaussian random walk (reference popstepsampler.py:192-358; same constructor and ``__next__`` contract)."""
+    """Vectorized Gaussian random walk (reference popstepsampler.py:192-358; same constructor and ``__next__`` contract).
+    With ``device_rng=DeviceRNG(seed)`` and the conditions of ``_device_route`` the whole refill runs on the device, up to
+    ``device_max_dim`` dimensions (an integer in [1, 1024]; default 128, above it the host loop runs)."""
 
     def __init__(self, popsize, nsteps, generate_direction, scale, scale_adapt_factor=0.9, scale_min=1e-20, scale_max=20,
-                 log=False, logfile=None, device_rng=None):
+                 log=False, logfile=None, device_rng=None, device_max_dim=128):
         assert scale_adapt_factor <= 1
         self.popsize, self.nsteps, self.generate_direction = popsize, nsteps, generate_direction
         self.scale, self.scale_adapt_factor, self.scale_min, self.scale_max = scale, scale_adapt_factor, scale_min, scale_max
@@ -197,6 +211,7 @@ class PopulationRandomWalkSampler(_BatchedPopulationSampler):
         if device_rng is not None and not isinstance(device_rng, DeviceRNG):
             raise TypeError("device_rng must be an ultranest_amd.regions.DeviceRNG")
         self.device_rng = device_rng
+        self.device_max_dim = _checked_device_max_dim(device_max_dim)
         self.force_chain_form = False     # tests: the general form (three launches per step) where one launch would do
         self._rwalk = None
         self._seen = dict(region=None, layer=None, r2=None, calls=0)
@@ -208,9 +223,10 @@ class PopulationRandomWalkSampler(_BatchedPopulationSampler):
     def _device_route(self, transform, loglike, ndim=None):
         """What a refill runs on: None = the host loop; else ``(device_kind, tspec, lspec, user)`` of a whole refill on the
         device -- it takes ``device_rng``, a direction generator with a ``device_kind``, a resident model (both callbacks
-        with a built-in ``device_spec``, or a user model as ``devicemodel.device_route`` decides it) and at most 128
-        dimensions (``mlf_rwalk``: one wave per walker, lane = coordinate pair)."""
-        if self.device_rng is None or (ndim is not None and ndim > 128):
+        with a built-in ``device_spec``, or a user model as ``devicemodel.device_route`` decides it) and at most
+        ``device_max_dim`` dimensions (``mlf_rwalk``: one wave per walker; up to 128 dimensions lane = coordinate pair, above
+        the lanes stride over the row)."""
+        if self.device_rng is None or (ndim is not None and ndim > self.device_max_dim):
             return None
         device_kind = getattr(self.generate_direction, "device_kind", None)
         if device_kind is None:
@@ -310,10 +326,12 @@ class PopulationSimpleSliceSampler(_BatchedPopulationSampler):
     (reference popstepsampler.py:746-1001; same constructor and ``__next__`` contract).  The likelihood is always called
     with ``popsize`` points: workers whose point has found its successor are dealt to the points still searching
     (``update_vectorised_slice_sampler``, reference stepfuncs.pyx:537-630 -- one workgroup on the device here).  With
-    ``device_rng=DeviceRNG(seed)`` and the conditions of ``_device_route`` the whole refill runs on the device instead."""
+    ``device_rng=DeviceRNG(seed)`` and the conditions of ``_device_route`` the whole refill runs on the device instead, up to
+    ``device_max_dim`` dimensions (an integer in [1, 1024]; default 128, above it the host loop runs)."""
 
     def __init__(self, popsize, nsteps, generate_direction, scale_adapt_factor=1.0, adapt_slice_scale_target=2.0, scale=1.0,
-                 scale_jitter_func=None, slice_limit=slice_limit_to_unitcube, max_it=100, shrink_factor=1.0, device_rng=None):
+                 scale_jitter_func=None, slice_limit=slice_limit_to_unitcube, max_it=100, shrink_factor=1.0, device_rng=None,
+                 device_max_dim=128):
         assert shrink_factor >= 1.0, "The shrink factor should be greater than 1.0 to be efficient"
         self.popsize, self.nsteps, self.generate_direction = popsize, nsteps, generate_direction
         self.max_it, self.shrink_factor = max_it, shrink_factor
@@ -327,6 +345,7 @@ class PopulationSimpleSliceSampler(_BatchedPopulationSampler):
         if device_rng is not None and not isinstance(device_rng, DeviceRNG):
             raise TypeError("device_rng must be an ultranest_amd.regions.DeviceRNG")
         self.device_rng = device_rng
+        self.device_max_dim = _checked_device_max_dim(device_max_dim)
         self.force_slots_per_poll = 0     # tests: slots queued between two reads of the control block (0: the library's policy)
         self._sslice = None
         self._seen = dict(region=None, layer=None, r2=None, calls=0)
@@ -338,10 +357,11 @@ class PopulationSimpleSliceSampler(_BatchedPopulationSampler):
     def _device_route(self, transform, loglike, ndim=None, test=False):
         """What a refill runs on: None = the host loop; else ``(device_kind, limit, tspec, lspec, user)`` of a whole refill on
         the device -- it takes ``device_rng``, a direction generator with a ``device_kind``, a resident model (both
-        callbacks with a built-in ``device_spec``, or a user model as ``devicemodel.device_route`` decides it), at most 128
-        dimensions (``mlf_sslice``: one wave per worker, lane = coordinate pair), one of this module's two ``slice_limit``
-        functions (by identity; `limit` 0 = unit cube, 1 = clipped to [-1, 1]) and no ``test`` start."""
-        if self.device_rng is None or test or (ndim is not None and ndim > 128):
+        callbacks with a built-in ``device_spec``, or a user model as ``devicemodel.device_route`` decides it), at most
+        ``device_max_dim`` dimensions (``mlf_sslice``: one wave per worker; up to 128 dimensions lane = coordinate pair, above
+        the lanes stride over the row), one of this module's two ``slice_limit`` functions (by identity; `limit` 0 = unit
+        cube, 1 = clipped to [-1, 1]) and no ``test`` start."""
+        if self.device_rng is None or test or (ndim is not None and ndim > self.device_max_dim):
             return None
         device_kind = getattr(self.generate_direction, "device_kind", None)
         if device_kind is None:
