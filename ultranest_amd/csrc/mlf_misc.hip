@@ -586,7 +586,7 @@ __global__ __launch_bounds__(64 * kCovWaves) void k_boot_cov(const double *__res
     if (k0 + q < d && l < d) {
       double tot = 0.0;
       for (int w = 0; w < kCovWaves; ++w) tot += part[w][q][l];
-      cov[((long long)b * d + k0 + q) * d + l] = tot / (double)(cnt - 1);
+      cov[((long long)b * d + k0 + q) * d + l] = cnt > 1 ? tot / (double)(cnt - 1) : NAN;   // as k_boot_cov_wide: fewer than two rows have no covariance
     }
   }
 }
@@ -673,7 +673,7 @@ __device__ __forceinline__ void cov_block(const double *__restrict__ u, int d, c
     if (k < d && col_l < d) {
       double tot = 0.0;
       for (int w = 0; w < kCovWaves; ++w) tot += part[w][kk][c][l];
-      tot /= (double)(cnt - 1);
+      tot = cnt > 1 ? tot / (double)(cnt - 1) : NAN;   // as k_boot_cov_wide: fewer than two rows have no covariance (an empty list gave -0.0)
       cov_b[(long long)k * d + col_l] = tot;
       if (c > 0) cov_b[(long long)col_l * d + k] = tot;   // the mirror image of an off-diagonal chunk
     }

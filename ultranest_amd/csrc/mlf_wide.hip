@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256) void k_boot_mean_wide(const double *__restrict
   const int *list = idx + (size_t)b * n;
   double s = 0.0;
   for (int e = 0; e < cnt; ++e) s += u[(size_t)list[e] * d + c];
-  mean[(size_t)b * d + c] = cnt > 0 ? s / (double)cnt : 0.0;
+  mean[(size_t)b * d + c] = s / (double)cnt;   // an empty list: 0 / 0 = NaN, as k_boot_mean
 }
 
 // cov[a][c] = sum over the selected rows of (x_a - m_a)(x_c - m_c) / (count - 1)   (np.cov of the centred rows, tolerance class);

@@ -26,7 +26,11 @@ logvolscale = 1/2 sum log L: no explicit inverse), `inv` + two `eigh` for the wr
 TOLERANCE CLASS, not bit parity with the default path: T, cov agree to ~1e-12 relative (different summation orders in the
 moments; eigh instead of inv), `unormed` with them; GIVEN T, the whitening is the region's own chain, so the radius is the
 kernel's exact answer for the `unormed` it is handed (tests/test_device_rebuild.py: against the golden bootstrap vectors
-g3 on their own inputs bit for bit, against the default path equal-or-adjacent binary32).  Cluster labels exactly (as long
+g3 on their own inputs bit for bit, against the default path equal-or-adjacent binary32).  The enlargement f is in the 1e-10
+class of the default path for live points spread over the cube; for points concentrated at 0.3 +- 1e-6 f itself is ill
+conditioned: there the reference's binary64 formulation is 3e-11 to 5e-10 from the exact value and these kernels 5e-12 to
+2e-10 (tests/test_ellipsoid_forms_gpu.py, Stage C; its Stage A holds the moment kernels, this module's all-ones selection
+among the cases, to bounds derived from their summation orders).  Cluster labels exactly (as long
 as no pair sits within rounding of the linking length); masks are exact FOR THE REGION AS BUILT.  `np.random` is consumed
 exactly as by the default path (one `randint(N, size=N)` per bootstrap round).  Supported: AffineLayer / LocalAffineLayer
 without wrapped axes, MLFriends, minvol = 0, d <= 64, one process; anything else -> `supported()` is False and the caller
