@@ -6,3 +6,5 @@ the vectorized-likelihood batch call.  Compute runs in hand-written HIP kernels 
 of ``include/mlfriends_hip.h``; there is no CPU fallback.
 """
 __version__ = "0.1.0"
+
+from . import priors  # noqa: E402,F401  (the prior library of device models: ultranest_amd.priors)

@@ -17,6 +17,8 @@ The sources define::
     __device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux);           // required
     __device__ void mlf_user_transform(const double *u, double *p, int d, const double *aux, long long naux);  // optional
 
+(``ultranest_amd.priors`` writes the transform source from a list of priors -- ``PriorTransform([...]).model(loglike_source)``.)
+
 ``aux`` is the model's data array (float64, uploaded once).  The code runs on a shared GPU: it reads ``aux`` only
 within ``naux``, writes nothing but the ``p`` row it is handed, and contains no inline assembly.  It is compiled with
 ``-O3 -std=c++17 -ffp-contract=off`` (the library's arithmetic contract: no FMA is formed, so a restated built-in

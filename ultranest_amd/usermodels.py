@@ -9,6 +9,8 @@
   gauss_derived  gauss with three derived parameters (``DeviceModel(..., nderived=3)``) whose arithmetic numpy reproduces bit for
               bit: q0 = p[0] + p[1], q1 = p[0] * p[1], q2 = the sum of p[k] in ascending k from 0.0
               (``np.cumsum(p, axis=1)[:, -1]``); no log or exp
+  gauss_normal_prior  gauss under independent Normal priors from the prior library (``ultranest_amd.priors``), with its
+              analytic evidence
 
 Likelihoods summed over data terms (``DeviceModel(..., nterms=K)``: one wave per row, the lanes split the terms), each with a
 default-form twin that computes the same terms in a serial loop k = 0..K-1 inside ``mlf_user_loglike``:
@@ -116,6 +118,21 @@ def gauss_centers(ndim, sigma=0.1):
 def gauss(ndim, sigma=0.1, affine=False):
     return DeviceModel(ndim, GAUSS_LOGLIKE % float(sigma), AFFINE_TRANSFORM if affine else None,
                        aux=gauss_centers(ndim, sigma), name="gauss%d" % ndim)
+
+
+def gauss_normal_prior(ndim, sigma=0.1, prior_sigma=1.0, prior_mean=0.5):
+    """The normalised Gaussian of `gauss` (centres c_k = gauss_centers, width sigma) under independent priors
+    ``Normal(m_k, t)`` from ``ultranest_amd.priors`` (m_k = prior_mean, a number or one per column; t = prior_sigma).  Returns
+    ``(model, lnZ)`` with the analytic evidence ln Z = sum_k ln N(c_k; m_k, sqrt(sigma^2 + t^2)): the convolution of two
+    Gaussians.  With the defaults every centre lies within 0.25 t of its prior's mean: the posterior sits in the prior's bulk."""
+    from . import priors
+    centers = gauss_centers(ndim, sigma)
+    means = np.broadcast_to(np.asarray(prior_mean, dtype=float), (ndim,))
+    pt = priors.PriorTransform([priors.Normal(m, prior_sigma, name="x%d" % k) for k, m in enumerate(means)])
+    model = pt.model(GAUSS_LOGLIKE % float(sigma), aux=centers, name="gauss_normal_prior%d" % ndim)
+    var = float(sigma) ** 2 + float(prior_sigma) ** 2
+    lnz = float(np.sum(-0.5 * (centers - means) ** 2 / var - 0.5 * np.log(2 * np.pi * var)))
+    return model, lnz
 
 
 GAUSS_DERIVED = r"""
