@@ -53,8 +53,29 @@ and ``+`` (no FMA is formed), so numpy restates it bit for bit from the z row; n
 ``OrderedUniform(lo, hi, n)``, an ascending vector (the order statistics of n uniform draws):
 ``t_(n-1) = exp(log(u_(n-1)) / n)``, ``t_k = t_(k+1) * exp(log(u_k) / (k + 1))`` for k = n-2 down to 0, ``p_k = lo + t_k * w``.
 
-Gamma, beta, Student-t and Dirichlet priors need inverse incomplete gamma / beta functions, which have no closed form: they
-are out of scope of this library (write them as a ``transform_source`` of your own).
+Gamma, beta, Student-t and Dirichlet priors need inverse incomplete gamma / beta functions, which have no closed form.  Their
+device functions are iterative and live in a second header, ``csrc/mlf_priors_special_dev.hpp``, whose text follows the first
+one's in ``source`` only when the list holds one of these families (a closed-form list gives exactly the text it always gave).
+Every function works from the smaller tail q = min(u, 1 - u) and runs Newton's iteration on ln(tail) in the logarithm of the
+unknown, with a compile-time cap on every loop (48 steps, 3000 terms); P, Q are the regularized incomplete gamma functions,
+I_x(a, b) the regularized incomplete beta function::
+
+    Gamma(shape, scale=1)               scale * x;  P(shape, x) = u for u <= 0.5, Q(shape, x) = 1 - u otherwise
+    ChiSquared(k)                       Gamma(k / 2, 2): the same device function
+    InverseGamma(shape, scale=1)        scale / x;  Q(shape, x) = u for u <= 0.5, P(shape, x) = 1 - u otherwise
+    Beta(a, b)  on (0, 1)               x with I_x(a, b) = u, solved for the smaller of x and y = 1 - x, returned as x or 1 - y
+    StudentT(nu, loc=0, scale=1)        loc + scale * t;  t = -sqrt(nu y / x) from x = nu / (nu + t^2) with I_x(nu/2, 1/2) = 2 q,
+                                        carried as ln x and ln y; the sign is flipped for u > 0.5 (StudentT(nu, 0, 1) is odd bit
+                                        for bit), t = 0 at u = 0.5
+    Dirichlet(alpha), block n <= 64     g_k = the Gamma(alpha_k, 1) quantile of u_k into p[k];  s = ((g_0 + g_1) + ...) + g_(n-1)
+                                        in ascending order with plain +;  p[k] = g_k / s, or 1 / n for every k if s == 0
+
+Accepted ranges (the ranges over which each quantile is held to 1e-12 * S against 60-digit references from u = 2^-1022 to
+1 - 2^-53; outside them the constructor raises ``ValueError``): shape, a, b and every alpha_k in [0.1, 1000], k in [0.2, 2000],
+nu in [1, 1000]; scale > 0, loc finite.  ``lgamma(shape + 1)``, ``ln B(a, b)``, ``1 / shape`` and the logarithms of the
+parameters are computed here in binary64 and passed as hexadecimal literals.  The columns of a Dirichlet block sum to 1, so no
+ellipsoid in parameter space has a volume: a driver's t-region cannot be built over it and the drivers run without one, as the
+reference does.  An iterative quantile costs several times a ``normcdfinv`` (DESIGN.md 7f has the measurement).
 
 Every prior validates its parameters at construction (``ValueError`` before anything is compiled) and takes an optional
 ``name``.  ``Uniform(..., circular=True)`` marks a periodic parameter (``PriorTransform.wrapped_dims``).
@@ -68,7 +89,10 @@ from . import devicemodel
 from .devicemodel import DeviceModel
 
 HEADER = os.path.join(devicemodel.INCLUDE_DIR, "mlf_priors_dev.hpp")
-MAX_BLOCK = 64          # largest MultivariateNormal block (its triangular product is straight-line code)
+SPECIAL_HEADER = os.path.join(devicemodel.INCLUDE_DIR, "mlf_priors_special_dev.hpp")
+MAX_BLOCK = 64          # largest MultivariateNormal or Dirichlet block (straight-line code)
+SHAPE_MIN, SHAPE_MAX = 0.1, 1000.0      # Gamma / InverseGamma shape, Beta a and b, Dirichlet alpha_k; ChiSquared k is twice it
+NU_MIN, NU_MAX = 1.0, 1000.0            # StudentT degrees of freedom
 
 CONSTANT_LOGLIKE = r"""
 __device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux) {
@@ -362,9 +386,124 @@ class OrderedUniform(Prior):
         return out
 
 
+def _in_range(owner, lo, hi, **values):
+    out = _finite(owner, **values)
+    for (key, _), v in zip(values.items(), out):
+        if not lo <= v <= hi:
+            raise ValueError("%s: %s must lie in [%g, %g] (the range over which the device quantile holds its error bound), "
+                             "got %r" % (owner, key, lo, hi, v))
+    return out
+
+
+def _lbeta(a, b):
+    return math.lgamma(a) + math.lgamma(b) - math.lgamma(a + b)
+
+
+class _Special(Prior):
+    """a family whose quantile is iterative (``csrc/mlf_priors_special_dev.hpp``): ``fn`` and ``consts``, the device function
+    and the constants it takes after u"""
+    special = True
+    fn, consts = None, ()
+
+    def call(self, u):
+        return self._call(self.fn, u, *self.consts)
+
+
+def _gamma_consts(scale, a):
+    return (scale, a, 1.0 / a, math.log(a), math.lgamma(a + 1.0))
+
+
+class Gamma(_Special):
+    fn = "mlf_prior_gamma"
+
+    def __init__(self, shape, scale=1.0, name=None):
+        Prior.__init__(self, name)
+        self.shape, = _in_range("Gamma", SHAPE_MIN, SHAPE_MAX, shape=shape)
+        self.scale, = _positive("Gamma", scale=scale)
+        self.consts = _gamma_consts(self.scale, self.shape)
+
+
+class ChiSquared(_Special):
+    fn = "mlf_prior_gamma"
+
+    def __init__(self, k, name=None):
+        Prior.__init__(self, name)
+        self.k, = _in_range("ChiSquared", 2.0 * SHAPE_MIN, 2.0 * SHAPE_MAX, k=k)
+        self.shape, self.scale = 0.5 * self.k, 2.0
+        self.consts = _gamma_consts(self.scale, self.shape)
+
+
+class InverseGamma(_Special):
+    fn = "mlf_prior_invgamma"
+
+    def __init__(self, shape, scale=1.0, name=None):
+        Prior.__init__(self, name)
+        self.shape, = _in_range("InverseGamma", SHAPE_MIN, SHAPE_MAX, shape=shape)
+        self.scale, = _positive("InverseGamma", scale=scale)
+        self.consts = _gamma_consts(self.scale, self.shape)
+
+
+class Beta(_Special):
+    fn = "mlf_prior_beta"
+
+    def __init__(self, a, b, name=None):
+        Prior.__init__(self, name)
+        self.a, self.b = _in_range("Beta", SHAPE_MIN, SHAPE_MAX, a=a, b=b)
+        self.consts = (self.a, self.b, _lbeta(self.a, self.b), math.log(self.a), math.log(self.b))
+
+
+class StudentT(_Special):
+    fn = "mlf_prior_studentt"
+
+    def __init__(self, nu, loc=0.0, scale=1.0, name=None):
+        Prior.__init__(self, name)
+        self.nu, = _in_range("StudentT", NU_MIN, NU_MAX, nu=nu)
+        self.loc, = _finite("StudentT", loc=loc)
+        self.scale, = _positive("StudentT", scale=scale)
+        ha = 0.5 * self.nu
+        self.consts = (self.loc, self.scale, ha, _lbeta(ha, 0.5), math.log(ha), math.log(self.nu))
+
+
+class Dirichlet(_Special):
+    def __init__(self, alpha, name=None):
+        Prior.__init__(self, name)
+        try:
+            alpha = np.array(alpha, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError("Dirichlet: alpha must be a vector of numbers")
+        if alpha.ndim != 1 or not 1 <= len(alpha) <= MAX_BLOCK:
+            raise ValueError("Dirichlet: alpha must be a vector of 1 to %d entries, got shape %s" % (MAX_BLOCK, alpha.shape))
+        for k, v in enumerate(alpha):
+            _in_range("Dirichlet", SHAPE_MIN, SHAPE_MAX, **{"alpha[%d]" % k: v})
+        self.alpha = alpha
+        self.size = len(alpha)
+
+    def gammas(self):
+        """the block's Gamma(alpha_k, 1) columns: the g row of the module docstring"""
+        return [Gamma(a, 1.0) for a in self.alpha]
+
+    def statements(self, first):
+        n = self.size
+        out = ["p[%d] = %s;" % (first + k, g.call("u[%d]" % (first + k))) for k, g in enumerate(self.gammas())]
+        out += ["{", "  double s = p[%d];" % first]
+        out += ["  s = s + p[%d];" % (first + k) for k in range(1, n)]
+        out.append("  if (s == %s) {" % _hex(0.0))
+        out += ["    p[%d] = %s;" % (first + k, _hex(1.0 / n)) for k in range(n)]
+        out.append("  } else {")
+        out += ["    p[%d] = p[%d] / s;" % (first + k, first + k) for k in range(n)]
+        out += ["  }", "}"]
+        return out
+
+
 def header_text():
     """the text of ``csrc/mlf_priors_dev.hpp``"""
     with open(HEADER) as fh:
+        return fh.read()
+
+
+def special_header_text():
+    """the text of ``csrc/mlf_priors_special_dev.hpp``"""
+    with open(SPECIAL_HEADER) as fh:
         return fh.read()
 
 
@@ -394,7 +533,8 @@ class PriorTransform(object):
             body += p.statements(first)
             first += p.size
         self.is_affine = all(p.affine for p in self.priors)
-        self.source = (header_text() + "\n__device__ void mlf_user_transform(const double *u, double *p, int d, const double *aux, "
+        special = special_header_text() if any(getattr(p, "special", False) for p in self.priors) else ""
+        self.source = (header_text() + special + "\n__device__ void mlf_user_transform(const double *u, double *p, int d, const double *aux, "
                        "long long naux) {\n" + "".join("  %s\n" % s for s in body) + "}\n")
         self._model = None
 
@@ -413,4 +553,5 @@ class PriorTransform(object):
 
 __all__ = ["Prior", "Fixed", "Uniform", "LogUniform", "Normal", "TruncatedNormal", "LogNormal", "HalfNormal", "Exponential",
            "Rayleigh", "Weibull", "Pareto", "Cauchy", "HalfCauchy", "Laplace", "Logistic", "Gumbel", "Triangular", "Sine",
-           "Cosine", "MultivariateNormal", "OrderedUniform", "PriorTransform"]
+           "Cosine", "MultivariateNormal", "OrderedUniform", "Gamma", "ChiSquared", "InverseGamma", "Beta", "StudentT",
+           "Dirichlet", "PriorTransform"]
