@@ -1,4 +1,4 @@
-"""Prior library for device models: closed-form quantile transforms.
+"""Prior library for device models: quantile transforms, closed-form, iterative, parameter-dependent and tabulated.
 
 A prior transform maps the unit cube to the parameters, column by column, through each prior's quantile function (inverse
 CDF).  In the reference users write it with ``scipy.stats.*.ppf`` inside ``transform``; a host callback keeps a model off every
@@ -79,6 +79,78 @@ reference does.  An iterative quantile costs several times a ``normcdfinv`` (DES
 
 Every prior validates its parameters at construction (``ValueError`` before anything is compiled) and takes an optional
 ``name``.  ``Uniform(..., circular=True)`` marks a periodic parameter (``PriorTransform.wrapped_dims``).
+
+Parameters that are other parameters: ``Ref``
+---------------------------------------------
+``Ref(target, scale=1.0, offset=0.0)`` in place of a number makes a prior's parameter the value of another column of the same
+row, ``scale * p[j] + offset`` (plain ``*`` and ``+``, hexadecimal ``scale`` and ``offset``; just ``p[j]`` for scale 1 and
+offset 0).  `target` is a name of ``paramnames`` (``name_k`` for a column of a block) or a column index::
+
+    PriorTransform([Normal(0.0, 10.0, name="mu"), LogUniform(0.01, 10.0, name="tau"),
+                    Normal(Ref("mu"), Ref("tau"), name="theta0"), TruncatedNormal(Ref("mu"), Ref("tau"), -50.0, 50.0, name="theta1"),
+                    Uniform(Ref("theta1"), 60.0, name="upper"), Normal(0.0, Ref("tau", scale=2.0, offset=0.1))])
+
+A ``Ref`` is taken by: ``Uniform`` lo, hi (not with ``circular=True``: the period would vary); ``LogUniform`` lo, hi; ``Normal``,
+``LogNormal`` mu, sigma; ``TruncatedNormal`` mu, sigma, lo, hi; the scale of ``HalfNormal``, ``Exponential``, ``Rayleigh``,
+``HalfCauchy``; ``Weibull`` scale, k; ``Pareto`` xm, alpha; loc and scale of ``Cauchy``, ``Laplace``, ``Logistic``, ``Gumbel``;
+``Triangular`` lo, mode, hi; the **scale** of ``Gamma`` and ``InverseGamma``; **loc and scale** of ``StudentT``.  The shapes of
+the iterative families (shape, k, a, b, nu, alpha: their lgamma and ln B constants come from the host, and their error bounds
+hold over a stated range), every parameter of the three block priors, ``Tabulated`` and ``Fixed`` stay constants (a ``Ref``
+there is a ``ValueError``); blocks and tables may be targets.
+
+Order.  Column j still consumes u[j]; the statements are written in dependency order, a stable topological sort with ties in
+list order (``PriorTransform.order``; ``PriorTransform.parents[j]`` are the columns that column j reads).  A cycle, a
+self-reference, an unknown target and a referenced name that occurs twice are ``ValueError``s.
+
+Support check.  Every column has a support, a closed interval of the extended reals (``PriorTransform.supports``): ``Fixed``
+[v, v]; ``Uniform``, ``LogUniform``, ``TruncatedNormal``, ``Triangular``, ``OrderedUniform``: their bounds; ``Sine`` [0, pi];
+``Cosine`` [-pi/2, pi/2]; ``Beta``, ``Dirichlet`` [0, 1]; ``Pareto`` [xm, inf); the positive families [0, inf); ``Tabulated``
+[x_0, x_(n-1)]; everything else the real line; a ``Ref`` maps its target's support affinely, and a prior with ``Ref`` bounds
+takes the hull.  A ``Ref`` in a scale-like or strictly positive parameter needs a mapped support with infimum >= 0, and for an
+ordered pair (lo / hi, lo / mode / hi) sup(support(lo)) <= inf(support(hi)) must hold; otherwise ``ValueError`` names the
+parameter and the target's support (``Normal(0, Ref("mu"))`` with mu ~ Normal is refused, and so is ``Uniform(Ref("x"), 20)``
+over an unbounded x).
+
+Run-time contract.  What the support check cannot exclude is a value that rounded to 0 or overflowed to inf, or the NaN of a
+parent.  A scale-like parameter must be >= 0 and finite (0 gives the point mass at loc); a strictly positive parameter
+(``Weibull`` k, ``Pareto`` xm and alpha, ``LogUniform`` bounds, ``TruncatedNormal`` sigma) must be > 0 and finite; a location must
+be finite; bounds must be ordered (equal ``Uniform`` or ``LogUniform`` bounds give the point mass; ``Triangular`` needs lo < hi,
+``TruncatedNormal`` some probability between its bounds in binary64).  If any of these fails the column is NaN, and so is every
+column that depends on it.  The likelihood is still called; a NaN L fails ``L > Lmin``, so such a row is never kept, harvested
+or accepted by any route.
+
+Device code (``csrc/mlf_priors_rt_dev.hpp``, appended to ``source`` after the other header(s) only when the list holds a ``Ref``
+or a ``Tabulated``: every other list gives exactly the text it always gave).  Pass-through families call the existing
+``mlf_prior_*`` function with each run-time argument wrapped in a guard that returns the value or NaN (``mlf_prior_rt_loc``,
+``_scale``, ``_pos``): with ``Fixed`` parents such a column is bit for bit the constant-parameter column.  Four families take
+constants that the host computes for constants; with a ``Ref`` the device evaluates the same expressions::
+
+    Uniform          lo + u * (hi - lo)                                      (numpy restates it bit for bit)
+    LogUniform       a = log(lo);  exp(a + u * (log(hi) - a))
+    TruncatedNormal  a, b, Fa, Fb, Qa, Qb from 0.5 * erfc(-+x / sqrt2) on the device, then the constant form's two-tail formula
+                     and clamp; NaN if neither Fb > Fa nor Qa > Qb
+    Triangular       w = hi - lo, c = (mode - lo) / w, c1 = w * (mode - lo), c2 = w * (hi - mode), then the constant form
+
+``is_affine`` is False for a list that holds a ``Ref``.
+
+Quantile functions given as numbers: ``Tabulated``
+--------------------------------------------------
+::
+
+    Tabulated(x, cdf)                          knots of the CDF: F(x_k) = cdf_k, linear in between
+    Tabulated.from_samples(samples)            sorted samples, cdf_k = k / (m - 1) in binary64 (np.quantile's "linear" rule)
+    Tabulated.from_histogram(edges, density)   piecewise-constant density; the CDF normalised, its ends pinned to 0.0 and 1.0
+
+2 <= n <= 4096 knots, at most 16 384 over all tables of one transform; everything finite; x non-decreasing with
+x[0] < x[-1] (a repeated x is a point mass); cdf non-decreasing from exactly 0.0 to exactly 1.0 (a repeated cdf is a gap in the
+support); every slope finite; more than 4096 samples are refused with the advice to pass quantile knots.  Weighted samples: pass
+``x, cdf``.  The host computes the slopes in binary64, s_k = (x_(k+1) - x_k) / (c_(k+1) - c_k), 0 on a flat CDF segment, and the
+table goes into ``source`` as one ``static __device__ const double`` array per prior, ``[c | x | s]`` in hexadecimal literals.
+The formula is the interface: k = the largest index <= n - 2 with c_k <= u (a branch-free bisection of ceil(log2(n - 1)) probes),
+dl = u - c_k, dr = c_(k+1) - u, ``p = dl <= dr ? x_k + dl * s_k : x_(k+1) - dr * s_k``: only +, -, * and comparisons, so numpy
+restates it bit for bit; it is monotone in u, stays within [x_0, x_(n-1)] and lies within
+2^-52 |p| + 3 * 2^-53 |x_(k+1) - x_k| of the exact piecewise-linear inverse of the binary64 table (tests/prior_rt_reference.py
+derives the bound).  Every load stays inside the table for every u.
 """
 import math
 import os
@@ -93,6 +165,9 @@ SPECIAL_HEADER = os.path.join(devicemodel.INCLUDE_DIR, "mlf_priors_special_dev.h
 MAX_BLOCK = 64          # largest MultivariateNormal or Dirichlet block (straight-line code)
 SHAPE_MIN, SHAPE_MAX = 0.1, 1000.0      # Gamma / InverseGamma shape, Beta a and b, Dirichlet alpha_k; ChiSquared k is twice it
 NU_MIN, NU_MAX = 1.0, 1000.0            # StudentT degrees of freedom
+RT_HEADER = os.path.join(devicemodel.INCLUDE_DIR, "mlf_priors_rt_dev.hpp")
+MAX_KNOTS = 4096            # knots of one Tabulated
+MAX_TABLE_KNOTS = 16384     # knots of all tables of one transform
 
 CONSTANT_LOGLIKE = r"""
 __device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux) {
@@ -132,29 +207,134 @@ def _ordered(owner, lo, hi):
         raise ValueError("%s: hi must be larger than lo, got lo = %r, hi = %r" % (owner, lo, hi))
 
 
+class Ref(object):
+    """A prior parameter that is another column of the row: ``scale * p[j] + offset`` (module docstring).  `target` is a
+    column name of ``PriorTransform.paramnames`` or a column index; it is resolved when the list becomes a PriorTransform."""
+
+    def __init__(self, target, scale=1.0, offset=0.0):
+        if isinstance(target, bool) or not isinstance(target, (str, int, np.integer)):
+            raise ValueError("Ref: target must be a column name or a column index, got %r" % (target,))
+        self.target = target if isinstance(target, str) else int(target)
+        self.scale, self.offset = _finite("Ref", scale=scale, offset=offset)
+        if self.scale == 0:
+            raise ValueError("Ref: scale must not be 0 (a constant parameter is written as a number)")
+
+    def __repr__(self):
+        return "Ref(%r, scale=%r, offset=%r)" % (self.target, self.scale, self.offset)
+
+    def expr(self, j):
+        """the C++ expression of the value from column j: plain * and +, hexadecimal constants"""
+        if self.scale == 1.0 and self.offset == 0.0:
+            return "p[%d]" % j
+        return "(%s * p[%d] + %s)" % (_hex(self.scale), j, _hex(self.offset))
+
+    def value(self, pj):
+        """the same expression in numpy (bit for bit: one product, one sum)"""
+        if self.scale == 1.0 and self.offset == 0.0:
+            return pj
+        return self.scale * pj + self.offset
+
+    def map(self, lo, hi):
+        """the image of the closed interval [lo, hi] of the extended reals"""
+        a, b = self.scale * lo + self.offset, self.scale * hi + self.offset
+        return (a, b) if self.scale > 0 else (b, a)
+
+
+_REAL_LINE = (-math.inf, math.inf)
+_POSITIVE = (0.0, math.inf)
+_GUARD = {"loc": "mlf_prior_rt_loc", "scale": "mlf_prior_rt_scale", "pos": "mlf_prior_rt_pos"}
+
+
 class Prior(object):
-    """One column (``size == 1``) or one block of consecutive columns of a prior transform."""
+    """One column (``size == 1``) or one block of consecutive columns of a prior transform.
+
+    ``refs`` maps the attribute of a parameter given as a ``Ref`` to ``(ref, kind, label)``, kind one of "loc" (finite),
+    "scale" (>= 0 and finite) and "pos" (> 0 and finite); ``ordered`` names the attributes that must ascend; ``support`` is the
+    closed interval of the extended reals that holds every value of the column."""
     size = 1
     affine = False
     circular = False
+    ordered = ()
+    base_support = _REAL_LINE
 
     def __init__(self, name=None):
         self.name = name
+        self.refs = {}
 
     def names(self, first):
         base = self.name or "p%d" % first
         return [base] if self.size == 1 else ["%s_%d" % (base, k) for k in range(self.size)]
 
-    def call(self, u):
-        """the C++ expression of a one-column prior from the expression `u`"""
+    def call(self, u, cols=None):
+        """the C++ expression of a one-column prior from the expression `u`; `cols` maps the attribute of every ``Ref``
+        parameter to the column it reads"""
         raise NotImplementedError
 
-    def statements(self, first):
+    def statements(self, first, cols=None):
         """the C++ statements that write p[first .. first + size)"""
-        return ["p[%d] = %s;" % (first, self.call("u[%d]" % first))]
+        return ["p[%d] = %s;" % (first, self.call("u[%d]" % first, cols))]
 
     def _call(self, fn, u, *consts):
         return "%s(%s)" % (fn, ", ".join((u,) + tuple(_hex(c) for c in consts)))
+
+    def _par(self, kind, attr, v, label=None):
+        """a parameter that may be a Ref: a constant is validated as it always was"""
+        label = label or attr
+        if isinstance(v, Ref):
+            self.refs[attr] = (v, kind, label)
+            return v
+        check = _finite if kind == "loc" else _positive
+        return check(type(self).__name__, **{label: v})[0]
+
+    def _const(self, attr, v, label=None):
+        """a parameter that stays a constant"""
+        if isinstance(v, Ref):
+            raise ValueError("%s: %s must be a constant, not a Ref" % (type(self).__name__, label or attr))
+        return v
+
+    def _arg(self, attr, cols, guard=True):
+        """the C++ expression of one parameter of a call with run-time arguments"""
+        if attr not in self.refs:
+            return _hex(getattr(self, attr))
+        ref, kind, _ = self.refs[attr]
+        e = ref.expr(cols[attr])
+        return "%s(%s)" % (_GUARD[kind], e) if guard else e
+
+    def _rt_call(self, fn, u, cols, attrs, guard=True):
+        return "%s(%s)" % (fn, ", ".join([u] + [self._arg(a, cols, guard) for a in attrs]))
+
+    def interval(self, attr, cols, supports):
+        """the interval that holds a parameter: [v, v] of a constant, the mapped support of a Ref's target"""
+        if attr in self.refs:
+            return self.refs[attr][0].map(*supports[cols[attr]])
+        v = getattr(self, attr)
+        return (v, v)
+
+    def check_refs(self, cols, supports, names):
+        """the support check of the module docstring: ValueError naming the parameter and the target's support"""
+        owner = type(self).__name__
+
+        def describe(attr):
+            ref, _, label = self.refs[attr]
+            j = cols[attr]
+            return "%s = %r reads column %d (%s) with support [%r, %r]" % ((label, ref, j, names[j]) + tuple(supports[j]))
+
+        for attr, (ref, kind, label) in self.refs.items():
+            lo, hi = self.interval(attr, cols, supports)
+            if kind in ("scale", "pos") and not lo >= 0:
+                raise ValueError("%s: %s, so the parameter is not bounded below by 0" % (owner, describe(attr)))
+        for i, a in enumerate(self.ordered):
+            for b in self.ordered[i + 1:]:
+                if a in self.refs or b in self.refs:
+                    sup, inf = self.interval(a, cols, supports)[1], self.interval(b, cols, supports)[0]
+                    if not sup <= inf:
+                        raise ValueError("%s: %s <= %s cannot be guaranteed (sup %r, inf %r): %s" % (
+                            owner, self.refs.get(a, (0, 0, a))[2], self.refs.get(b, (0, 0, b))[2], sup, inf,
+                            "; ".join(describe(x) for x in (a, b) if x in self.refs)))
+
+    def support(self, cols=None, supports=None):
+        """(lo, hi): the interval that holds every value of the column (of each column of a block prior)"""
+        return self.base_support
 
 
 class Fixed(Prior):
@@ -162,53 +342,81 @@ class Fixed(Prior):
 
     def __init__(self, v, name=None):
         Prior.__init__(self, name)
-        self.v, = _finite("Fixed", v=v)
+        self.v, = _finite("Fixed", v=self._const("v", v))
 
-    def call(self, u):
+    def call(self, u, cols=None):
         return _hex(self.v)
 
+    def support(self, cols=None, supports=None):
+        return (self.v, self.v)
 
-class Uniform(Prior):
+
+class _Bounded(Prior):
+    """a family on [lo, hi]: the support is the hull of the two parameters' intervals"""
+    ordered = ("lo", "hi")
+
+    def support(self, cols=None, supports=None):
+        return (self.interval("lo", cols, supports)[0], self.interval("hi", cols, supports)[1])
+
+
+class Uniform(_Bounded):
     affine = True
 
     def __init__(self, lo, hi, circular=False, name=None):
         Prior.__init__(self, name)
-        self.lo, self.hi = _finite("Uniform", lo=lo, hi=hi)
+        self.lo, self.hi = self._par("loc", "lo", lo), self._par("loc", "hi", hi)
+        self.circular = bool(circular)
+        if self.refs:
+            self.affine = False
+            if self.circular:
+                raise ValueError("Uniform: a circular parameter needs constant bounds (the period would vary with a Ref)")
+            return
         _ordered("Uniform", self.lo, self.hi)
         self.w, = _finite("Uniform", width=self.hi - self.lo)
-        self.circular = bool(circular)
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call("mlf_prior_rt_uniform", u, cols, ("lo", "hi"), guard=False)
         return self._call("mlf_prior_uniform", u, self.lo, self.w)
 
 
-class LogUniform(Prior):
+class LogUniform(_Bounded):
     def __init__(self, lo, hi, name=None):
         Prior.__init__(self, name)
-        self.lo, self.hi = _positive("LogUniform", lo=lo, hi=hi)
+        self.lo, self.hi = self._par("pos", "lo", lo), self._par("pos", "hi", hi)
+        if self.refs:
+            return
         _ordered("LogUniform", self.lo, self.hi)
         self.a = math.log(self.lo)
         self.w = math.log(self.hi) - math.log(self.lo)
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call("mlf_prior_rt_loguniform", u, cols, ("lo", "hi"), guard=False)
         return self._call("mlf_prior_loguniform", u, self.a, self.w)
 
 
 class Normal(Prior):
     def __init__(self, mu, sigma, name=None):
         Prior.__init__(self, name)
-        self.mu, = _finite("Normal", mu=mu)
-        self.sigma, = _positive("Normal", sigma=sigma)
+        self.mu = self._par("loc", "mu", mu)
+        self.sigma = self._par("scale", "sigma", sigma)
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call("mlf_prior_normal", u, cols, ("mu", "sigma"))
         return self._call("mlf_prior_normal", u, self.mu, self.sigma)
 
 
-class TruncatedNormal(Prior):
+class TruncatedNormal(_Bounded):
     def __init__(self, mu, sigma, lo, hi, name=None):
         Prior.__init__(self, name)
-        self.mu, self.lo, self.hi = _finite("TruncatedNormal", mu=mu, lo=lo, hi=hi)
-        self.sigma, = _positive("TruncatedNormal", sigma=sigma)
+        self.mu, self.lo, self.hi = self._par("loc", "mu", mu), self._par("loc", "lo", lo), self._par("loc", "hi", hi)
+        self.sigma = self._par("pos", "sigma", sigma)
+        if self.refs:
+            if "lo" not in self.refs and "hi" not in self.refs:
+                _ordered("TruncatedNormal", self.lo, self.hi)
+            return
         _ordered("TruncatedNormal", self.lo, self.hi)
         self.a, self.b = (self.lo - self.mu) / self.sigma, (self.hi - self.mu) / self.sigma
         r2 = math.sqrt(2.0)
@@ -217,28 +425,37 @@ class TruncatedNormal(Prior):
         if not (self.Fb > self.Fa or self.Qa > self.Qb):
             raise ValueError("TruncatedNormal: no probability between lo = %r and hi = %r in binary64" % (self.lo, self.hi))
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call("mlf_prior_rt_truncnormal", u, cols, ("mu", "sigma", "lo", "hi"), guard=False)
         return self._call("mlf_prior_truncnormal", u, self.mu, self.sigma, self.a, self.b, self.Fa, self.Fb, self.Qa, self.Qb)
 
 
 class LogNormal(Prior):
+    base_support = _POSITIVE
+
     def __init__(self, mu, sigma, name=None):
         Prior.__init__(self, name)
-        self.mu, = _finite("LogNormal", mu=mu)
-        self.sigma, = _positive("LogNormal", sigma=sigma)
+        self.mu = self._par("loc", "mu", mu)
+        self.sigma = self._par("scale", "sigma", sigma)
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call("mlf_prior_lognormal", u, cols, ("mu", "sigma"))
         return self._call("mlf_prior_lognormal", u, self.mu, self.sigma)
 
 
 class _OneScale(Prior):
     fn, key = None, "scale"
+    base_support = _POSITIVE
 
     def __init__(self, scale, name=None):
         Prior.__init__(self, name)
-        self.scale, = _positive(type(self).__name__, **{self.key: scale})
+        self.scale = self._par("scale", "scale", scale, self.key)
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call(self.fn, u, cols, ("scale",))
         return self._call(self.fn, u, self.scale)
 
 
@@ -259,13 +476,17 @@ class HalfCauchy(_OneScale):
 
 
 class _ScaleShape(Prior):
-    fn, keys = None, ("scale", "shape")
+    fn, keys, scale_kind = None, ("scale", "shape"), "scale"
+    base_support = _POSITIVE
 
     def __init__(self, scale, shape, name=None):
         Prior.__init__(self, name)
-        self.scale, self.shape = _positive(type(self).__name__, **{self.keys[0]: scale, self.keys[1]: shape})
+        self.scale = self._par(self.scale_kind, "scale", scale, self.keys[0])
+        self.shape = self._par("pos", "shape", shape, self.keys[1])
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call(self.fn, u, cols, ("scale", "shape"))
         return self._call(self.fn, u, self.scale, self.shape)
 
 
@@ -274,7 +495,10 @@ class Weibull(_ScaleShape):
 
 
 class Pareto(_ScaleShape):
-    fn, keys = "mlf_prior_pareto", ("xm", "alpha")
+    fn, keys, scale_kind = "mlf_prior_pareto", ("xm", "alpha"), "pos"
+
+    def support(self, cols=None, supports=None):
+        return (self.interval("scale", cols, supports)[0], math.inf)
 
 
 class _LocScale(Prior):
@@ -282,10 +506,12 @@ class _LocScale(Prior):
 
     def __init__(self, loc, scale, name=None):
         Prior.__init__(self, name)
-        self.loc, = _finite(type(self).__name__, loc=loc)
-        self.scale, = _positive(type(self).__name__, **{self.key: scale})
+        self.loc = self._par("loc", "loc", loc)
+        self.scale = self._par("scale", "scale", scale, self.key)
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call(self.fn, u, cols, ("loc", "scale"))
         return self._call(self.fn, u, self.loc, self.scale)
 
 
@@ -305,10 +531,17 @@ class Gumbel(_LocScale):
     fn, key = "mlf_prior_gumbel", "s"
 
 
-class Triangular(Prior):
+class Triangular(_Bounded):
+    ordered = ("lo", "mode", "hi")
+
     def __init__(self, lo, mode, hi, name=None):
         Prior.__init__(self, name)
-        self.lo, self.mode, self.hi = _finite("Triangular", lo=lo, mode=mode, hi=hi)
+        self.lo, self.mode, self.hi = self._par("loc", "lo", lo), self._par("loc", "mode", mode), self._par("loc", "hi", hi)
+        if self.refs:
+            consts = [getattr(self, a) for a in self.ordered if a not in self.refs]
+            if consts != sorted(consts):
+                raise ValueError("Triangular: lo <= mode <= hi must hold, got %r" % (consts,))
+            return
         _ordered("Triangular", self.lo, self.hi)
         if not self.lo <= self.mode <= self.hi:
             raise ValueError("Triangular: mode must lie in [lo, hi], got %r" % (self.mode,))
@@ -316,17 +549,23 @@ class Triangular(Prior):
         self.c = (self.mode - self.lo) / w
         self.c1, self.c2 = _finite("Triangular", c1=w * (self.mode - self.lo), c2=w * (self.hi - self.mode))
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            return self._rt_call("mlf_prior_rt_triangular", u, cols, ("lo", "mode", "hi"), guard=False)
         return self._call("mlf_prior_triangular", u, self.lo, self.hi, self.c, self.c1, self.c2)
 
 
 class Sine(Prior):
-    def call(self, u):
+    base_support = (0.0, math.pi)
+
+    def call(self, u, cols=None):
         return "mlf_prior_sine(%s)" % u
 
 
 class Cosine(Prior):
-    def call(self, u):
+    base_support = (-0.5 * math.pi, 0.5 * math.pi)
+
+    def call(self, u, cols=None):
         return "mlf_prior_cosine(%s)" % u
 
 
@@ -354,7 +593,7 @@ class MultivariateNormal(Prior):
         self.mean, self.cov, self.L = mean, cov, np.tril(L)
         self.size = len(mean)
 
-    def statements(self, first):
+    def statements(self, first, cols=None):
         n = self.size
         out = ["p[%d] = mlf_prior_z(u[%d]);" % (first + k, first + k) for k in range(n)]
         for i in range(n - 1, -1, -1):      # row i reads z_0 .. z_i only: descending rows may overwrite in place
@@ -366,6 +605,9 @@ class MultivariateNormal(Prior):
 
 
 class OrderedUniform(Prior):
+    def support(self, cols=None, supports=None):
+        return (self.lo, self.hi)
+
     def __init__(self, lo, hi, n, name=None):
         Prior.__init__(self, name)
         self.lo, self.hi = _finite("OrderedUniform", lo=lo, hi=hi)
@@ -375,7 +617,7 @@ class OrderedUniform(Prior):
             raise ValueError("OrderedUniform: n must be a positive integer, got %r" % (n,))
         self.size = int(n)
 
-    def statements(self, first):
+    def statements(self, first, cols=None):
         n = self.size
         out = ["{", "  double t = mlf_prior_ordered_factor(u[%d], %s);" % (first + n - 1, _hex(n)),
                "  p[%d] = %s + t * %s;" % (first + n - 1, _hex(self.lo), _hex(self.w))]
@@ -404,8 +646,12 @@ class _Special(Prior):
     and the constants it takes after u"""
     special = True
     fn, consts = None, ()
+    rt_attrs = ()       # the attributes behind the leading entries of `consts` that may be a Ref
 
-    def call(self, u):
+    def call(self, u, cols=None):
+        if self.refs:
+            head = [self._arg(a, cols) for a in self.rt_attrs]
+            return "%s(%s)" % (self.fn, ", ".join([u] + head + [_hex(c) for c in self.consts[len(head):]]))
         return self._call(self.fn, u, *self.consts)
 
 
@@ -414,17 +660,17 @@ def _gamma_consts(scale, a):
 
 
 class Gamma(_Special):
-    fn = "mlf_prior_gamma"
+    fn, rt_attrs, base_support = "mlf_prior_gamma", ("scale",), _POSITIVE
 
     def __init__(self, shape, scale=1.0, name=None):
         Prior.__init__(self, name)
         self.shape, = _in_range("Gamma", SHAPE_MIN, SHAPE_MAX, shape=shape)
-        self.scale, = _positive("Gamma", scale=scale)
+        self.scale = self._par("scale", "scale", scale)
         self.consts = _gamma_consts(self.scale, self.shape)
 
 
 class ChiSquared(_Special):
-    fn = "mlf_prior_gamma"
+    fn, base_support = "mlf_prior_gamma", _POSITIVE
 
     def __init__(self, k, name=None):
         Prior.__init__(self, name)
@@ -434,17 +680,17 @@ class ChiSquared(_Special):
 
 
 class InverseGamma(_Special):
-    fn = "mlf_prior_invgamma"
+    fn, rt_attrs, base_support = "mlf_prior_invgamma", ("scale",), _POSITIVE
 
     def __init__(self, shape, scale=1.0, name=None):
         Prior.__init__(self, name)
         self.shape, = _in_range("InverseGamma", SHAPE_MIN, SHAPE_MAX, shape=shape)
-        self.scale, = _positive("InverseGamma", scale=scale)
+        self.scale = self._par("scale", "scale", scale)
         self.consts = _gamma_consts(self.scale, self.shape)
 
 
 class Beta(_Special):
-    fn = "mlf_prior_beta"
+    fn, base_support = "mlf_prior_beta", (0.0, 1.0)
 
     def __init__(self, a, b, name=None):
         Prior.__init__(self, name)
@@ -453,18 +699,20 @@ class Beta(_Special):
 
 
 class StudentT(_Special):
-    fn = "mlf_prior_studentt"
+    fn, rt_attrs = "mlf_prior_studentt", ("loc", "scale")
 
     def __init__(self, nu, loc=0.0, scale=1.0, name=None):
         Prior.__init__(self, name)
         self.nu, = _in_range("StudentT", NU_MIN, NU_MAX, nu=nu)
-        self.loc, = _finite("StudentT", loc=loc)
-        self.scale, = _positive("StudentT", scale=scale)
+        self.loc = self._par("loc", "loc", loc)
+        self.scale = self._par("scale", "scale", scale)
         ha = 0.5 * self.nu
         self.consts = (self.loc, self.scale, ha, _lbeta(ha, 0.5), math.log(ha), math.log(self.nu))
 
 
 class Dirichlet(_Special):
+    base_support = (0.0, 1.0)
+
     def __init__(self, alpha, name=None):
         Prior.__init__(self, name)
         try:
@@ -482,7 +730,7 @@ class Dirichlet(_Special):
         """the block's Gamma(alpha_k, 1) columns: the g row of the module docstring"""
         return [Gamma(a, 1.0) for a in self.alpha]
 
-    def statements(self, first):
+    def statements(self, first, cols=None):
         n = self.size
         out = ["p[%d] = %s;" % (first + k, g.call("u[%d]" % (first + k))) for k, g in enumerate(self.gammas())]
         out += ["{", "  double s = p[%d];" % first]
@@ -493,6 +741,90 @@ class Dirichlet(_Special):
         out += ["    p[%d] = p[%d] / s;" % (first + k, first + k) for k in range(n)]
         out += ["  }", "}"]
         return out
+
+
+class Tabulated(Prior):
+    """A quantile function given as the knots of its CDF: F(x_k) = cdf_k, linear in between (module docstring).  ``table`` is
+    the array the generated source holds, ``[c | x | s]`` with the slopes s computed here in binary64; ``steps`` the trip count
+    of the device's bisection."""
+    tabulated = True
+
+    def __init__(self, x, cdf, name=None):
+        Prior.__init__(self, name)
+        try:
+            x, c = np.array(x, dtype=float), np.array(cdf, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError("Tabulated: x and cdf must be arrays of numbers")
+        if x.ndim != 1 or c.shape != x.shape:
+            raise ValueError("Tabulated: x and cdf must be vectors of one length, got shapes %s and %s" % (x.shape, c.shape))
+        n = len(x)
+        if not 2 <= n <= MAX_KNOTS:
+            raise ValueError("Tabulated: a table has 2 to %d knots, got %d" % (MAX_KNOTS, n))
+        if not (np.isfinite(x).all() and np.isfinite(c).all()):
+            raise ValueError("Tabulated: x and cdf must be finite")
+        if (np.diff(x) < 0).any() or not x[0] < x[-1]:
+            raise ValueError("Tabulated: x must be non-decreasing with x[0] < x[-1]")
+        if (np.diff(c) < 0).any() or c[0] != 0.0 or c[-1] != 1.0:
+            raise ValueError("Tabulated: cdf must be non-decreasing from exactly 0.0 to exactly 1.0")
+        dx, dc = x[1:] - x[:-1], c[1:] - c[:-1]
+        with np.errstate(all="ignore"):
+            s = np.where(dc > 0, dx / np.where(dc > 0, dc, 1.0), 0.0)
+        if not np.isfinite(s).all():
+            raise ValueError("Tabulated: every slope (x[k+1] - x[k]) / (cdf[k+1] - cdf[k]) must be finite")
+        self.x, self.cdf, self.slopes, self.n = x, c, s, n
+        self.steps = (n - 2).bit_length()           # ceil(log2(n - 1))
+        self.table = np.concatenate([c, x, s])
+
+    @classmethod
+    def from_samples(cls, samples, name=None):
+        """equally weighted samples: the sorted samples at cdf_k = k / (m - 1) (the "linear" rule of ``np.quantile``)"""
+        try:
+            x = np.sort(np.array(samples, dtype=float).ravel())
+        except (TypeError, ValueError):
+            raise ValueError("Tabulated.from_samples: samples must be numbers")
+        m = len(x)
+        if m > MAX_KNOTS:
+            raise ValueError("Tabulated.from_samples: %d samples, above the %d knots of a table: pass quantile knots instead, "
+                             "such as Tabulated(np.quantile(samples, q), q) for a grid q from 0 to 1" % (m, MAX_KNOTS))
+        if m < 2:
+            raise ValueError("Tabulated.from_samples: at least 2 samples are needed")
+        return cls(x, np.arange(m) / float(m - 1), name=name)
+
+    @classmethod
+    def from_histogram(cls, edges, density, name=None):
+        """a piecewise-constant density over the bins between `edges`; the CDF is normalised, its ends pinned to 0.0 and 1.0"""
+        try:
+            e, h = np.array(edges, dtype=float), np.array(density, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError("Tabulated.from_histogram: edges and density must be arrays of numbers")
+        if e.ndim != 1 or h.ndim != 1 or len(e) != len(h) + 1 or len(h) < 1:
+            raise ValueError("Tabulated.from_histogram: n bins need n + 1 edges, got shapes %s and %s" % (e.shape, h.shape))
+        if not (np.isfinite(e).all() and np.isfinite(h).all()) or (h < 0).any() or (np.diff(e) <= 0).any():
+            raise ValueError("Tabulated.from_histogram: edges must be finite and ascending, density finite and >= 0")
+        cum = np.concatenate([[0.0], np.cumsum(h * np.diff(e))])
+        if not (np.isfinite(cum[-1]) and cum[-1] > 0):
+            raise ValueError("Tabulated.from_histogram: the density must have a positive, finite integral")
+        c = cum / cum[-1]
+        c[0], c[-1] = 0.0, 1.0
+        return cls(e, c, name=name)
+
+    def support(self, cols=None, supports=None):
+        return (float(self.x[0]), float(self.x[-1]))
+
+    def array_name(self, first):
+        return "mlf_prior_tab%d" % first
+
+    def declaration(self, first):
+        """the table as one array of the generated source"""
+        vals = [_hex(v) for v in self.table]
+        rows = [", ".join(vals[i:i + 6]) for i in range(0, len(vals), 6)]
+        return "static __device__ const double %s[%d] = {\n  %s\n};\n" % (self.array_name(first), len(vals), ",\n  ".join(rows))
+
+    def call(self, u, cols=None):
+        raise NotImplementedError("a Tabulated column is written by statements(): it needs its column for the array's name")
+
+    def statements(self, first, cols=None):
+        return ["p[%d] = mlf_prior_table(u[%d], %s, %d, %d);" % (first, first, self.array_name(first), self.n, self.steps)]
 
 
 def header_text():
@@ -507,12 +839,20 @@ def special_header_text():
         return fh.read()
 
 
+def rt_header_text():
+    """the text of ``csrc/mlf_priors_rt_dev.hpp``"""
+    with open(RT_HEADER) as fh:
+        return fh.read()
+
+
 class PriorTransform(object):
     """The prior transform of a list of priors (module docstring): ``ndim``, ``paramnames``, ``wrapped_dims`` (the circular
     columns, for the transform layer's ``wrapped_dims=``), ``is_affine`` (every prior ``Fixed`` or ``Uniform``: what the
     reference's ``is_affine_transform`` would find, and with it whether a driver needs a t-region), ``source`` (a
     self-contained HIP text defining ``mlf_user_transform``, a deterministic function of the priors' parameter bits),
-    ``model(loglike_source, ...)`` and the vectorized callback ``transform``."""
+    ``order`` (the priors in the order their statements are written: a stable topological sort of the ``Ref``s, ties in list
+    order), ``parents`` (per column, the ascending tuple of columns it reads), ``supports`` (per column, the closed interval that holds
+    it), ``model(loglike_source, ...)`` and the vectorized callback ``transform``."""
 
     def __init__(self, priors):
         self.priors = list(priors)
@@ -524,19 +864,83 @@ class PriorTransform(object):
         self.ndim = sum(p.size for p in self.priors)
         if self.ndim > devicemodel.MAX_DIM:
             raise ValueError("the priors span %d columns, above MLF_MAX_DIM = %d" % (self.ndim, devicemodel.MAX_DIM))
-        self.paramnames, self.wrapped_dims, body = [], [], []
+        self.paramnames, self.wrapped_dims, firsts = [], [], []
         first = 0
         for p in self.priors:
             self.paramnames += p.names(first)
             if p.circular:
                 self.wrapped_dims.append(first)
-            body += p.statements(first)
+            firsts.append(first)
             first += p.size
+        tables = [p for p in self.priors if getattr(p, "tabulated", False)]
+        if sum(p.n for p in tables) > MAX_TABLE_KNOTS:
+            raise ValueError("the tables of one transform hold at most %d knots, got %d" % (MAX_TABLE_KNOTS, sum(p.n for p in tables)))
+        cols = self._resolve(firsts)
+        order = self._sort(firsts, cols)
+        self.order = [self.priors[i] for i in order]
+        self.parents = [()] * self.ndim
+        supports = [None] * self.ndim
+        body = []
+        for i in order:             # dependency order: every parent's support is known and its statement already written
+            p, first = self.priors[i], firsts[i]
+            if p.refs:
+                self.parents[first] = tuple(sorted(set(cols[i].values())))
+                p.check_refs(cols[i], supports, self.paramnames)
+            supports[first:first + p.size] = [p.support(cols[i], supports)] * p.size
+            body += p.statements(first, cols[i])
+        self.supports = supports
         self.is_affine = all(p.affine for p in self.priors)
         special = special_header_text() if any(getattr(p, "special", False) for p in self.priors) else ""
-        self.source = (header_text() + special + "\n__device__ void mlf_user_transform(const double *u, double *p, int d, const double *aux, "
+        rt = ""
+        if tables or any(p.refs for p in self.priors):
+            rt = rt_header_text() + "".join("\n" + p.declaration(firsts[i]) for i, p in enumerate(self.priors) if p in tables)
+        self.source = (header_text() + special + rt + "\n__device__ void mlf_user_transform(const double *u, double *p, int d, const double *aux, "
                        "long long naux) {\n" + "".join("  %s\n" % s for s in body) + "}\n")
         self._model = None
+
+    def _resolve(self, firsts):
+        """per prior, the column behind every Ref parameter: {attribute: column}"""
+        out = []
+        for p, first in zip(self.priors, firsts):
+            mine = {}
+            for attr, (ref, _, label) in p.refs.items():
+                where = "%s (column %d): %s = %r" % (type(p).__name__, first, label, ref)
+                if isinstance(ref.target, str):
+                    hits = [j for j, nm in enumerate(self.paramnames) if nm == ref.target]
+                    if not hits:
+                        raise ValueError("%s names no column; the columns are %s" % (where, ", ".join(self.paramnames)))
+                    if len(hits) > 1:
+                        raise ValueError("%s is ambiguous: columns %s carry that name" % (where, hits))
+                    j = hits[0]
+                else:
+                    j = ref.target
+                    if not 0 <= j < self.ndim:
+                        raise ValueError("%s: there are columns 0 to %d" % (where, self.ndim - 1))
+                if j == first:
+                    raise ValueError("%s refers to its own column" % where)
+                mine[attr] = j
+            out.append(mine)
+        return out
+
+    def _sort(self, firsts, cols):
+        """a stable topological sort of the priors (a block is one unit): of the priors whose parents are all written, the
+        one that comes first in the list is next"""
+        owner = {}
+        for i, p in enumerate(self.priors):
+            for k in range(p.size):
+                owner[firsts[i] + k] = i
+        needs = [set(owner[j] for j in mine.values()) for mine in cols]
+        if not any(needs):
+            return list(range(len(self.priors)))
+        done, order = set(), []
+        while len(order) < len(self.priors):
+            ready = [i for i in range(len(self.priors)) if i not in done and needs[i] <= done]
+            if not ready:
+                left = [self.paramnames[firsts[i]] for i in range(len(self.priors)) if i not in done]
+                raise ValueError("the Refs of the columns %s form a cycle" % ", ".join(left))
+            done.add(ready[0])
+            order.append(ready[0])
+        return order
 
     def model(self, loglike_source, aux=None, **kw):
         """``DeviceModel(ndim, loglike_source, transform_source=self.source, aux=aux, **kw)``: name, nterms, nsums, nderived,
@@ -554,4 +958,4 @@ class PriorTransform(object):
 __all__ = ["Prior", "Fixed", "Uniform", "LogUniform", "Normal", "TruncatedNormal", "LogNormal", "HalfNormal", "Exponential",
            "Rayleigh", "Weibull", "Pareto", "Cauchy", "HalfCauchy", "Laplace", "Logistic", "Gumbel", "Triangular", "Sine",
            "Cosine", "MultivariateNormal", "OrderedUniform", "Gamma", "ChiSquared", "InverseGamma", "Beta", "StudentT",
-           "Dirichlet", "PriorTransform"]
+           "Dirichlet", "Ref", "Tabulated", "PriorTransform"]

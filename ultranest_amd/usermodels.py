@@ -11,6 +11,8 @@
               (``np.cumsum(p, axis=1)[:, -1]``); no log or exp
   gauss_normal_prior  gauss under independent Normal priors from the prior library (``ultranest_amd.priors``), with its
               analytic evidence
+  hierarchical_gauss  mu ~ Normal(0, 1), theta_i ~ Normal(Ref("mu"), 0.5): a prior whose location is another parameter
+              (``priors.Ref``), Gaussian data around the theta_i, with its analytic evidence
 
 Likelihoods summed over data terms (``DeviceModel(..., nterms=K)``: one wave per row, the lanes split the terms), each with a
 default-form twin that computes the same terms in a serial loop k = 0..K-1 inside ``mlf_user_loglike``:
@@ -132,6 +134,43 @@ def gauss_normal_prior(ndim, sigma=0.1, prior_sigma=1.0, prior_mean=0.5):
     model = pt.model(GAUSS_LOGLIKE % float(sigma), aux=centers, name="gauss_normal_prior%d" % ndim)
     var = float(sigma) ** 2 + float(prior_sigma) ** 2
     lnz = float(np.sum(-0.5 * (centers - means) ** 2 / var - 0.5 * np.log(2 * np.pi * var)))
+    return model, lnz
+
+
+HIER_GAUSS_LOGLIKE = r"""
+#define MLF_HIER_SIGMA %r
+__device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux) {
+  const double sigma = MLF_HIER_SIGMA;
+  double s = 0.0;
+  for (int k = 1; k < d && k - 1 < naux; ++k) {
+    const double z = (p[k] - aux[k - 1]) / sigma;
+    s += z * z;
+  }
+  return -0.5 * s - 0.5 * log(2.0 * 3.141592653589793 * sigma * sigma) * (double)(d - 1);
+}
+"""
+
+
+def hierarchical_gauss_data(ngroups):
+    """the fixed group means y_i of `hierarchical_gauss`: within one prior sigma of 0, spread over 0.8"""
+    return 0.3 + 0.8 * np.sin(1.0 + 2.0 * np.arange(ngroups)) / 2.
+
+
+def hierarchical_gauss(ngroups, tau=0.5, sigma=0.3):
+    """A hierarchical model whose prior needs ``priors.Ref``: mu ~ Normal(0, 1), theta_i ~ Normal(Ref("mu"), tau) for
+    i < ngroups, likelihood prod_i N(y_i | theta_i, sigma) with the fixed y of `hierarchical_gauss_data` in aux (columns: mu,
+    theta_0, ...).  Returns ``(model, lnZ)``; marginally y ~ N(0, (tau^2 + sigma^2) I + 1 1^T), so with v = tau^2 + sigma^2 and
+    n = ngroups, ln Z = -0.5 * (y.y / v - (sum y)^2 / (v (v + n))) - 0.5 * (n ln(2 pi) + (n - 1) ln v + ln(v + n))
+    (Sherman-Morrison and the matrix determinant lemma).  With the defaults v = 0.34."""
+    from . import priors
+    if ngroups < 1:
+        raise ValueError("hierarchical_gauss needs at least one group")
+    y = hierarchical_gauss_data(ngroups)
+    pt = priors.PriorTransform([priors.Normal(0.0, 1.0, name="mu")]
+                               + [priors.Normal(priors.Ref("mu"), tau, name="theta%d" % i) for i in range(ngroups)])
+    model = pt.model(HIER_GAUSS_LOGLIKE % float(sigma), aux=y, name="hierarchical_gauss%d" % ngroups)
+    v, n = float(tau) ** 2 + float(sigma) ** 2, ngroups
+    lnz = float(-0.5 * (y.dot(y) / v - y.sum() ** 2 / (v * (v + n))) - 0.5 * (n * np.log(2 * np.pi) + (n - 1) * np.log(v) + np.log(v + n)))
     return model, lnz
 
 
