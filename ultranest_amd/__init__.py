@@ -8,3 +8,4 @@ of ``include/mlfriends_hip.h``; there is no CPU fallback.
 __version__ = "0.1.0"
 
 from . import priors  # noqa: E402,F401  (the prior library of device models: ultranest_amd.priors)
+from . import hotstart  # noqa: E402,F401  (warm start, auxiliary problems on the host and on the device routes)
