@@ -622,11 +622,8 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
  *                          wherever a default model does.
  *   MLF_USERMODEL_SUMS_TREGION  the same, gated: entry mlf_user_rows_sums_tregion, the parameters of
  *                          mlf_user_rows_sum_tregion; runs where MLF_USERMODEL_TREGION runs.
- * A summed code object is loaded with mlf_usermodel_create_sum (variant MLF_USERMODEL_SUM, _SUM_TREGION, _SUMS or
- * _SUMS_TREGION, nterms >= 1; everything else as create_variant, which returns MLF_E_BADARG for these four variants).  The two
- * _SUMS variants are compiled with mlf_usermodel_compile_sums (nsums = M; MLF_E_BADARG for any other variant and for M outside
- * 1 ... MLF_USERMODEL_MAX_SUMS; compile_variant returns MLF_E_BADARG for them); M is part of the program, so create_sum and the
- * launches take no further argument.
+ * Which entries compile and load these variants, and with which counts: the table below.  M is part of a _SUMS program, so
+ * create_sum and the launches take no further argument.
  *
  * Derived parameters (MLF_USERMODEL_DERIVED): output columns computed from a row's parameters (the reference driver's
  * derived_param_names).  The program is compiled with mlf_usermodel_compile_variant(source, ..., has_transform (ignored),
@@ -657,8 +654,7 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
  * d-wide p row, in one launch.  AN OPT-IN ABOUT COST: mlf_user_derived then runs on every member row of the batch, not only on
  * the kept rows.  Entries mlf_user_rows_tregion_derived / mlf_user_rows_sum_tregion_derived / mlf_user_rows_sums_tregion_derived:
  * the parameters of their gated sibling, then (int nq, double *q_scratch).
- *   compile_gate_derived  nsums = M for _SUMS_TREGION_DERIVED, 0 for the other two (else MLF_E_BADARG; compile_variant and
- *                   compile_sums return MLF_E_BADARG for these variants).
+ *   compile_gate_derived  nsums = M for _SUMS_TREGION_DERIVED, 0 for the other two (else MLF_E_BADARG).
  *   create_gate_derived   records nderived (>= 1, d + nderived <= MLF_MAX_DIM, else MLF_E_DIM) and nterms (>= 1 for the summed
  *                   variants, 0 for MLF_USERMODEL_TREGION_DERIVED); MLF_E_BADARG for a code object without the variant's entry.
  *                   Such a handle runs in mlf_region_refill_user_derived_gated ONLY: every other evaluating entry (eval,
@@ -669,7 +665,25 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
  *                   (mlf_region_set_tregion_wide): draws, counts, compaction and offsets are those of the gated
  *                   mlf_region_refill_user, *nevaluated = count(accepted && gate), the rows stay d wide and the derive program
  *                   extends the kept rows.  MLF_E_STATE without a t-region or for a model of another variant; MLF_E_BADARG
- *                   where the t-region's width is not d + nderived or model and derive handle differ in nderived. */
+ *                   where the t-region's width is not d + nderived or model and derive handle differ in nderived.
+ *
+ * THE VARIANTS IN ONE TABLE (the library's own copy is kVariants in csrc/mlf_user.hip; everything above follows from a row): the
+ * only kernel of the variant's program, and the one compile and the one create entry that accept it -- every other compile or
+ * create entry returns MLF_E_BADARG for it, as for a number that is no variant, and mlf_last_error() names the entry that does.
+ * mlf_usermodel_compile / _create are compile_variant / create_variant with MLF_USERMODEL_DEFAULT.
+ *   variant                             kernel                              compiled by           loaded by
+ *   MLF_USERMODEL_DEFAULT               mlf_user_rows                       compile_variant       create_variant
+ *   MLF_USERMODEL_TREGION               mlf_user_rows_tregion               compile_variant       create_variant
+ *   MLF_USERMODEL_SUM                   mlf_user_rows_sum                   compile_variant       create_sum
+ *   MLF_USERMODEL_SUM_TREGION           mlf_user_rows_sum_tregion           compile_variant       create_sum
+ *   MLF_USERMODEL_SUMS                  mlf_user_rows_sums                  compile_sums          create_sum
+ *   MLF_USERMODEL_SUMS_TREGION          mlf_user_rows_sums_tregion          compile_sums          create_sum
+ *   MLF_USERMODEL_DERIVED               mlf_user_derive_rows                compile_variant       create_derived
+ *   MLF_USERMODEL_TREGION_DERIVED       mlf_user_rows_tregion_derived       compile_gate_derived  create_gate_derived
+ *   MLF_USERMODEL_SUM_TREGION_DERIVED   mlf_user_rows_sum_tregion_derived   compile_gate_derived  create_gate_derived
+ *   MLF_USERMODEL_SUMS_TREGION_DERIVED  mlf_user_rows_sums_tregion_derived  compile_gate_derived  create_gate_derived
+ * The counts: nsums is 1 ... MLF_USERMODEL_MAX_SUMS for a _SUMS variant, else 0; nterms >= 1 for a summed variant, else 0;
+ * nderived >= 1 (and d + nderived <= MLF_MAX_DIM) for MLF_USERMODEL_DERIVED and the _TREGION_DERIVED variants. */
 #define MLF_USERMODEL_DEFAULT 0
 #define MLF_USERMODEL_TREGION 1
 #define MLF_USERMODEL_SUM 2

@@ -56,6 +56,10 @@ def _parents_key(source, has_transform, gated=False, summed=False, nsums=None):
     return h.hexdigest()
 
 
+def _derive_key(source):
+    return dm._cache_key(source, dm.Form(False, derived="derive"))
+
+
 def test_existing_cache_keys_are_what_they_were():
     m = usermodels.gauss_derived(5, affine=True)
     keys = set()
@@ -71,9 +75,9 @@ def test_existing_cache_keys_are_what_they_were():
     assert len(keys) == 2 * 2 * 2 * 5
     # the derive program has a key of its own, over the source it is compiled from
     full = m.source + "\n" + usermodels.GAUSS_DERIVED
-    assert dm._derive_cache_key(full) not in keys and dm._derive_cache_key(full) != dm._derive_cache_key(m.source)
-    assert dm._derive_cache_key(full) != _parents_key(full, False)
-    assert dm._code_cache[dm._derive_cache_key(full)] is m.derive_code
+    assert _derive_key(full) not in keys and _derive_key(full) != _derive_key(m.source)
+    assert _derive_key(full) != _parents_key(full, False)
+    assert dm._code_cache[_derive_key(full)] is m.derive_code
     assert dm._code_cache[dm._cache_key(m.source, True)] is m.code
 
 
@@ -307,7 +311,8 @@ def test_model_handle_keys_the_derive_program_separately(monkeypatch):
     made = []
 
     class H(object):
-        def __init__(self, code, ndim, nderived, aux):
+        def __init__(self, code, ndim, has_transform, aux, gated=False, derived=None, nderived=None):
+            assert (has_transform, gated, derived) == (False, False, "derive")
             made.append((code, ndim, nderived))
             self.handle = 100 + len(made)
             self.closed = False
@@ -315,11 +320,11 @@ def test_model_handle_keys_the_derive_program_separately(monkeypatch):
         def close(self):
             self.closed = True
 
-    monkeypatch.setattr(dm, "_DeriveHandle", H)
+    monkeypatch.setattr(dm, "_Handle", H)
     m = usermodels.gauss_derived(5)
     a = m.derive_handle()
     assert m.derive_handle() == a and made == [(m.derive_code, 5, 3)]
-    h = m._handles["derived"]
+    h = m._handles[dm.Form(False, derived="derive")]
     m.close()
     assert h.closed and m._handles == {}
     with pytest.raises(ValueError, match="nderived"):

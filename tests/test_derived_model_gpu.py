@@ -55,9 +55,10 @@ def _rows(n, d, seed=1):
 
 # ---- the kernel against numpy ------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("d,nq", [(2, 1), (5, 3), (50, 3), (124, 3)])
+@pytest.mark.parametrize("d,nq", [(2, 1), (5, 3), (50, 3), (123, 3), (124, 3)])
 def test_derive_equals_numpy_bit_for_bit(d, nq):
-    """(124, 3) is the direct form (one thread per row), the others are staged through LDS; d = 5 and 50 do not divide 64"""
+    """(124, 3) is the direct form (one thread per row), the others are staged through LDS; d = 5 and 50 do not divide 64;
+    (123, 3) is the largest staged shape: 64 * (124 + 4) * 8 = 65536 bytes, exactly the budget"""
     m = _model(d, nq)
     assert (dm._lib.lib().mlf_usermodel_derive_lds_bytes(d, nq) == 0) == (d == 124)
     for n in (0, 1, 63, 64, 65, 130):

@@ -89,6 +89,10 @@ def test_a_source_without_the_derived_function_fails_at_the_first_gated_use():
 
 # ---- cache keys --------------------------------------------------------------------------------------------------------------
 
+def _gate_derived_key(source, has_transform, summed=False, nsums=None):
+    return dm._cache_key(source, dm.Form(has_transform, True, summed, nsums, derived="gate"))
+
+
 def test_existing_cache_keys_are_what_they_were_with_and_without_the_flag():
     keys = set()
     for flag in (False, True):
@@ -103,18 +107,18 @@ def test_existing_cache_keys_are_what_they_were_with_and_without_the_flag():
                         keys.add(dm._cache_key(m.source, tr, gated, True, nsums=nsums))
             full = m.source + "\n" + NONLINEAR_DERIVED
             assert dm._code_cache[dm._cache_key(m.source, True, False, m.summed, nsums=m.nsums)] is m.code
-            assert dm._code_cache[dm._derive_cache_key(full)] is m.derive_code
+            assert dm._code_cache[DC._derive_key(full)] is m.derive_code
     assert len(keys) == 3 * 2 * 2 * 5
     # the new programs have keys of their own, over the source they are compiled from
     new = set()
     for m in (_default(), _summed(), _multisum()):
         full = m.source + "\n" + NONLINEAR_DERIVED
         for tr in (False, True):
-            k = dm._gate_derived_cache_key(full, tr, m.summed, m.nsums)
-            assert k not in keys and k != dm._derive_cache_key(full) and k != DC._parents_key(full, tr, True, m.summed, m.nsums)
-            assert k != dm._gate_derived_cache_key(m.source, tr, m.summed, m.nsums)
+            k = _gate_derived_key(full, tr, m.summed, m.nsums)
+            assert k not in keys and k != DC._derive_key(full) and k != DC._parents_key(full, tr, True, m.summed, m.nsums)
+            assert k != _gate_derived_key(m.source, tr, m.summed, m.nsums)
             new.add(k)
-        assert dm._code_cache[dm._gate_derived_cache_key(full, True, m.summed, m.nsums)] is m.compile_gate_derived(True)
+        assert dm._code_cache[_gate_derived_key(full, True, m.summed, m.nsums)] is m.compile_gate_derived(True)
     assert len(new) == 6
 
 
@@ -155,14 +159,15 @@ def test_handle_arguments(monkeypatch):
     made = []
 
     class H(object):
-        def __init__(self, code, ndim, has_transform, aux, nderived, nterms=None, nsums=None):
+        def __init__(self, code, ndim, has_transform, aux, gated=False, nterms=None, nsums=None, derived=None, nderived=None):
+            assert (gated, derived) == (True, "gate")
             made.append((code, ndim, has_transform, nderived, nterms, nsums))
             self.handle = 200 + len(made)
 
         def close(self):
             pass
 
-    monkeypatch.setattr(dm, "_GateDerivedHandle", H)
+    monkeypatch.setattr(dm, "_Handle", H)
     a = m.handle(True, gated=True, derived=True)
     assert m.handle(True, gated=True, derived=True) == a and made == [(m.compile_gate_derived(True), 5, True, 3, None, None)]
     s = _multisum()

@@ -219,7 +219,7 @@ def test_mismatched_handles_and_widths_are_refused():
     assert dm._lib.lib().mlf_usermodel_eval(gd, dm.ptr(rows), 4, None, dm.ptr(out)) == 4          # MLF_E_STATE: it evaluates nowhere else
     # a code object loaded as the variant it was not compiled as
     with pytest.raises(ValueError, match="no entry of this variant"):
-        dm._GateDerivedHandle(M._compile(True, True), d, True, M.aux, Q)
+        dm._Handle(M._compile(True, True), d, True, M.aux, gated=True, derived="gate", nderived=Q)
     with pytest.raises(ValueError, match="no entry of this variant"):
         dm._Handle(M.compile_gate_derived(True), d, True, M.aux, gated=True)
     # a width below the region's, and everything still works afterwards

@@ -332,29 +332,57 @@ int mlf_region_clear_tregion(mlf_region *r) {
   return 0;
 }
 
-int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
-                           mlf_usermodel *model, double *out_u, double *out_p, double *out_L, size_t capacity,
-                           size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
-  if (!r || !model || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
-    return fail_arg(MLF_E_BADARG, "null pointer");
+// What the three mlf_region_refill_user* entries share.  refill_user_pair: `derive` is a derive handle of the model's dimensionality
+// (and, with nq != 0, of that many derived columns), and model and region agree in dimensionality.
+static int refill_user_pair(const mlf_region *r, const mlf_usermodel *model, const mlf_usermodel *derive, int nq) {
+  if (derive) {
+    if (usermodel_nderived(derive) == 0) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+    if (nq && usermodel_nderived(derive) != nq)
+      return fail_arg(MLF_E_BADARG, "user model and its derive program differ in the number of derived parameters");
+    if (usermodel_dim(derive) != usermodel_dim(model))
+      return fail_arg(MLF_E_BADARG, "user model and its derive program differ in dimensionality");
+  }
   if (r->ready && usermodel_dim(model) != r->d) return fail_arg(MLF_E_BADARG, "user model and region differ in dimensionality");
-  if (r->tr_on && r->tr_w != r->d)   // (the kernel would read the w x w matrix as d x d)
-    return fail_arg(MLF_E_STATE, "the region's t-region spans d + nderived columns: it gates mlf_region_refill_user_derived_gated only");
-  if (r->tr_on != usermodel_gated(model))
-    return fail_arg(MLF_E_STATE, r->tr_on ? "the region has a t-region: the user model must be loaded as MLF_USERMODEL_TREGION"
-                                          : "user model loaded as MLF_USERMODEL_TREGION, but the region has no t-region");
-  // one mlf_user_rows launch for transform + likelihood; rows outside the membership mask are not evaluated (L = -inf: the
-  // threshold cut that follows drops them either way)
+  return 0;
+}
+
+// refill_user: one mlf_user_rows launch for transform + likelihood; rows outside the membership mask are not evaluated (L = -inf:
+// the threshold cut that follows drops them either way).  The gate: none without a t-region on the handle, d wide with nq == 0,
+// else d + nq wide -- the same launch computes q before the gate, and r->rf_q holds the direct form's q rows (the staged form keeps
+// them in LDS).  The rows stay d wide; with `derive`, region_refill widens the kept rows alone.
+static int refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin, mlf_usermodel *model,
+                       mlf_usermodel *derive, int nq, double *out_u, double *out_p, double *out_L, size_t capacity,
+                       size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
   auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
                       const double **prow) -> int {
     double *p = usermodel_has_transform(model) ? pbuf : nullptr;
     if (p) *prow = p;
     if (!r->tr_on) return usermodel_rows(model, rows, n, member, p, Lbuf, s);
-    const TregionGate g = region_tregion(r);
+    TregionGate g = region_tregion(r);
+    if (nq) {
+      CK(r->rf_q.reserve((size_t)n * (size_t)nq * sizeof(double)));
+      g.width = r->tr_w;
+      g.q_scratch = r->rf_q.as<double>();
+    }
     return usermodel_rows(model, rows, n, member, p, Lbuf, s, &g);
   };
   return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
-                       next_offset);
+                       next_offset, derive);
+}
+
+int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
+                           mlf_usermodel *model, double *out_u, double *out_p, double *out_L, size_t capacity,
+                           size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
+  if (!r || !model || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
+    return fail_arg(MLF_E_BADARG, "null pointer");
+  if (int rc = refill_user_pair(r, model, nullptr, 0)) return rc;
+  if (r->tr_on && r->tr_w != r->d)   // (the kernel would read the w x w matrix as d x d)
+    return fail_arg(MLF_E_STATE, "the region's t-region spans d + nderived columns: it gates mlf_region_refill_user_derived_gated only");
+  if (r->tr_on != usermodel_gated(model))
+    return fail_arg(MLF_E_STATE, r->tr_on ? "the region has a t-region: the user model must be loaded as MLF_USERMODEL_TREGION"
+                                          : "user model loaded as MLF_USERMODEL_TREGION, but the region has no t-region");
+  return refill_user(r, method, nsamples, seed, offset, Lmin, model, nullptr, 0, out_u, out_p, out_L, capacity, nevaluated, nkept,
+                     next_offset);
 }
 
 int mlf_region_refill_user_derived(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
@@ -362,23 +390,13 @@ int mlf_region_refill_user_derived(mlf_region *r, int method, size_t nsamples, u
                                    size_t capacity, size_t *nevaluated, size_t *nkept, uint64_t *next_offset) {
   if (!r || !model || !derive || !out_u || !out_p || !out_L || !nevaluated || !nkept || !next_offset)
     return fail_arg(MLF_E_BADARG, "null pointer");
-  if (usermodel_nderived(derive) == 0) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
-  if (usermodel_dim(derive) != usermodel_dim(model))
-    return fail_arg(MLF_E_BADARG, "user model and its derive program differ in dimensionality");
-  if (r->ready && usermodel_dim(model) != r->d) return fail_arg(MLF_E_BADARG, "user model and region differ in dimensionality");
+  if (int rc = refill_user_pair(r, model, derive, 0)) return rc;
   // the reference's t-region spans all nparams columns: its gate would need q before the likelihood (such a batch takes the host
-  // sequence)
+  // sequence, or mlf_region_refill_user_derived_gated)
   if (r->tr_on) return fail_arg(MLF_E_STATE, "derived parameters together with a t-region do not run on the device");
   if (usermodel_gated(model)) return fail_arg(MLF_E_STATE, "user model loaded as MLF_USERMODEL_TREGION, but the region has no t-region");
-  // the evaluation of mlf_region_refill_user without a t-region; region_refill widens the kept rows alone
-  auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
-                      const double **prow) -> int {
-    double *p = usermodel_has_transform(model) ? pbuf : nullptr;
-    if (p) *prow = p;
-    return usermodel_rows(model, rows, n, member, p, Lbuf, s);
-  };
-  return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
-                       next_offset, derive);
+  return refill_user(r, method, nsamples, seed, offset, Lmin, model, derive, 0, out_u, out_p, out_L, capacity, nevaluated, nkept,
+                     next_offset);
 }
 
 int mlf_region_refill_user_derived_gated(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
@@ -389,29 +407,12 @@ int mlf_region_refill_user_derived_gated(mlf_region *r, int method, size_t nsamp
   const int nq = usermodel_gate_nderived(model);
   if (nq == 0)
     return fail_arg(MLF_E_STATE, "the user model is not of a _TREGION_DERIVED variant (mlf_usermodel_create_gate_derived)");
-  if (usermodel_nderived(derive) == 0) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
-  if (usermodel_nderived(derive) != nq)
-    return fail_arg(MLF_E_BADARG, "user model and its derive program differ in the number of derived parameters");
-  if (usermodel_dim(derive) != usermodel_dim(model))
-    return fail_arg(MLF_E_BADARG, "user model and its derive program differ in dimensionality");
-  if (r->ready && usermodel_dim(model) != r->d) return fail_arg(MLF_E_BADARG, "user model and region differ in dimensionality");
+  if (int rc = refill_user_pair(r, model, derive, nq)) return rc;
   if (!r->tr_on) return fail_arg(MLF_E_STATE, "no t-region set: the gated derived refill needs mlf_region_set_tregion_wide");
   if (r->tr_w != r->d + nq)
     return fail_arg(MLF_E_BADARG, "the t-region's width is not d + nderived (mlf_region_set_tregion_wide)");
-  // mlf_region_refill_user's evaluation with the gate over [p | q]: one launch computes p, q, the gate and the likelihood; the rows
-  // stay d wide, and region_refill widens the kept rows alone with the derive program, as without a t-region
-  auto evaluate = [&](const double *rows, const uint8_t *member, long long n, double *pbuf, double *Lbuf, hipStream_t s,
-                      const double **prow) -> int {
-    double *p = usermodel_has_transform(model) ? pbuf : nullptr;
-    if (p) *prow = p;
-    CK(r->rf_q.reserve((size_t)n * (size_t)nq * sizeof(double)));   // the direct form's q rows (the staged form keeps them in LDS)
-    TregionGate g = region_tregion(r);
-    g.width = r->tr_w;
-    g.q_scratch = r->rf_q.as<double>();
-    return usermodel_rows(model, rows, n, member, p, Lbuf, s, &g);
-  };
-  return region_refill(r, method, nsamples, seed, offset, Lmin, evaluate, out_u, out_p, out_L, capacity, nevaluated, nkept,
-                       next_offset, derive);
+  return refill_user(r, method, nsamples, seed, offset, Lmin, model, derive, nq, out_u, out_p, out_L, capacity, nevaluated, nkept,
+                     next_offset);
 }
 
 }  // extern "C"

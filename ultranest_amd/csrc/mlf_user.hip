@@ -23,21 +23,61 @@
 
 using namespace mlf;
 
+namespace {
+
+// THE FORM TABLE: what each MLF_USERMODEL_* variant is, indexed by its number.  Nothing else in the library tells variants apart.
+struct Variant {
+  const char *kernel;   // the only kernel of the variant's program (mlf_user_rows.hpp)
+  bool gated;           // the kernel takes the t-region gate's five parameters behind the others
+  bool summed;          // one wave (= one workgroup) per row instead of one thread, nterms behind the first eight parameters
+  bool multi;           // several sums: their number is a constant of the program (-DMLF_USER_NSUMS)
+  bool derive;          // p (n, d) -> [p | q] (n, d + nderived); such a handle runs in the derive entries only
+  bool gate_derived;    // (gated is set too) the kernel computes nderived columns per member row, gates over d + nderived columns and
+                        // takes (nq, q_scratch) behind the gate's five; such a handle runs in mlf_region_refill_user_derived_gated only
+  const char *compile_entry, *create_entry;   // the exported entries that accept the variant
+  unsigned (*lds_bytes)(int d, int nq, bool p_buffer);   // dynamic LDS of a launch (0: the kernel's direct form)
+};
+
+unsigned lds_rows(int d, int, bool p_buffer) { return mlf_user_rows_lds_bytes(d, p_buffer); }
+unsigned lds_sum(int d, int, bool p_buffer) { return mlf_user_rows_sum_lds_bytes(d, p_buffer); }
+unsigned lds_derive(int d, int nq, bool) { return mlf_user_rows_derive_lds_bytes(d, nq); }
+unsigned lds_gate_derived(int d, int nq, bool p_buffer) { return mlf_user_rows_gate_derived_lds_bytes(d, nq, p_buffer); }
+unsigned lds_sum_gate_derived(int d, int nq, bool p_buffer) { return mlf_user_rows_sum_gate_derived_lds_bytes(d, nq, p_buffer); }
+
+// the exported entries' names: an entry owns the variants whose row names it
+constexpr char COMPILE_VARIANT[] = "mlf_usermodel_compile_variant", COMPILE_SUMS[] = "mlf_usermodel_compile_sums",
+               COMPILE_GATE_DERIVED[] = "mlf_usermodel_compile_gate_derived", CREATE_VARIANT[] = "mlf_usermodel_create_variant",
+               CREATE_SUM[] = "mlf_usermodel_create_sum", CREATE_DERIVED[] = "mlf_usermodel_create_derived",
+               CREATE_GATE_DERIVED[] = "mlf_usermodel_create_gate_derived";
+constexpr Variant kVariants[] = {
+    //                                       gated summed multi derive gate_derived
+    {"mlf_user_rows",                        false, false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows},
+    {"mlf_user_rows_tregion",                true,  false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows},
+    {"mlf_user_rows_sum",                    false, true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum},
+    {"mlf_user_rows_sum_tregion",            true,  true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum},
+    {"mlf_user_rows_sums",                   false, true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum},
+    {"mlf_user_rows_sums_tregion",           true,  true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum},
+    {"mlf_user_derive_rows",                 false, false, false, true,  false, COMPILE_VARIANT, CREATE_DERIVED, lds_derive},
+    {"mlf_user_rows_tregion_derived",        true,  false, false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_gate_derived},
+    {"mlf_user_rows_sum_tregion_derived",    true,  true,  false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived},
+    {"mlf_user_rows_sums_tregion_derived",   true,  true,  true,  false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived},
+};
+static_assert(MLF_USERMODEL_DEFAULT == 0 && MLF_USERMODEL_TREGION == 1 && MLF_USERMODEL_SUM == 2 && MLF_USERMODEL_SUM_TREGION == 3 &&
+                  MLF_USERMODEL_SUMS == 4 && MLF_USERMODEL_SUMS_TREGION == 5 && MLF_USERMODEL_DERIVED == 6 &&
+                  MLF_USERMODEL_TREGION_DERIVED == 7 && MLF_USERMODEL_SUM_TREGION_DERIVED == 8 &&
+                  MLF_USERMODEL_SUMS_TREGION_DERIVED == 9 && sizeof(kVariants) / sizeof(kVariants[0]) == 10,
+              "kVariants is indexed by the MLF_USERMODEL_* numbers");
+
+}  // namespace
+
 struct mlf_usermodel {
   hipModule_t module = nullptr;
   hipFunction_t fn = nullptr;
+  const Variant *v = nullptr;
   int d = 0;
   bool has_transform = false;
-  bool gated = false;   // the MLF_USERMODEL_TREGION / _SUM_TREGION / _SUMS_TREGION variants: the kernel takes the gate's five
-                        // parameters as well
-  bool summed = false;  // the MLF_USERMODEL_SUM / _SUM_TREGION / _SUMS / _SUMS_TREGION variants: one wave per row, nterms behind
-                        // the first eight parameters (the number of sums is baked into a _SUMS program)
-  long long nterms = 0;
-  int nderived = 0;     // the MLF_USERMODEL_DERIVED variant: fn is mlf_user_derive_rows, p (n, d) -> [p | q] (n, d + nderived); such a
-                        // handle runs in the derive entries only
-  int gate_nq = 0;      // the _TREGION_DERIVED variants (gated is set too): the kernel computes this many derived columns per member
-                        // row, gates over d + gate_nq columns and takes (nq, q_scratch) behind the gate's five parameters; such a
-                        // handle runs in mlf_region_refill_user_derived_gated only
+  long long nterms = 0;   // of a summed variant
+  int nderived = 0;       // of the derive variant and the gate_derived ones
   long long naux = 0;
   DevBuf aux;
   DevBuf hu, hp, hL;   // staging of mlf_usermodel_eval (host arrays)
@@ -111,32 +151,30 @@ namespace mlf {
 
 int usermodel_dim(const mlf_usermodel *m) { return m->d; }
 bool usermodel_has_transform(const mlf_usermodel *m) { return m->has_transform; }
-bool usermodel_gated(const mlf_usermodel *m) { return m->gated; }
-int usermodel_nderived(const mlf_usermodel *m) { return m->nderived; }
-int usermodel_gate_nderived(const mlf_usermodel *m) { return m->gate_nq; }
+bool usermodel_gated(const mlf_usermodel *m) { return m->v->gated; }
+int usermodel_nderived(const mlf_usermodel *m) { return m->v->derive ? m->nderived : 0; }
+int usermodel_gate_nderived(const mlf_usermodel *m) { return m->v->gate_derived ? m->nderived : 0; }
 
 int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
                    hipStream_t s, const TregionGate *gate) {
-  if (m->nderived) return fail_arg(MLF_E_STATE, "a derive handle (mlf_usermodel_create_derived) evaluates nothing: it runs in the derive entries only");
+  const Variant &v = *m->v;
+  const int gate_nq = usermodel_gate_nderived(m);
+  if (v.derive) return fail_arg(MLF_E_STATE, "a derive handle (mlf_usermodel_create_derived) evaluates nothing: it runs in the derive entries only");
   // the two variants differ in their parameter lists: never launch one with the other's
-  if (m->gated != (gate != nullptr))
-    return fail_arg(MLF_E_STATE, m->gated ? "user model loaded as the t-region variant: it runs only in a refill with a t-region set"
-                                          : "user model not loaded as the t-region variant (mlf_usermodel_create_variant)");
+  if (v.gated != (gate != nullptr))
+    return fail_arg(MLF_E_STATE, v.gated ? "user model loaded as the t-region variant: it runs only in a refill with a t-region set"
+                                         : "user model not loaded as the t-region variant (mlf_usermodel_create_variant)");
   // a gate over derived columns is w = d + gate_nq wide and brings the q rows' scratch; every other gate is d wide
-  if (m->gate_nq ? (gate->width != m->d + m->gate_nq || gate->q_scratch == nullptr) : (gate != nullptr && gate->width != 0))
-    return fail_arg(MLF_E_STATE, m->gate_nq ? "user model loaded as a _TREGION_DERIVED variant: it runs only in "
-                                              "mlf_region_refill_user_derived_gated, with a t-region over d + nderived columns"
-                                            : "a t-region over d + nderived columns needs a user model loaded as a _TREGION_DERIVED "
-                                              "variant (mlf_usermodel_create_gate_derived)");
+  if (gate_nq ? (gate->width != m->d + gate_nq || gate->q_scratch == nullptr) : (gate != nullptr && gate->width != 0))
+    return fail_arg(MLF_E_STATE, gate_nq ? "user model loaded as a _TREGION_DERIVED variant: it runs only in "
+                                           "mlf_region_refill_user_derived_gated, with a t-region over d + nderived columns"
+                                         : "a t-region over d + nderived columns needs a user model loaded as a _TREGION_DERIVED "
+                                           "variant (mlf_usermodel_create_gate_derived)");
   if (n <= 0) return 0;
   // default form: one thread per row, 64 rows per workgroup; summed form: one wave (= one workgroup) per row
-  const long long blocks = m->summed ? n : (n + 63) / 64;
+  const long long blocks = v.summed ? n : (n + 63) / 64;
   if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
-  const bool p_buffer = p != nullptr && m->has_transform;
-  const unsigned lds = m->gate_nq ? (m->summed ? mlf_user_rows_sum_gate_derived_lds_bytes(m->d, m->gate_nq, p_buffer)
-                                               : mlf_user_rows_gate_derived_lds_bytes(m->d, m->gate_nq, p_buffer))
-                       : m->summed ? mlf_user_rows_sum_lds_bytes(m->d, p_buffer)
-                                   : mlf_user_rows_lds_bytes(m->d, p_buffer);
+  const unsigned lds = v.lds_bytes(m->d, gate_nq, p != nullptr && m->has_transform);
   // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
   const double *a_u = u;
   long long a_n = n;
@@ -154,18 +192,18 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
     g_enlarge = gate->enlarge;
     g_member2 = gate->member2;
   }
-  int g_nq = m->gate_nq;
+  int g_nq = gate_nq;
   double *g_scratch = gate ? gate->q_scratch : nullptr;
   // the first eight, nterms in the ninth place of a summed model, the gate's five behind them when gated, (nq, q_scratch) behind
   // those in a _TREGION_DERIVED variant
   void *args[16] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
   int na = 8;
-  if (m->summed) args[na++] = &a_nterms;
+  if (v.summed) args[na++] = &a_nterms;
   if (gate) {
     void *g[] = {&g_A, &g_ctr, &g_fixed, &g_enlarge, &g_member2};
     for (void *x : g) args[na++] = x;
   }
-  if (m->gate_nq) {
+  if (gate_nq) {
     args[na++] = &g_nq;
     args[na++] = &g_scratch;
   }
@@ -174,11 +212,11 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
 }
 
 int usermodel_derive_rows(const mlf_usermodel *m, const double *p, long long n, double *out, hipStream_t s) {
-  if (!m->nderived) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+  if (!m->v->derive) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
   if (n <= 0) return 0;
   const long long blocks = (n + 63) / 64;   // one thread per row, 64 rows per workgroup
   if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
-  const unsigned lds = mlf_user_rows_derive_lds_bytes(m->d, m->nderived);
+  const unsigned lds = m->v->lds_bytes(m->d, m->nderived, false);
   // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
   const double *a_p = p;
   long long a_n = n;
@@ -195,50 +233,59 @@ int usermodel_derive_rows(const mlf_usermodel *m, const double *p, long long n, 
 
 namespace {
 
-// the gate over derived columns: the gated variants with MLF_USER_GATE_DERIVED=1
-bool variant_gate_derived(int v) {
-  return v == MLF_USERMODEL_TREGION_DERIVED || v == MLF_USERMODEL_SUM_TREGION_DERIVED || v == MLF_USERMODEL_SUMS_TREGION_DERIVED;
-}
-bool variant_gated(int v) {
-  return v == MLF_USERMODEL_TREGION || v == MLF_USERMODEL_SUM_TREGION || v == MLF_USERMODEL_SUMS_TREGION || variant_gate_derived(v);
-}
-bool variant_multi(int v) { return v == MLF_USERMODEL_SUMS || v == MLF_USERMODEL_SUMS_TREGION || v == MLF_USERMODEL_SUMS_TREGION_DERIVED; }
-bool variant_summed(int v) {
-  return v == MLF_USERMODEL_SUM || v == MLF_USERMODEL_SUM_TREGION || v == MLF_USERMODEL_SUM_TREGION_DERIVED || variant_multi(v);
+// the row of `variant` where the exported entry `mine` (one of the names above) owns it; else NULL, and the message names the
+// entry that does
+const Variant *owned(int variant, const char *mine, const char *Variant::*owner) {
+  if (variant < 0 || variant >= (int)(sizeof(kVariants) / sizeof(kVariants[0]))) {
+    fail_arg(MLF_E_BADARG, "unknown user-model variant");
+    return nullptr;
+  }
+  const Variant *v = &kVariants[variant];
+  if (v->*owner == mine) return v;
+  fail_arg(MLF_E_BADARG, (std::string(mine) + ": user-model variant " + std::to_string(variant) + " (entry " + v->kernel +
+                          ") goes through " + v->*owner).c_str());
+  return nullptr;
 }
 
-// the checks every create entry makes before it touches the device
-int check_create_args(const void *code, size_t nbytes, size_t d) {
-  if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
-  if (d > MLF_MAX_DIM) return fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
-  if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return fail_arg(MLF_E_BADARG, "not a code object (ELF)");
+// the counts against the row, each rule once.  A compile entry brings the number of sums (the entries without one: 0), a create
+// entry (nsums NULL) the numbers of terms and of derived columns (the entries without one: 0).
+int check_counts(const Variant &v, const int *nsums, size_t nterms = 0, size_t nderived = 0) {
+  if (nsums) {
+    if (v.multi ? (*nsums < 1 || *nsums > MLF_USERMODEL_MAX_SUMS) : *nsums != 0)
+      return fail_arg(MLF_E_BADARG, "nsums must be 1 to 8 for a variant with several sums (_SUMS), else 0");
+    return 0;
+  }
+  if (v.summed ? (nterms == 0 || nterms > 0x7fffffffffffffffull) : nterms != 0)
+    return fail_arg(MLF_E_BADARG, "nterms: a summed user model has at least one term, every other variant 0");
+  if ((v.derive || v.gate_derived) ? nderived == 0 : nderived != 0)
+    return fail_arg(MLF_E_BADARG, "nderived: a derive program and a gate over derived parameters have at least one derived "
+                                  "parameter, every other variant 0");
   return 0;
 }
 
-// loads the code object as `variant` (arguments checked by the caller); nterms: 0 unless the variant is a summed one; nderived:
-// 0 unless the variant is MLF_USERMODEL_DERIVED (a derive handle) or a _TREGION_DERIVED one (the columns its gate spans)
-int load_model(const void *code, size_t d, int has_transform, int variant, size_t nterms, const double *aux, size_t naux,
-               mlf_usermodel **out, size_t nderived = 0) {
+// the checks every create entry makes before it touches the device
+int check_create_args(const void *code, size_t nbytes, size_t d, size_t nderived) {
+  if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
+  if (d > MLF_MAX_DIM) return fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
+  if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return fail_arg(MLF_E_BADARG, "not a code object (ELF)");
+  if (nderived > MLF_MAX_DIM - d) return fail_arg(MLF_E_DIM, "user model: parameters and derived parameters above MLF_MAX_DIM");
+  return 0;
+}
+
+// loads the code object as the variant `v` (arguments checked by the caller)
+int load_model(const void *code, size_t d, int has_transform, const Variant &v, size_t nterms, size_t nderived, const double *aux,
+               size_t naux, mlf_usermodel **out) {
   if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   mlf_usermodel *m = new mlf_usermodel();
+  m->v = &v;
   m->d = (int)d;
   m->has_transform = has_transform != 0;
-  m->gated = variant_gated(variant);
-  m->summed = variant_summed(variant);
   m->nterms = (long long)nterms;
-  m->nderived = variant == MLF_USERMODEL_DERIVED ? (int)nderived : 0;
-  m->gate_nq = variant_gate_derived(variant) ? (int)nderived : 0;
+  m->nderived = (int)nderived;
   m->naux = (long long)naux;
-  const char *entry = variant == MLF_USERMODEL_DERIVED ? "mlf_user_derive_rows"
-                      : variant == MLF_USERMODEL_TREGION_DERIVED      ? "mlf_user_rows_tregion_derived"
-                      : variant == MLF_USERMODEL_SUM_TREGION_DERIVED  ? "mlf_user_rows_sum_tregion_derived"
-                      : variant == MLF_USERMODEL_SUMS_TREGION_DERIVED ? "mlf_user_rows_sums_tregion_derived"
-                      : variant_multi(variant) ? (m->gated ? "mlf_user_rows_sums_tregion" : "mlf_user_rows_sums")
-                      : m->summed            ? (m->gated ? "mlf_user_rows_sum_tregion" : "mlf_user_rows_sum")
-                                             : (m->gated ? "mlf_user_rows_tregion" : "mlf_user_rows");
   hipError_t e = hipModuleLoadData(&m->module, code);
-  if (e == hipSuccess && hipModuleGetFunction(&m->fn, m->module, entry) != hipSuccess) {
+  if (e == hipSuccess && hipModuleGetFunction(&m->fn, m->module, v.kernel) != hipSuccess) {
     // the variants' entries differ in name: this code object was compiled as the other one (or is no user model at all)
     (void)hipGetLastError();
     (void)hipModuleUnload(m->module);
@@ -258,13 +305,9 @@ int load_model(const void *code, size_t d, int has_transform, int variant, size_
   return 0;
 }
 
-// hiprtc on `source` + the wrapper header as `variant` (checked by the caller); nsums: 0 unless the variant is a _SUMS one
-int compile_program(const char *source, const char *include_dir, int has_transform, int variant, int nsums, void *code_out,
+// hiprtc on `source` + the wrapper header as the variant `v` (nsums checked by the caller: 0 unless v.multi)
+int compile_program(const char *source, const char *include_dir, int has_transform, const Variant &v, int nsums, void *code_out,
                     size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  const bool v_gated = variant_gated(variant);
-  const bool v_summed = variant_summed(variant);
-  const bool v_derived = variant == MLF_USERMODEL_DERIVED;
-  const bool v_gate_derived = variant_gate_derived(variant);
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
@@ -276,14 +319,16 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
   const std::string src = std::string(source) + "\n#include \"mlf_user_rows.hpp\"\n";
   const std::string inc = std::string("-I") + include_dir;
   const std::string sums = "-DMLF_USER_NSUMS=" + std::to_string(nsums);
-  // (a _SUMS variant adds its one option behind the others, and so does the derive program, which never calls the transform:
-  // the other variants' programs are compiled as they were)
+  // every program gets the first eight; a variant's own options follow (so the other variants' programs are compiled as they were
+  // before it existed; the derive program never calls the transform)
   const char *opts[10] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
-                          has_transform && !v_derived ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
-                          v_gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
-                          v_summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0", v_derived ? "-DMLF_USER_DERIVED=1" : sums.c_str()};
-  int nopts = variant_multi(variant) || v_derived ? 9 : 8;
-  if (v_gate_derived) opts[nopts++] = "-DMLF_USER_GATE_DERIVED=1";   // (behind whatever its gated sibling is compiled with)
+                          has_transform && !v.derive ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
+                          v.gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
+                          v.summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0"};
+  int nopts = 8;
+  if (v.multi) opts[nopts++] = sums.c_str();
+  if (v.derive) opts[nopts++] = "-DMLF_USER_DERIVED=1";
+  if (v.gate_derived) opts[nopts++] = "-DMLF_USER_GATE_DERIVED=1";
   hiprtcProgram prog = nullptr;
   hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
   if (res != HIPRTC_SUCCESS) {
@@ -322,6 +367,28 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
   return rc;
 }
 
+// every exported compile entry: the pointers, "is this variant mine", the counts, one compile
+int compile_entry(const char *mine, const char *source, const char *include_dir, int has_transform, int variant, int nsums,
+                  void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
+  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
+  const Variant *v = owned(variant, mine, &Variant::compile_entry);
+  if (!v) return MLF_E_BADARG;
+  if (int rc = check_counts(*v, &nsums)) return rc;
+  return compile_program(source, include_dir, has_transform, *v, nsums, code_out, code_cap, code_size, log, log_cap);
+}
+
+// every exported create entry: the pointers, "is this variant mine", the counts, d and the code object, one load
+int create_entry(const char *mine, const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
+                 size_t nderived, const double *aux, size_t naux, mlf_usermodel **out) {
+  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
+  *out = nullptr;
+  const Variant *v = owned(variant, mine, &Variant::create_entry);
+  if (!v) return MLF_E_BADARG;
+  if (int rc = check_counts(*v, nullptr, nterms, nderived)) return rc;
+  if (int rc = check_create_args(code, nbytes, d, nderived)) return rc;
+  return load_model(code, d, has_transform, *v, nterms, nderived, aux, naux, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -334,36 +401,18 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
 
 int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant, void *code_out,
                                   size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (variant_gate_derived(variant))
-    return fail_arg(MLF_E_BADARG, "a _TREGION_DERIVED variant is compiled with mlf_usermodel_compile_gate_derived");
-  if (variant_multi(variant))
-    return fail_arg(MLF_E_BADARG, "a user-model variant with several sums needs their number: mlf_usermodel_compile_sums");
-  if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION && variant != MLF_USERMODEL_SUM &&
-      variant != MLF_USERMODEL_SUM_TREGION && variant != MLF_USERMODEL_DERIVED)
-    return fail_arg(MLF_E_BADARG, "unknown user-model variant");
-  return compile_program(source, include_dir, has_transform, variant, 0, code_out, code_cap, code_size, log, log_cap);
+  return compile_entry(COMPILE_VARIANT, source, include_dir, has_transform, variant, 0, code_out, code_cap, code_size, log, log_cap);
 }
 
 int mlf_usermodel_compile_sums(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
                                void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (!variant_multi(variant) || variant_gate_derived(variant))
-    return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_sums: the variant must be MLF_USERMODEL_SUMS or MLF_USERMODEL_SUMS_TREGION");
-  if (nsums < 1 || nsums > MLF_USERMODEL_MAX_SUMS)
-    return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_sums: nsums must be 1 to 8");
-  return compile_program(source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log, log_cap);
+  return compile_entry(COMPILE_SUMS, source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log, log_cap);
 }
 
 int mlf_usermodel_compile_gate_derived(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
                                        void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (!variant_gate_derived(variant))
-    return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_gate_derived: the variant must be MLF_USERMODEL_TREGION_DERIVED, "
-                                  "_SUM_TREGION_DERIVED or _SUMS_TREGION_DERIVED");
-  if (variant_multi(variant) ? (nsums < 1 || nsums > MLF_USERMODEL_MAX_SUMS) : nsums != 0)
-    return fail_arg(MLF_E_BADARG, "mlf_usermodel_compile_gate_derived: nsums must be 1 to 8 for _SUMS_TREGION_DERIVED, else 0");
-  return compile_program(source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log, log_cap);
+  return compile_entry(COMPILE_GATE_DERIVED, source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log,
+                       log_cap);
 }
 
 int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_transform, const double *aux, size_t naux,
@@ -373,52 +422,22 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
 
 int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int has_transform, int variant, const double *aux,
                                  size_t naux, mlf_usermodel **out) {
-  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
-  *out = nullptr;
-  if (variant_gate_derived(variant))
-    return fail_arg(MLF_E_BADARG, "a _TREGION_DERIVED variant is loaded with mlf_usermodel_create_gate_derived");
-  if (variant_summed(variant))
-    return fail_arg(MLF_E_BADARG, "a summed user-model variant needs its number of terms: mlf_usermodel_create_sum");
-  if (variant != MLF_USERMODEL_DEFAULT && variant != MLF_USERMODEL_TREGION)
-    return fail_arg(MLF_E_BADARG, "unknown user-model variant");
-  if (int rc = check_create_args(code, nbytes, d)) return rc;
-  return load_model(code, d, has_transform, variant, 0, aux, naux, out);
+  return create_entry(CREATE_VARIANT, code, nbytes, d, has_transform, variant, 0, 0, aux, naux, out);
 }
 
 int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
                              const double *aux, size_t naux, mlf_usermodel **out) {
-  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
-  *out = nullptr;
-  if (!variant_summed(variant) || variant_gate_derived(variant))
-    return fail_arg(MLF_E_BADARG, "mlf_usermodel_create_sum: the variant must be MLF_USERMODEL_SUM, _SUM_TREGION, _SUMS or _SUMS_TREGION");
-  if (nterms == 0 || nterms > 0x7fffffffffffffffull) return fail_arg(MLF_E_BADARG, "a summed user model has at least one term");
-  if (int rc = check_create_args(code, nbytes, d)) return rc;
-  return load_model(code, d, has_transform, variant, nterms, aux, naux, out);
+  return create_entry(CREATE_SUM, code, nbytes, d, has_transform, variant, nterms, 0, aux, naux, out);
 }
 
 int mlf_usermodel_create_derived(const void *code, size_t nbytes, size_t d, size_t nderived, const double *aux, size_t naux,
                                  mlf_usermodel **out) {
-  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
-  *out = nullptr;
-  if (nderived == 0) return fail_arg(MLF_E_BADARG, "a derive program has at least one derived parameter");
-  if (int rc = check_create_args(code, nbytes, d)) return rc;
-  if (nderived > MLF_MAX_DIM - d) return fail_arg(MLF_E_DIM, "user model: parameters and derived parameters above MLF_MAX_DIM");
-  return load_model(code, d, 0, MLF_USERMODEL_DERIVED, 0, aux, naux, out, nderived);
+  return create_entry(CREATE_DERIVED, code, nbytes, d, 0, MLF_USERMODEL_DERIVED, 0, nderived, aux, naux, out);
 }
 
 int mlf_usermodel_create_gate_derived(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
                                       size_t nderived, const double *aux, size_t naux, mlf_usermodel **out) {
-  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
-  *out = nullptr;
-  if (!variant_gate_derived(variant))
-    return fail_arg(MLF_E_BADARG, "mlf_usermodel_create_gate_derived: the variant must be MLF_USERMODEL_TREGION_DERIVED, "
-                                  "_SUM_TREGION_DERIVED or _SUMS_TREGION_DERIVED");
-  if (nderived == 0) return fail_arg(MLF_E_BADARG, "a gate over derived parameters has at least one derived parameter");
-  if (variant_summed(variant) ? (nterms == 0 || nterms > 0x7fffffffffffffffull) : nterms != 0)
-    return fail_arg(MLF_E_BADARG, "nterms: at least one term for a summed variant, 0 for MLF_USERMODEL_TREGION_DERIVED");
-  if (int rc = check_create_args(code, nbytes, d)) return rc;
-  if (nderived > MLF_MAX_DIM - d) return fail_arg(MLF_E_DIM, "user model: parameters and derived parameters above MLF_MAX_DIM");
-  return load_model(code, d, has_transform, variant, nterms, aux, naux, out, nderived);
+  return create_entry(CREATE_GATE_DERIVED, code, nbytes, d, has_transform, variant, nterms, nderived, aux, naux, out);
 }
 
 int mlf_usermodel_gate_derived_lds_bytes(size_t d, size_t nderived, int has_p_buffer) {
@@ -450,7 +469,7 @@ int mlf_usermodel_destroy(mlf_usermodel *m) {
 
 int mlf_usermodel_eval(mlf_usermodel *m, const double *u, size_t n, double *p_out, double *L_out) {
   if (!m || !u || (!p_out && !L_out)) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (m->nderived) return fail_arg(MLF_E_STATE, "a derive handle (mlf_usermodel_create_derived) evaluates nothing");
+  if (m->v->derive) return fail_arg(MLF_E_STATE, "a derive handle (mlf_usermodel_create_derived) evaluates nothing");
   if (n == 0) return 0;
   if (n > 0x7fffffffffffull / (size_t)m->d) return fail_arg(MLF_E_BADARG, "batch too large");
   hipStream_t s = ctx_stream();
@@ -471,7 +490,7 @@ int mlf_usermodel_eval(mlf_usermodel *m, const double *u, size_t n, double *p_ou
 
 int mlf_usermodel_derive(mlf_usermodel *m, const double *p, size_t n, double *out) {
   if (!m) return fail_arg(MLF_E_BADARG, "null model");
-  if (!m->nderived) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+  if (!m->v->derive) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
   if (n == 0) return 0;
   if (!p || !out) return fail_arg(MLF_E_BADARG, "null pointer");
   const size_t w = (size_t)m->d + (size_t)m->nderived;
@@ -490,7 +509,7 @@ int mlf_usermodel_derive(mlf_usermodel *m, const double *p, size_t n, double *ou
 
 int mlf_usermodel_derive_dev(mlf_usermodel *m, const double *d_p, size_t n, double *d_out, void *stream) {
   if (!m) return fail_arg(MLF_E_BADARG, "null model");
-  if (!m->nderived) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
+  if (!m->v->derive) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
   if (n == 0) return 0;
   if (!d_p || !d_out) return fail_arg(MLF_E_BADARG, "null pointer");
   if (int rc = usermodel_derive_rows(m, d_p, (long long)n, d_out, (hipStream_t)stream)) return rc;

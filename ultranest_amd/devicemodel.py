@@ -104,8 +104,8 @@ The routes above evaluate populations of 10^2 to 10^4 rows, which is a few dozen
 and ``L(p) = sum over k in [0, K) of term(k)``.  One wave then owns one row, its 64 lanes split the terms and read ``aux``
 side by side (index ``aux`` by ``k``).  Transform source, ``aux``, the callbacks, ``eval_dev`` and ``device_route`` are
 unchanged, and every route recognises a summed model exactly as it does a default one; its four programs (with or without
-transform, gated or not) are compiled with ``-DMLF_USER_SUM=1`` under their own cache keys and loaded through
-``mlf_usermodel_create_sum``.  The prior transform of a summed model runs on one lane of the row's wave.
+transform, gated or not) are compiled with ``-DMLF_USER_SUM=1`` under their own cache keys ("Forms" below).  The prior transform
+of a summed model runs on one lane of the row's wave.
 
 The order of the sum is part of the interface (``csrc/mlf_user_rows.hpp``; ``-ffp-contract=off`` as above):
 
@@ -139,9 +139,8 @@ defines, INSTEAD of ``mlf_user_loglike_term``::
 ``terms`` writes all M entries ``t[0..M)`` for data index ``k`` (the kernel does not pre-set ``t``: an entry the function
 leaves unwritten is undefined); ``finish`` receives the M sums, the row's ``p`` and the data and returns ``L``.  ``nsums=1`` is
 a function of one sum.  Per-row constants go into term 0 or into ``finish``.  M is a constant of the program (the accumulators
-live in registers); the programs are compiled with ``-DMLF_USER_SUM=1 -DMLF_USER_NSUMS=M`` under their own cache keys (entries
-``mlf_user_rows_sums`` / ``mlf_user_rows_sums_tregion``) and loaded through ``mlf_usermodel_create_sum`` as variants 4 and 5;
-everything else -- transform, ``aux``, callbacks, ``eval_dev``, ``device_route``, every route -- is that of a summed model.
+live in registers); the programs are compiled with ``-DMLF_USER_SUM=1 -DMLF_USER_NSUMS=M`` under their own cache keys ("Forms"
+below); everything else -- transform, ``aux``, callbacks, ``eval_dev``, ``device_route``, every route -- is that of a summed model.
 
 The order contract extends the one above and is part of the interface:
 
@@ -175,9 +174,17 @@ default form reads once per 64 rows).  So: the summed form for what the populati
 the whole-refill samplers, region refills of a few thousand draws, up to about 10^4 rows per call -- and for many terms; the
 default form for batches of 10^5 rows and more, or for a likelihood of a handful of terms.
 
+Forms
+-----
+Which program a handle runs is one ``Form(has_transform, gated, summed, nsums, derived)``: it checks the combination, gives the
+library's variant number (``Form.variant``; the table in ``include/mlfriends_hip.h`` names each variant's kernel and the entries
+that compile and load it) and the option tags of the cache key.  ``_cache_key(source, form)`` is the only key, ``compile_form``
+the only caller of the library's compile entries, ``_Handle`` the only handle class, and a model keeps its handles by ``Form``.
+
 Compiling needs no GPU; code objects are cached per process, keyed by a hash of the source, the options and the
 wrapper header.  Evaluating without a GPU raises ``HipLibraryError`` like every other compute call (no CPU fallback).
 """
+import collections
 import ctypes
 import hashlib
 import os
@@ -213,17 +220,17 @@ class DeviceModelCompileError(RuntimeError):
         RuntimeError.__init__(self, "the device model did not compile:\n" + log)
 
 
-def _check_nsums(nsums, summed):
-    """nsums as an int (None stays None); ValueError naming ``nsums`` otherwise.  No library call."""
-    if nsums is None:
+def _check_count(name, value, what, most=None):
+    """A count as an int (None stays None); ValueError naming the argument otherwise.  No library call."""
+    if value is None:
         return None
-    if isinstance(nsums, bool) or not isinstance(nsums, (int, np.integer)):
-        raise ValueError("nsums must be an integer (the number of sums of the summed form), got %r" % (nsums,))
-    if not 1 <= nsums <= MAX_SUMS:
-        raise ValueError("nsums must be 1 to %d, got %d" % (MAX_SUMS, nsums))
-    if not summed:
-        raise ValueError("nsums needs the summed form: give nterms (the number of data terms) as well")
-    return int(nsums)
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError("%s must be an integer (the number of %s), got %r" % (name, what, value))
+    if most is not None and not 1 <= value <= most:
+        raise ValueError("%s must be 1 to %d, got %d" % (name, most, value))
+    if value < 1:
+        raise ValueError("%s must be at least 1, got %d" % (name, value))
+    return int(value)
 
 
 def _check_nderived(ndim, nderived, derived_source):
@@ -232,79 +239,91 @@ def _check_nderived(ndim, nderived, derived_source):
         if derived_source is not None:
             raise ValueError("derived_source needs nderived (the number of derived parameters it writes)")
         return None
-    if isinstance(nderived, bool) or not isinstance(nderived, (int, np.integer)):
-        raise ValueError("nderived must be an integer (the number of derived parameters), got %r" % (nderived,))
-    if nderived < 1:
-        raise ValueError("nderived must be at least 1, got %d" % nderived)
+    nderived = _check_count("nderived", nderived, "derived parameters")
     if ndim + nderived > MAX_DIM:
         raise ValueError("ndim + nderived must be at most %d (MLF_MAX_DIM), got %d + %d" % (MAX_DIM, ndim, nderived))
     if derived_source is None:
         raise ValueError("nderived needs derived_source (the source that defines mlf_user_derived)")
-    return int(nderived)
+    return nderived
 
 
-def _derive_cache_key(source):
-    """the key of a derive program: that of a program without a transform, with " derived" among its options"""
-    h = hashlib.sha256()
-    with open(HEADER, "rb") as fh:
-        header = fh.read()
-    options = repr((COMPILE_OPTIONS, False)) + " derived"
-    for part in (source.encode(), b"\0", options.encode(), b"\0", header):
-        h.update(part)
-    return h.hexdigest()
+class Form(collections.namedtuple("Form", "has_transform gated summed nsums derived")):
+    """Which program of a model: with its transform or the identity; gated by a t-region; the summed form, with nsums=M several
+    sums; derived="derive" the derive program (none of the others apply), derived="gate" the gate over derived parameters (a gated
+    program).  The one place that maps these to a MLF_USERMODEL_* number and to the option tags of a cache key.  ValueError for a
+    combination that is no program."""
+    __slots__ = ()
+
+    def __new__(cls, has_transform, gated=False, summed=False, nsums=None, derived=None):
+        nsums = _check_count("nsums", nsums, "sums of the summed form", MAX_SUMS)
+        if nsums is not None and not summed:
+            raise ValueError("nsums needs the summed form: give nterms (the number of data terms) as well")
+        if derived == "gate" and not gated:
+            raise ValueError("derived=True names the gate over the derived parameters: it needs gated=True")
+        if derived not in (None, "gate") and (derived != "derive" or has_transform or gated or summed):
+            raise ValueError("derived is None, 'gate' or 'derive' (the derive program: no transform, gate or sum), got %r" % (derived,))
+        return super(Form, cls).__new__(cls, bool(has_transform), bool(gated), bool(summed), nsums, derived)
+
+    @property
+    def variant(self):
+        if self.derived == "derive":
+            return VARIANT_DERIVED
+        kind = 2 if self.nsums is not None else 1 if self.summed else 0      # default, one sum, several sums
+        if self.derived == "gate":
+            return (VARIANT_TREGION_DERIVED, VARIANT_SUM_TREGION_DERIVED, VARIANT_SUMS_TREGION_DERIVED)[kind]
+        return (VARIANT_DEFAULT, VARIANT_SUM, VARIANT_SUMS)[kind] + (VARIANT_TREGION if self.gated else 0)
+
+    @property
+    def tags(self):
+        """what the options part of a cache key says behind ``repr((COMPILE_OPTIONS, has_transform))``"""
+        return ((" tregion" if self.gated else "") + (" gate_derived" if self.derived == "gate" else "") +
+                (" sum" if self.summed else "") + ("" if self.nsums is None else " sums=%d" % self.nsums) +
+                (" derived" if self.derived == "derive" else ""))
 
 
-def _gate_derived_cache_key(source, has_transform, summed=False, nsums=None):
-    """the key of a gate-derived program (`source`: the model's source followed by its derived source): that of its gated
-    sibling over that source, with " gate_derived" among its options"""
+DERIVE = Form(False, derived="derive")
+
+
+def _cache_key(source, form, *flags, **more):
+    """sha256 over the source, the options and the headers the program includes (the gate's only where it is gated).  `form`: a
+    Form, or the arguments of one (``has_transform, gated, summed, nsums``)"""
+    if not isinstance(form, Form):
+        form = Form(form, *flags, **more)
     h = hashlib.sha256()
     header = b""
-    for path in (HEADER, GATE_HEADER):
+    for path in (HEADER, GATE_HEADER) if form.gated else (HEADER,):
         with open(path, "rb") as fh:
             header += fh.read()
-    options = repr((COMPILE_OPTIONS, bool(has_transform))) + " tregion gate_derived"
-    if summed:
-        options += " sum"
-    if nsums is not None:
-        options += " sums=%d" % nsums
+    options = repr((COMPILE_OPTIONS, form.has_transform)) + form.tags
     for part in (source.encode(), b"\0", options.encode(), b"\0", header):
         h.update(part)
     return h.hexdigest()
 
 
-def _cache_key(source, has_transform, gated=False, summed=False, nsums=None):
-    h = hashlib.sha256()
-    with open(HEADER, "rb") as fh:
-        header = fh.read()
-    options = repr((COMPILE_OPTIONS, bool(has_transform)))
-    if gated:
-        options += " tregion"
-        with open(GATE_HEADER, "rb") as fh:
-            header += fh.read()
-    if summed:
-        options += " sum"
-    if nsums is not None:
-        options += " sums=%d" % nsums
-    for part in (source.encode(), b"\0", options.encode(), b"\0", header):
-        h.update(part)
-    return h.hexdigest()
-
-
-def _compile_cached(key, call):
-    """The code object under `key`, from the cache or from ``call(library, buf, cap, size, log)`` (one of the library's compile
-    entries; once more with the reported size where the buffer was too small)."""
+def compile_form(source, form):
+    """The gfx950 code object (bytes) of `source` + the wrapper kernel as `form`, from the cache or from the library's compile
+    entry for ``form.variant`` (once more with the reported size where the buffer was too small); cached per process."""
     global compile_calls
+    key = _cache_key(source, form)
     code = _code_cache.get(key)
     if code is not None:
         return code
     L = _lib.lib()
+    v = form.variant
     size = ctypes.c_size_t(0)
     log = ctypes.create_string_buffer(1 << 16)
     cap = 1 << 20
     for _ in range(2):
         buf = ctypes.create_string_buffer(cap)
+        head = (source.encode(), INCLUDE_DIR.encode(), int(form.has_transform), v)
+        tail = (buf, cap, ctypes.byref(size), log, len(log))
         compile_calls += 1
-        rc = call(L, buf, cap, size, log)
+        if form.derived == "gate":
+            rc = L.mlf_usermodel_compile_gate_derived(*(head + (form.nsums or 0,) + tail))
+        elif form.nsums is not None:
+            rc = L.mlf_usermodel_compile_sums(*(head + (form.nsums,) + tail))
+        else:
+            rc = L.mlf_usermodel_compile_variant(*(head + tail))
         if rc == MLF_E_COMPILE:
             raise DeviceModelCompileError(log.value.decode(errors="replace"))
         if rc != 0 and size.value > cap:      # code object larger than the buffer: once more with its size
@@ -322,50 +341,20 @@ def compile_model(source, has_transform, gated=False, summed=False, nsums=None):
     t-region test between transform and likelihood (module docstring), another program under its own key.  summed: the
     one-wave-per-row form around ``mlf_user_loglike_term`` (module docstring), two more programs under their own keys.
     nsums=M (with summed): M sums and a final function (``mlf_user_loglike_terms`` / ``_finish``), two more programs per M."""
-    nsums = _check_nsums(nsums, summed)
-    if nsums is None:
-        key = _cache_key(source, has_transform, gated, summed)
-        variant = (VARIANT_TREGION if gated else VARIANT_DEFAULT) + (VARIANT_SUM if summed else 0)
-    else:
-        key = _cache_key(source, has_transform, gated, summed, nsums=nsums)
-        variant = VARIANT_SUMS_TREGION if gated else VARIANT_SUMS
-
-    def call(L, buf, cap, size, log):
-        if nsums is not None:
-            return L.mlf_usermodel_compile_sums(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), variant, nsums,
-                                                buf, cap, ctypes.byref(size), log, len(log))
-        if variant != VARIANT_DEFAULT:
-            return L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)),
-                                                   variant, buf, cap, ctypes.byref(size), log, len(log))
-        return L.mlf_usermodel_compile(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), buf, cap,
-                                       ctypes.byref(size), log, len(log))
-
-    return _compile_cached(key, call)
+    return compile_form(source, Form(has_transform, gated, summed, nsums))
 
 
 def compile_derived(source):
     """The gfx950 code object of the derive program of `source` (a model's source followed by its derived source): the
     wrapper compiled with ``-DMLF_USER_DERIVED=1``, ``mlf_user_derive_rows`` its only kernel; cached per process."""
-    def call(L, buf, cap, size, log):
-        return L.mlf_usermodel_compile_variant(source.encode(), INCLUDE_DIR.encode(), 0, VARIANT_DERIVED, buf, cap,
-                                               ctypes.byref(size), log, len(log))
-
-    return _compile_cached(_derive_cache_key(source), call)
+    return compile_form(source, DERIVE)
 
 
 def compile_gate_derived(source, has_transform, summed=False, nsums=None):
     """The gfx950 code object of the gate-derived program of `source` (a model's source followed by its derived source): the
     gated wrapper compiled with ``-DMLF_USER_GATE_DERIVED=1`` as well, whose only kernel computes the derived columns of every
     member row and gates over ``[p | q]`` (module docstring); cached per process under its own key."""
-    nsums = _check_nsums(nsums, summed)
-    variant = (VARIANT_SUMS_TREGION_DERIVED if nsums is not None else
-               VARIANT_SUM_TREGION_DERIVED if summed else VARIANT_TREGION_DERIVED)
-
-    def call(L, buf, cap, size, log):
-        return L.mlf_usermodel_compile_gate_derived(source.encode(), INCLUDE_DIR.encode(), int(bool(has_transform)), variant,
-                                                    nsums or 0, buf, cap, ctypes.byref(size), log, len(log))
-
-    return _compile_cached(_gate_derived_cache_key(source, has_transform, summed, nsums), call)
+    return compile_form(source, Form(has_transform, True, summed, nsums, "gate"))
 
 
 class UserModelSpec(object):
@@ -390,25 +379,27 @@ class _Callback(object):
 
 
 class _Handle(object):
-    """One loaded model (``mlf_usermodel``) on the library's device."""
+    """One loaded program (``mlf_usermodel``) on the library's device, created through the entry that owns its form's variant.
+    nterms: the summed form; derived, nderived: one of the two derived kinds (``Form``)."""
 
-    def __init__(self, code, ndim, has_transform, aux, gated=False, nterms=None, nsums=None):
-        h = ctypes.c_void_p()
-        if nterms is not None:
-            if nsums is not None:        # (the number of sums is baked into the program: the variant alone names its entry)
-                variant = VARIANT_SUMS_TREGION if gated else VARIANT_SUMS
-            else:
-                variant = VARIANT_SUM_TREGION if gated else VARIANT_SUM
-            check(_lib.lib().mlf_usermodel_create_sum(code, len(code), int(ndim), int(bool(has_transform)), variant,
-                                                      int(nterms), ptr(aux), len(aux), ctypes.byref(h)))
-        elif gated:
-            check(_lib.lib().mlf_usermodel_create_variant(code, len(code), int(ndim), int(bool(has_transform)),
-                                                          VARIANT_TREGION, ptr(aux), len(aux), ctypes.byref(h)))
+    def __init__(self, code, ndim, has_transform, aux, gated=False, nterms=None, nsums=None, derived=None, nderived=None):
+        form = Form(has_transform, gated, nterms is not None, nsums, derived)
+        L, h = _lib.lib(), ctypes.c_void_p()
+        head = (code, len(code), int(ndim))
+        tail = (ptr(aux), len(aux), ctypes.byref(h))
+        if form == DERIVE:
+            rc = L.mlf_usermodel_create_derived(*(head + (int(nderived),) + tail))
         else:
-            check(_lib.lib().mlf_usermodel_create(code, len(code), int(ndim), int(bool(has_transform)), ptr(aux), len(aux),
-                                                  ctypes.byref(h)))
+            head += (int(form.has_transform), form.variant)
+            if form.derived == "gate":
+                rc = L.mlf_usermodel_create_gate_derived(*(head + (int(nterms or 0), int(nderived)) + tail))
+            elif form.summed:
+                rc = L.mlf_usermodel_create_sum(*(head + (int(nterms),) + tail))
+            else:
+                rc = L.mlf_usermodel_create_variant(*(head + tail))
+        check(rc)
         self._h = h
-        self.has_transform = bool(has_transform)
+        self.has_transform = form.has_transform
 
     @property
     def handle(self):
@@ -424,30 +415,6 @@ class _Handle(object):
             self.close()
         except Exception:
             pass
-
-
-class _DeriveHandle(_Handle):
-    """The loaded derive program of a model (``mlf_usermodel_create_derived``)."""
-
-    def __init__(self, code, ndim, nderived, aux):
-        h = ctypes.c_void_p()
-        check(_lib.lib().mlf_usermodel_create_derived(code, len(code), int(ndim), int(nderived), ptr(aux), len(aux),
-                                                      ctypes.byref(h)))
-        self._h = h
-        self.has_transform = False
-
-
-class _GateDerivedHandle(_Handle):
-    """The loaded gate-derived program of a model (``mlf_usermodel_create_gate_derived``)."""
-
-    def __init__(self, code, ndim, has_transform, aux, nderived, nterms=None, nsums=None):
-        h = ctypes.c_void_p()
-        variant = (VARIANT_SUMS_TREGION_DERIVED if nsums is not None else
-                   VARIANT_SUM_TREGION_DERIVED if nterms is not None else VARIANT_TREGION_DERIVED)
-        check(_lib.lib().mlf_usermodel_create_gate_derived(code, len(code), int(ndim), int(bool(has_transform)), variant,
-                                                           int(nterms or 0), int(nderived), ptr(aux), len(aux), ctypes.byref(h)))
-        self._h = h
-        self.has_transform = bool(has_transform)
 
 
 class DeviceModel(object):
@@ -472,19 +439,14 @@ class DeviceModel(object):
             raise ValueError("gate_derived needs nderived and derived_source: it gates the t-region over the derived parameters")
         self.gate_derived = bool(gate_derived)
         self.nparams = self.ndim + (self.nderived or 0)
-        if nterms is not None:
-            if isinstance(nterms, bool) or not isinstance(nterms, (int, np.integer)):
-                raise ValueError("nterms must be an integer (the number of terms of the summed form), got %r" % (nterms,))
-            if nterms < 1:
-                raise ValueError("nterms must be at least 1, got %d" % nterms)
-            nterms = int(nterms)
-        self.nterms = nterms
-        self.nsums = _check_nsums(nsums, nterms is not None)
+        self.nterms = _check_count("nterms", nterms, "terms of the summed form")
+        self.nsums = Form(False, summed=self.summed, nsums=nsums).nsums
         self.has_transform = transform_source is not None
         self.source = loglike_source if transform_source is None else loglike_source + "\n" + transform_source
         self.aux = np.empty(0) if aux is None else f64(np.ravel(aux)).copy()
         DeviceModel._count += 1
         self.name = name or "DeviceModel%d" % DeviceModel._count
+        self._forms = {}
         self.code = self._compile(self.has_transform, False)
         # the derive program: the model's source (helpers included) followed by the derived source; the main programs above
         # are compiled from self.source alone, as those of the model without nderived
@@ -498,17 +460,24 @@ class DeviceModel(object):
     def summed(self):
         return self.nterms is not None
 
-    def _compile(self, tr, gated):
-        if self.nsums is not None:
-            return compile_model(self.source, tr, gated=gated, summed=True, nsums=self.nsums)
-        return compile_model(self.source, tr, gated=gated, summed=self.summed)
+    def _form(self, tr, gated, derived=None):
+        """(remembered: every route asks for its handle once per device call)"""
+        key = (tr, gated, derived)
+        if key not in self._forms:
+            self._forms[key] = DERIVE if derived == "derive" else Form(tr, gated, self.summed, self.nsums, derived)
+        return self._forms[key]
+
+    def _compile(self, tr, gated, derived=None):
+        """the code object of one of the model's programs: the derived kinds over the source followed by the derived source"""
+        if derived is None:
+            return compile_form(self.source, self._form(tr, gated))
+        if self.nderived is None:
+            raise ValueError("%s has no derived parameters (nderived)" % self.name)
+        return compile_form(self.source + "\n" + self.derived_source, self._form(tr, gated, derived))
 
     def compile_gate_derived(self, with_transform=True):
         """The code object of the model's gate-derived program (needs no GPU; cached per process)."""
-        if self.nderived is None:
-            raise ValueError("%s has no derived parameters (nderived)" % self.name)
-        return compile_gate_derived(self.source + "\n" + self.derived_source, bool(with_transform and self.has_transform),
-                                    summed=self.summed, nsums=self.nsums)
+        return self._compile(bool(with_transform and self.has_transform), True, "gate")
 
     def handle(self, with_transform=True, gated=False, derived=False):
         """The loaded model (created on first use: needs the GPU).  with_transform=False: the variant whose prior
@@ -517,41 +486,23 @@ class DeviceModel(object):
         model (``nterms``) loads its own programs under its own keys, and so does one of several sums (``nsums``).
         gated=True, derived=True: the gate over ``[p | q]`` (a model with ``nderived``; compiled and loaded on first such use; it
         runs in ``mlf_region_refill_user_derived_gated`` only)."""
-        tr = bool(with_transform and self.has_transform)
-        if derived:
-            if not gated:
-                raise ValueError("derived=True names the gate over the derived parameters: it needs gated=True")
-            key = (tr, "gate_derived")
-            h = self._handles.get(key)
-            if h is None:
-                h = self._handles[key] = _GateDerivedHandle(self.compile_gate_derived(tr), self.ndim, tr, self.aux, self.nderived,
-                                                            nterms=self.nterms, nsums=self.nsums)
-            return h.handle
-        key = (tr, True) if gated else tr
-        if self.summed:
-            key = (tr, bool(gated), "sum" if self.nsums is None else "sums")
-        h = self._handles.get(key)
-        if h is None:
-            if gated:
-                code = self._compile(tr, True)
-            else:
-                code = self.code if tr == self.has_transform else self._compile(tr, False)
-            if self.nsums is not None:
-                h = _Handle(code, self.ndim, tr, self.aux, gated=gated, nterms=self.nterms, nsums=self.nsums)
-            elif self.summed:
-                h = _Handle(code, self.ndim, tr, self.aux, gated=gated, nterms=self.nterms)
-            else:
-                h = _Handle(code, self.ndim, tr, self.aux, gated=gated)
-            self._handles[key] = h
-        return h.handle
+        return self._load(bool(with_transform and self.has_transform), bool(gated), "gate" if derived else None)
 
     def derive_handle(self):
         """The loaded derive program (created on first use: needs the GPU); cached with the model's other handles."""
-        if self.nderived is None:
-            raise ValueError("%s has no derived parameters (nderived)" % self.name)
-        h = self._handles.get("derived")
+        return self._load(False, False, "derive")
+
+    def _load(self, tr, gated, derived):
+        """the handle of one program, keyed by its Form; compiled unless it is one of the constructor's two programs"""
+        form = self._form(tr, gated, derived)
+        h = self._handles.get(form)
         if h is None:
-            h = self._handles["derived"] = _DeriveHandle(self.derive_code, self.ndim, self.nderived, self.aux)
+            code = {self._form(self.has_transform, False): self.code, DERIVE: self.derive_code}.get(form)
+            # (a count that is not the form's stays out of the call)
+            counts = dict(nterms=self.nterms if form.summed else None, nsums=form.nsums, derived=form.derived,
+                          nderived=self.nderived if form.derived else None)
+            h = self._handles[form] = _Handle(code or self._compile(tr, gated, derived), self.ndim, tr, self.aux, gated=gated,
+                                              **{k: v for k, v in counts.items() if v is not None})
         return h.handle
 
     def close(self):
