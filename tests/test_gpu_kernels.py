@@ -2,6 +2,8 @@
   (a) the golden vectors produced by the real reference (tests/golden/*.npz), and
   (b) the CPU oracle on seeded inputs at sizes it finishes in seconds.
 Bit-exact for indices, counts, masks, radii; stated tolerances elsewhere.  Run with `-m gpu`."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -617,6 +619,122 @@ def test_prep64_proposals_on_the_ellipsoid_boundary_and_wrapped_axes(d, K, oracl
     want = oracle.inside_ellipsoid(pts2, ctr, inv, 3.0) & (oracle.find_nearby(tl_w, oracle.affine_transform(wrapped(pts2), ctr, T), r2) >= 0)
     assert np.array_equal(reg.inside(pts2), want)
     reg.close()
+
+
+_BOUNDARY_ENLARGE = 1.7
+_BOUNDARY_R2 = 16.0      # whitened, the ellipsoid q <= 1.7 is the ball |t|^2 <= 1.7: every proposal in it has a live point within 4
+
+
+@functools.lru_cache(maxsize=None)
+def _boundary_inputs(d, p):
+    """300 live points, p proposals, every second one scaled onto q = enlarge within +-3e-16 relative (the construction of
+    test_prep64_proposals_on_the_ellipsoid_boundary_and_wrapped_axes); checked from numpy, before any device call: enough of
+    them lie inside the band 2^-34 |A|_F |delta|^2, where the reference tier decides"""
+    rs = np.random.RandomState(9700 + d)
+    n = 300
+    u = 0.5 + 0.05 * rs.normal(size=(n, d))
+    ctr = u.mean(axis=0)
+    cov = np.cov(u, rowvar=0) * (d + 2) + 1e-6 * np.eye(d)
+    ev, evec = np.linalg.eigh(cov)
+    T = evec * ev ** -0.5
+    inv = np.linalg.inv(cov)
+    dl = rs.normal(size=(p, d)) * 0.05
+    q = np.einsum('ij,jk,ik->i', dl, inv, dl)
+    scale = np.sqrt(_BOUNDARY_ENLARGE / q)
+    scale[1::2] *= 1.0 + rs.uniform(-3e-16, 3e-16, size=len(scale[1::2]))
+    pts = ctr + dl * np.where(np.arange(p) % 4 < 2, scale, 1.0)[:, None]
+    dl = pts - ctr
+    q = np.einsum('ij,jk,ik->i', dl, inv, dl)
+    in_band = np.abs(q - _BOUNDARY_ENLARGE) <= 2.0 ** -34 * np.sqrt((inv ** 2).sum()) * (dl ** 2).sum(axis=1)
+    # 500 as long as the batch has them: of the 200 proposals of the single-launch path 100 are placed on the boundary
+    assert in_band.sum() >= min(500, p // 2), (d, p, int(in_band.sum()))
+    shift = np.full(d, np.nan)
+    shift[[0, 3, d - 1]] = [0.3, 0.9, 0.55]
+    return u, ctr, T, inv, pts, shift
+
+
+# route -> (d, proposals, options, what debug_stats must show, matrix-kernel launches of the batch).  The launches are counted
+# by the handle's launch timing (time_filter_launches): one per sweep of a range, one for k_uncertain, two above 128 dimensions
+# (quantiser and sweep), none for k_inside_mid (its stage stamps appear instead) and none where the pre-filter is not taken.
+# The library reports no more than that about a batch's path: the vector and the binary64 stage (k_prep, k_prep3, k_prep_wide)
+# and the single launch are told apart by the options and the batch length alone.
+_BOUNDARY_ROUTES = {
+    # binary64 per-proposal stage
+    "k_prep3 d=17": (17, 2000, {"prep_bounded": 0}, None, 0),
+    "k_prep3 d=50": (50, 2000, {"prep_bounded": 0}, None, 0),
+    # consumers of the band list of the bounded stage (the pre-filter on for this live set; no one-launch path)
+    "ell_exact_wave in k_sweep": (50, 2000, {"filter_min_queries": 1, "mid_max_queries": 0}, "list", 1),
+    "ell_exact_wave in k_uncertain": (50, 2000, {"filter_min_queries": 1, "mid_max_queries": 0, "filter_phase_min_queries": 1,
+                                                 "filter_phases": 2}, "list, min-only ranges", 3),
+    "ell_exact_wave in k_recheck_whiten": (50, 2000, {"filter_min_queries": 1, "mid_max_queries": 0, "filter_phase_min_queries": 1,
+                                                      "filter_phases": 2, "sweep_min": 0}, "list", 2),
+    "k_ell_exact": (50, 2000, {}, "list, no scan", 0),
+    # one launch
+    "k_inside_mid": (50, 1500, {"filter_min_queries": 1}, "stamps", 0),
+    # vector stage
+    "k_prep d=17": (17, 2000, {"fused_prep": 0}, None, 0),
+    "k_prep d=64": (64, 2000, {"fused_prep": 0}, None, 0),
+    # above 128 dimensions
+    "k_prep_mfma64_wide": (130, 2000, {}, None, 2),
+    "k_prep_wide": (130, 2000, {"fused_prep": 0}, None, 2),
+    # single launch, host input
+    "k_inside_small": (17, 200, {}, None, 0),
+}
+
+
+@pytest.mark.parametrize("route", sorted(_BOUNDARY_ROUTES))
+def test_proposals_on_the_ellipsoid_boundary_on_every_route(route, K, oracle):
+    """every route that reaches the shared reference arithmetic (mlf_refarith_dev.hpp) with proposals ON the ellipsoid, where the
+    band hands them to the einsum-order evaluation, and then a layer with three wrapped axes; every mask must be the oracle's.
+    The options are set on this handle only and steer the batch to the route named."""
+    d, p, opts, check, launches = _BOUNDARY_ROUTES[route]
+    check = check or ""
+    opts = dict(opts, time_filter_launches=1)
+    u, ctr, T, inv, pts, shift = _boundary_inputs(d, p)
+    enlarge = _BOUNDARY_ENLARGE
+    emask_o = oracle.inside_ellipsoid(pts, ctr, inv, enlarge)
+    assert 0.2 < emask_o.mean() < 0.9
+    tl = oracle.affine_transform(u, ctr, T)
+    # the radius is huge for this geometry (and still in the range the pre-filter takes): the mask IS the ellipsoid test
+    assert np.array_equal(oracle.region_inside(pts, tl, ctr, T, ctr, inv, enlarge, _BOUNDARY_R2), emask_o)
+
+    def wrapped(x):      # the wrap of circular axes (mlfriends.pyx:529-536)
+        w = np.array(x, dtype=float)
+        for k_, sh in enumerate(shift):
+            if sh == sh:
+                w[:, k_] = np.fmod(w[:, k_] + sh, 1.0)
+        return w
+    tl_w = oracle.affine_transform(wrapped(u), ctr, T)
+    dd = ((tl_w[:100, None, :] - tl_w[None, :100, :]) ** 2).sum(axis=2)
+    np.fill_diagonal(dd, np.inf)
+    r2 = float(np.quantile(dd.min(axis=1), 0.8))
+    pts2 = inputs.proposal_mix(9800 + d, u, p, shell_q=2.0)
+    want2 = oracle.inside_ellipsoid(pts2, ctr, inv, 3.0) & oracle.region_inside(wrapped(pts2), tl_w, ctr, T, ctr, inv, 1e300, r2)
+    assert 0.02 < want2.mean() < 0.98
+    reg = K.DeviceRegion()
+    try:
+        if "no scan" in check:      # an ellipsoid alone: the band list is decided by k_ell_exact
+            reg.set(None, 0, None, None, None, ctr, inv, enlarge, 1e300, use_scan=False)
+        else:
+            reg.set(tl, 0, ctr, T, None, ctr, inv, enlarge, _BOUNDARY_R2)
+        for k_, v_ in opts.items():
+            reg.set_option(k_, v_)
+        assert np.array_equal(reg.inside(pts), emask_o)
+        # the path the batch took, as far as the library reports it
+        assert reg.timing_filter_launches()[0] == launches
+        stats = reg.debug_stats()
+        if "list" in check:      # the bounded stage listed the boundary proposals and the list was consumed
+            assert stats["ellipsoid_band"] >= 500
+        assert (stats["range_cuts"][0] > 0) == ("min-only ranges" in check)
+        if check == "stamps":      # k_inside_mid leaves its stage stamps
+            assert "stamp7" in stats
+        if "no scan" not in check:
+            reg.set(tl_w, 0, ctr, T, shift, ctr, inv, 3.0, r2)
+            assert np.array_equal(reg.inside(pts2), want2)
+    finally:
+        for k_ in opts:
+            reg.set_option(k_)
+        reg.close()
 
 
 def test_wide_reference_classes_at_d_200(K, oracle):

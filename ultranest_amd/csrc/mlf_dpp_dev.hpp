@@ -63,6 +63,13 @@ __device__ __forceinline__ int half_min32(int x) {
   return (int)lo < (int)hi ? (int)lo : (int)hi;
 }
 
+// sum over lanes l, l^16, l^32, l^48: the four lanes that share a proposal in the 16x16x4 binary64 matrix-core layout
+__device__ __forceinline__ double quad_sum(double v) {
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+
 __device__ __forceinline__ void dpp_settle(double &x) { asm volatile("s_nop 1" : "+v"(x)); }
 
 template <int K, int N, class F>

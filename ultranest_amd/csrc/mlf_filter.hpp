@@ -114,10 +114,7 @@ struct MidArgs {
   Prep4Consts c;
   const double *stats;    // [0] sigma, [1] namax, [8 + c] centre of the whitened live points
   double r2;
-  // exact ellipsoid test of the band proposals
-  const double *ell_ctr, *ell_L, *ell_A;
-  double ell_eps_scale, enlarge;
-  int chol_ok;
+  EllExactArgs ell;       // exact ellipsoid test of the band proposals (ell_exact_decide: operands only, no list)
   // sweep + re-check
   const void *refF;
   int ntiles32;

@@ -125,12 +125,9 @@ int region_inside_mid(mlf_region *r, const BatchPlan &p, const double *d_pts, lo
   ma.c.enl_hi = f32_up(r->enlarge);
   ma.stats = f.stats.as<double>();
   ma.r2 = r->r2;
-  ma.ell_ctr = r->ell_ctr.as<double>();
-  ma.ell_L = r->ell_L.as<double>();
-  ma.ell_A = r->ell_A.as<double>();
-  ma.ell_eps_scale = r->ell_eps_scale;
-  ma.enlarge = r->enlarge;
-  ma.chol_ok = r->chol_ok ? 1 : 0;
+  ma.ell = region_ell_args(r, d_pts, np, nullptr, nullptr);
+  ma.ell.count = ma.ell.done = ma.ell.last = nullptr;   // the band proposals are decided on the spot: no list
+  ma.ell.list = nullptr;
   ma.refF = p.ordered ? f.refFm.p : f.refF.p;
   ma.ntiles32 = f.ntiles32;
   ma.refR = p.ordered ? f.refRm.as<double>() : r->refR.as<double>();

@@ -218,40 +218,6 @@ typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned gu32;
 #define MLF_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-// one band proposal decided in binary64 by the whole wave (ell_exact_wave's arithmetic for one proposal)
-__device__ __forceinline__ bool ell_exact_one(const MidArgs &a, long long p, double *dls, int lane) {
-  const int d = a.d;
-  const bool own = lane < d;
-  const double *row = a.pts + p * (long long)d;
-  const double dl = own ? row[lane] - a.ell_ctr[lane] : 0.0;
-  __builtin_amdgcn_wave_barrier();
-  dls[lane] = dl;
-  __builtin_amdgcn_wave_barrier();
-  const double *lcol = a.ell_L + (own ? lane : 0);
-  double y = 0.0;
-#pragma unroll 10
-  for (int j = 0; j < d; ++j) y = __builtin_fma(lcol[(size_t)j * a.dp], dls[j], y);
-  if (!own) y = 0.0;
-  double qt = y * y, nrm2 = dl * dl;
-  for (int o = 32; o > 0; o >>= 1) {
-    qt += __shfl_xor(qt, o, 64);
-    nrm2 += __shfl_xor(nrm2, o, 64);
-  }
-  const double eps = a.ell_eps_scale * nrm2;
-  if (a.chol_ok && qt + eps < a.enlarge) return true;
-  if (a.chol_ok && qt - eps > a.enlarge) return false;
-  double acc = 0.0;
-  if (lane == 0) {   // the reference's own order: one accumulator, j outer, (d_j A_jk) d_k, no FMA (mlfriends.pyx:882-912)
-    for (int j = 0; j < d; ++j) {
-      const double dj = row[j] - a.ell_ctr[j];
-      const double *arow = a.ell_A + (size_t)j * a.dp;
-      for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * (row[k] - a.ell_ctr[k]);
-    }
-  }
-  acc = __shfl(acc, 0, 64);
-  return acc <= a.enlarge;
-}
-
 }  // namespace
 
 template <int DP>
@@ -497,7 +463,7 @@ __global__ __launch_bounds__(512, 1) void k_inside_mid(MidArgs a) {
       while (bm != 0ull) {   // wave-uniform, rare
         const int l = __builtin_ctzll(bm);
         bm &= bm - 1ull;
-        const bool in = ell_exact_one(a, grp * 32 + l, xs, lane);   // the rows of the group are no longer needed
+        const bool in = ell_exact_decide(a.ell, grp * 32 + l, ell_exact_centre(a.ell, lane), xs, lane);   // the rows of the group are no longer needed
         if (lane == l || lane == l + 32) gate = in;
       }
     }

@@ -6,6 +6,7 @@
 #include <math.h>
 
 #include "mlf_dpp_dev.hpp"
+#include "mlf_refarith_dev.hpp"
 
 namespace mlf {
 
@@ -378,7 +379,7 @@ __global__ void k_scaling_transform(const double *pts, long long np, int d, cons
   double w = pts[e];
   if (wrap_shift) {
     const double sh = wrap_shift[k];
-    if (sh == sh) w = fmod(w + sh, 1.0);
+    if (sh == sh) w = mlf_wrap_unit(w, sh);
   }
   out[p * ldt + k] = (w - mean[k]) / std[k];
 }

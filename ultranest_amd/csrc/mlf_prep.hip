@@ -12,6 +12,7 @@
 // defined, this is what OpenBLAS produced for most probed shapes; tolerance class).
 #include "mlf_common.hpp"
 #include "mlf_dpp_dev.hpp"
+#include "mlf_refarith_dev.hpp"
 
 namespace mlf {
 
@@ -32,17 +33,9 @@ __global__ __launch_bounds__(256) void k_prep(PrepArgs a) {
 #pragma unroll
     for (int k = 0; k < DP; ++k) dl[k] = (k < d) ? row[k] - a.ell_ctr[k] : 0.0;
     __syncthreads();
-    double acc = 0.0;
-    for (int j = 0; j < d; ++j) {
-      const double dj = row[j] - a.ell_ctr[j];  // same subtraction as dl[j], bit-identical
-      const double2 *arow = reinterpret_cast<const double2 *>(mat + j * DP);
-#pragma unroll
-      for (int k = 0; k < DP; k += 2) {
-        const double2 v = arow[k >> 1];
-        acc += (dj * v.x) * dl[k];
-        acc += (dj * v.y) * dl[k + 1];
-      }
-    }
+    // (delta_j: the same subtraction as dl[j], bit-identical)
+    const double acc = mlf_tregion_q<DP>(
+        d, [&](int j) { return row[j] - a.ell_ctr[j]; }, [&](int k) { return dl[k]; }, [&](int j, int k) { return mat[j * DP + k]; });
     inside = live && (acc <= a.enlarge);
     if (live) {
       a.mask[p] = inside ? 1 : 0;
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(256) void k_prep(PrepArgs a) {
           w = row[k];
           if (a.wrap_shift) {
             const double sh = a.wrap_shift[k];
-            if (sh == sh) w = fmod(w + sh, 1.0);  // NaN marks an unwrapped dimension
+            if (sh == sh) w = mlf_wrap_unit(w, sh);  // NaN marks an unwrapped dimension
           }
           w -= a.lay_ctr[k];
         }
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(256) void k_boot_quadmax(QuadMaxArgs a) {
       dl[k] = (k < d) ? v : 0.0;
     }
     double acc = 0.0;
-    for (int j = 0; j < d; ++j) {
+    for (int j = 0; j < d; ++j) {   // this kernel's main loop: it restates mlf_tregion_q<DP> (mlf_tregion_dev.hpp)
       const double dj = row[j] - ctr[j];
       const double2 *arow = reinterpret_cast<const double2 *>(mat + j * DP);
 #pragma unroll
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(256) void k_whiten_rows(const double *__restrict__ 
       double w = 0.0;
       if (k < d) {
         w = pts[row * d + k];
-        if (sh == sh) w = fmod(w + sh, 1.0);   // NaN marks an unwrapped dimension
+        if (sh == sh) w = mlf_wrap_unit(w, sh);   // NaN marks an unwrapped dimension
         w -= ctr;
       }
       x[i][ch] = w;

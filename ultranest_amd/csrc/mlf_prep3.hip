@@ -27,21 +27,15 @@
 
 #include <vector>
 
+#include "mlf_dpp_dev.hpp"
 #include "mlf_filter_dev.hpp"
+#include "mlf_refarith_dev.hpp"
 
 namespace mlf {
 
 typedef double double4v __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ __attribute__((noinline)) double wrap_coordinate3(double w, double shift) { return fmod(w + shift, 1.0); }
-
-__device__ __forceinline__ double quad_sum(double v) {   // sum over lanes l, l^16, l^32, l^48
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
 
 // instantiated k-step counts are 1,2,3,4,5,6,8,10,13,16: an instance NK serves 4 prev(NK) < d <= 4 NK
 constexpr int prev_ksteps(int nk) { return nk == 16 ? 13 : nk == 13 ? 10 : nk == 10 ? 8 : nk == 8 ? 6 : nk - 1; }
@@ -174,10 +168,7 @@ __global__ __launch_bounds__(256, 2) void k_prep3(Prep3Args a) {
           double w = x;
           if (WRAP && ok && a.do_tr) {
             const double sh = c_wrap[k];
-            if (sh == sh) {   // NaN marks an unwrapped dimension
-              const double xs = w + sh;
-              w = (xs >= 0.0 && xs < 2.0) ? (xs >= 1.0 ? xs - 1.0 : xs) : wrap_coordinate3(w, sh);
-            }
+            if (sh == sh) w = mlf_wrap_unit_fast(w, sh);   // NaN marks an unwrapped dimension
           }
           dl[ks] = ok ? x - c_ell[k] : 0.0;
           dw[ks] = (ok && a.do_tr) ? w - c_lay[k] : 0.0;
@@ -207,22 +198,15 @@ __global__ __launch_bounds__(256, 2) void k_prep3(Prep3Args a) {
           for (int r = 0; r < 4; ++r) qt = __builtin_fma(y[ct][r], y[ct][r], qt);
         qt = quad_sum(qt);
       }
-      const double eps = a.ell_eps_scale * nrm2;
-      const bool sure_in = a.chol_ok && (qt + eps < a.enlarge);
-      const bool sure_out = a.chol_ok && (qt - eps > a.enlarge);
-      bool inside = sure_in;
-      const bool need_exact = live && !sure_in && !sure_out;   // also every NaN
+      const int band = mlf_ell_band(qt, nrm2, a.ell_eps_scale, a.enlarge, a.chol_ok);
+      bool inside = band == 1;
+      // band == 0 (also every NaN), written as the two tests it replaces: as `band == 0` it costs NK = 13 and 16 ten to
+      // fourteen registers (profiles/refarith_checks.md)
+      const bool need_exact = live && band != 1 && band >= 0;
       if (__any(need_exact)) {
-        // the reference's arithmetic: one accumulator, j outer, (d_j*A_jk)*d_k; done by the
-        // proposal's first lane and shared with the other three
+        // the reference's arithmetic, by the proposal's first lane and shared with the other three
         double acc = 0.0;
-        if (need_exact && kq == 0) {
-          for (int j = 0; j < d; ++j) {
-            const double dj = row[j] - a.ell_ctr[j];
-            const double *arow = a.ell_A + (size_t)j * a.lda;
-            for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * (row[k] - a.ell_ctr[k]);
-          }
-        }
+        if (need_exact && kq == 0) acc = mlf_ell_q_row(row, a.ell_ctr, d, a.ell_A, a.lda);
         acc = __shfl(acc, pl, 64);
         if (need_exact) inside = acc <= a.enlarge;
       }

@@ -552,7 +552,7 @@ hipError_t launch_prep4(const Prep4Args &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- exact ellipsoid test ----------
-// (body: mlf_ell_exact.hpp -- it also runs as the tail of the second-stage scan launch)
+// (body: mlf_ell_exact.hpp)
 __global__ __launch_bounds__(256) void k_ell_exact(EllExactArgs a) {
   extern __shared__ __attribute__((aligned(16))) double ltl[];
   ell_exact_body(a, ltl, blockIdx.x, gridDim.x);

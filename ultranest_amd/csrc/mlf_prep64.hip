@@ -20,21 +20,32 @@
 
 #include <atomic>
 
+#include "mlf_dpp_dev.hpp"
+#include "mlf_refarith_dev.hpp"
+
 namespace mlf {
 
 typedef double double4m __attribute__((ext_vector_type(4)));
 
 namespace {
 
-__device__ __attribute__((noinline)) double wrap_coordinate64(double w, double shift) { return fmod(w + shift, 1.0); }
-
-__device__ __forceinline__ double quad_sum64(double v) {   // sum over lanes l, l^16, l^32, l^48
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
 constexpr int kP64Waves = 4;
+
+// the decision of proposal p behind qt = |L^T delta|^2 and nrm2 = |delta|^2 (the same in its four lanes): the band, and inside it
+// the reference's arithmetic on the row as handed over, by the proposal's first lane (kq == 0; q: its lane).  (The row's
+// address is formed inside the cold branch: handed over as a pointer it cost the k_prep_mfma64 instances two registers, profiles/refarith_checks.md.)
+__device__ __forceinline__ bool ell_decide64(const Prep64Args &a, long long p, double qt, double nrm2, bool live, int q, int kq) {
+  const int band = mlf_ell_band(qt, nrm2, a.ell_eps_scale, a.enlarge, a.chol_ok);
+  bool inside = band > 0;
+  const bool need_exact = live && band == 0;   // also every NaN
+  if (__any(need_exact)) {
+    double acc = 0.0;
+    if (need_exact && kq == 0) acc = mlf_ell_q_row(a.pts + p * (long long)a.d, a.ell_ctr, a.d, a.ell_A, a.lda);
+    acc = __shfl(acc, q, 64);
+    if (need_exact) inside = acc <= a.enlarge;
+  }
+  return inside && live;
+}
 
 // NK = k-steps of 4 coordinates (4 NK >= dp), NC = output tiles of 16
 template <int NK>
@@ -103,29 +114,10 @@ __global__ __launch_bounds__(64 * kP64Waves, 2) void k_prep_mfma64(Prep64Args a)
       for (int ct = 0; ct < NC; ++ct)
 #pragma unroll
         for (int r = 0; r < 4; ++r) qt = __builtin_fma(y[ct][r], y[ct][r], qt);
-      qt = quad_sum64(qt);
-      nrm2 = quad_sum64(nrm2);
+      qt = quad_sum(qt);
+      nrm2 = quad_sum(nrm2);
     }
-    const double eps = a.ell_eps_scale * nrm2;
-    const bool sure_in = a.chol_ok && (qt + eps < a.enlarge);
-    const bool sure_out = a.chol_ok && (qt - eps > a.enlarge);
-    bool inside = sure_in;
-    const bool need_exact = live && !sure_in && !sure_out;   // also every NaN
-    if (__any(need_exact)) {
-      // the reference's arithmetic: one accumulator, j outer, (d_j A_jk) d_k, no fma; by the proposal's first lane
-      double acc = 0.0;
-      if (need_exact && kq == 0) {
-        const double *grow = a.pts + p * (long long)d;
-        for (int j = 0; j < d; ++j) {
-          const double dj = grow[j] - a.ell_ctr[j];
-          const double *arow = a.ell_A + (size_t)j * a.lda;
-          for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * (grow[k] - a.ell_ctr[k]);
-        }
-      }
-      acc = __shfl(acc, q, 64);
-      if (need_exact) inside = acc <= a.enlarge;
-    }
-    inside = inside && live;
+    const bool inside = ell_decide64(a, p, qt, nrm2, live, q, kq);
     if (live && kq == 0) a.gate[p] = inside ? 1 : 0;
     if (!a.do_tr || !__any(inside)) continue;
     // ---- T1: t = delta_w T on the matrix cores, k ascending, one fma per term
@@ -140,10 +132,7 @@ __global__ __launch_bounds__(64 * kP64Waves, 2) void k_prep_mfma64(Prep64Args a)
         double w = row[k];
         if (a.wrap_shift) {
           const double sh = a.wrap_shift[k];
-          if (sh == sh) {   // NaN marks an unwrapped dimension
-            const double xs = w + sh;
-            w = (xs >= 0.0 && xs < 2.0) ? (xs >= 1.0 ? xs - 1.0 : xs) : wrap_coordinate64(w, sh);
-          }
+          if (sh == sh) w = mlf_wrap_unit_fast(w, sh);   // NaN marks an unwrapped dimension
         }
         dw = w - a.lay_ctr[k];
       }
@@ -227,27 +216,9 @@ __global__ __launch_bounds__(64 * kP64Waves) void k_prep_mfma64_wide(Prep64Args 
 #pragma unroll
         for (int r = 0; r < 4; ++r) qt = __builtin_fma(y[ct][r], y[ct][r], qt);
     }
-    qt = quad_sum64(qt);
-    nrm2 = quad_sum64(nrm2);
-    const double eps = a.ell_eps_scale * nrm2;
-    const bool sure_in = a.chol_ok && (qt + eps < a.enlarge);
-    const bool sure_out = a.chol_ok && (qt - eps > a.enlarge);
-    bool inside = sure_in;
-    const bool need_exact = live && !sure_in && !sure_out;   // also every NaN
-    if (__any(need_exact)) {
-      // the reference's arithmetic: one accumulator, j outer, (d_j A_jk) d_k, no fma; by the proposal's first lane
-      double acc = 0.0;
-      if (need_exact && kq == 0) {
-        for (int j = 0; j < d; ++j) {
-          const double dj = row[j] - a.ell_ctr[j];
-          const double *arow = a.ell_A + (size_t)j * a.lda;
-          for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * (row[k] - a.ell_ctr[k]);
-        }
-      }
-      acc = __shfl(acc, q, 64);
-      if (need_exact) inside = acc <= a.enlarge;
-    }
-    inside = inside && live;
+    qt = quad_sum(qt);
+    nrm2 = quad_sum(nrm2);
+    const bool inside = ell_decide64(a, live ? p : 0, qt, nrm2, live, q, kq);   // the row index as `row` was formed from it
     if (live && kq == 0) a.gate[p] = inside ? 1 : 0;
     if (!a.do_tr || !__any(inside)) continue;
     // ---- T1: t = delta_w T, k ascending, one fma per term
@@ -263,10 +234,7 @@ __global__ __launch_bounds__(64 * kP64Waves) void k_prep_mfma64_wide(Prep64Args 
           double w = row[k];
           if (a.wrap_shift) {
             const double sh = a.wrap_shift[k];
-            if (sh == sh) {   // NaN marks an unwrapped dimension
-              const double xs = w + sh;
-              w = (xs >= 0.0 && xs < 2.0) ? (xs >= 1.0 ? xs - 1.0 : xs) : wrap_coordinate64(w, sh);
-            }
+            if (sh == sh) w = mlf_wrap_unit_fast(w, sh);   // NaN marks an unwrapped dimension
           }
           dw = w - a.lay_ctr[k];
         }

@@ -5,67 +5,75 @@
 // between sweep and re-check, and the band proposals ride in the first sweep launch).
 #pragma once
 #include "mlf_prep4.hpp"
+#include "mlf_refarith_dev.hpp"
 
 namespace mlf {
 
 constexpr unsigned kEllWaves = 512;
 
-// the ellipsoid band, one wave per proposal, as light as the re-check waves it shares a launch with: row k of L^T
-// is read through the vector L1 (20 KB, resident), delta sits in 64 doubles of LDS
+// The second tier of the exact ellipsoid test, wave-wide: qt = |L^T delta|^2 and nrm2 = |delta|^2 (the same in every lane)
+// against the band; inside the band -- practically never -- lane 0 evaluates the reference's quadratic form for all
+__device__ __forceinline__ bool ell_exact_settle(const EllExactArgs &a, const double *row, double qt, double nrm2, int lane) {
+  const int band = mlf_ell_band(qt, nrm2, a.eps_scale, a.enlarge, a.chol_ok);
+  if (band != 0) return band > 0;
+  double acc = 0.0;
+  if (lane == 0) acc = mlf_ell_q_row(row, a.ell_ctr, a.d, a.ell_A, a.dp);
+  return __shfl(acc, 0, 64) <= a.enlarge;
+}
+
+// One proposal decided by one wave, as light as the re-check waves it shares a launch with: column `lane` of the lower
+// factor is read through the vector L1 (20 KB, resident; L[j][lane], coalesced over the lanes), delta sits in the wave's 64
+// doubles of LDS (dls).  myctr: coordinate `lane` of the ellipsoid's centre (ell_exact_centre) -- the caller's to fetch, so
+// that a loop over proposals fetches it once (the stores of the loop keep the compiler from hoisting it itself)
+__device__ __forceinline__ double ell_exact_centre(const EllExactArgs &a, int lane) { return lane < a.d ? a.ell_ctr[lane] : 0.0; }
+__device__ __forceinline__ bool ell_exact_decide(const EllExactArgs &a, long long p, double myctr, double *dls, int lane) {
+  const int d = a.d;
+  const bool own = lane < d;
+  const double *row = a.pts + p * (long long)d;
+  const double *lcol = a.ell_L + (own ? lane : 0);
+  const double dl = own ? row[lane] - myctr : 0.0;
+  __builtin_amdgcn_wave_barrier();
+  dls[lane] = dl;
+  __builtin_amdgcn_wave_barrier();
+  double y = 0.0;
+#pragma unroll 10
+  for (int j = 0; j < d; ++j) y = __builtin_fma(lcol[(size_t)j * a.dp], dls[j], y);   // (L^T delta)_lane; L is stored with its zeros
+  if (!own) y = 0.0;
+  double qt = y * y, nrm2 = dl * dl;
+  for (int o = 32; o > 0; o >>= 1) {
+    qt += __shfl_xor(qt, o, 64);
+    nrm2 += __shfl_xor(nrm2, o, 64);
+  }
+  return ell_exact_settle(a, row, qt, nrm2, lane);
+}
+
+// a listed proposal that turned out to lie outside (one lane)
+__device__ __forceinline__ void ell_exact_reject(const EllExactArgs &a, long long p) {
+  a.gate[p] = 0;
+  if (a.route) a.route[p] = 0;
+}
+
+// One thread of each of the `nunits` units (waves or workgroups) that share a band list calls this when its unit is done:
+// the last one resets the list counters for the next batch (every unit has read the count by then)
+__device__ __forceinline__ void ell_list_finish(const EllExactArgs &a, unsigned nunits) {
+  const unsigned t = atomicAdd(a.done, 1u);
+  if (t == nunits - 1u) {
+    if (a.last) *a.last = *a.count;   // kept for mlf_region_debug_stats
+    *a.count = 0u;
+    *a.done = 0u;
+  }
+}
+
+// the ellipsoid band list, one wave per proposal
 __device__ __forceinline__ void ell_exact_wave(const EllExactArgs &a, double *dls, unsigned wave, unsigned nwaves) {
   const unsigned count = *a.count < a.cap ? *a.count : a.cap;
   const int lane = threadIdx.x & 63;
-  const int d = a.d;
-  const bool own = lane < d;
-  const double *lcol = a.ell_L + (own ? lane : 0);   // column `lane` of the lower factor: L[j][lane], coalesced over the lanes
-  const double myctr = own ? a.ell_ctr[lane] : 0.0;
+  const double myctr = ell_exact_centre(a, lane);
   for (unsigned e = wave; e < count; e += nwaves) {
     const long long p = a.list[e];
-    const double *row = a.pts + p * (long long)d;
-    const double dl = own ? row[lane] - myctr : 0.0;
-    __builtin_amdgcn_wave_barrier();
-    dls[lane] = dl;
-    __builtin_amdgcn_wave_barrier();
-    double y = 0.0;
-#pragma unroll 10
-    for (int j = 0; j < d; ++j) y = __builtin_fma(lcol[(size_t)j * a.dp], dls[j], y);   // (L^T delta)_lane; L is stored with its zeros
-    if (!own) y = 0.0;
-    double qt = y * y, nrm2 = dl * dl;
-    for (int o = 32; o > 0; o >>= 1) {
-      qt += __shfl_xor(qt, o, 64);
-      nrm2 += __shfl_xor(nrm2, o, 64);
-    }
-    const double eps = a.eps_scale * nrm2;
-    bool inside;
-    if (a.chol_ok && qt + eps < a.enlarge) {
-      inside = true;
-    } else if (a.chol_ok && qt - eps > a.enlarge) {
-      inside = false;
-    } else {
-      double acc = 0.0;
-      if (lane == 0) {
-        for (int j = 0; j < d; ++j) {
-          const double dj = row[j] - a.ell_ctr[j];
-          const double *arow = a.ell_A + (size_t)j * a.dp;
-          for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * (row[k] - a.ell_ctr[k]);
-        }
-      }
-      acc = __shfl(acc, 0, 64);
-      inside = acc <= a.enlarge;
-    }
-    if (!inside && lane == 0) {
-      a.gate[p] = 0;
-      if (a.route) a.route[p] = 0;
-    }
+    if (!ell_exact_decide(a, p, myctr, dls, lane) && lane == 0) ell_exact_reject(a, p);
   }
-  if (lane == 0) {
-    const unsigned t = atomicAdd(a.done, 1u);
-    if (t == nwaves - 1u) {
-      if (a.last) *a.last = *a.count;   // kept for mlf_region_debug_stats
-      *a.count = 0u;
-      *a.done = 0u;
-    }
-  }
+  if (lane == 0) ell_list_finish(a, nwaves);
 }
 
 constexpr int kTQ = 8;     // whitened queries held in LDS per round

@@ -103,7 +103,8 @@ __device__ __forceinline__ void rows_times_matrix(double *zs, int zs_stride, con
         double v = acc[kk] + shift[k];
         if (wrap_shift) {
           const double sh = wrap_shift[k];
-          if (sh == sh) v = fmod(v + (1.0 - sh), 1.0);   // cut = 1 - shift
+          // the INVERSE of mlf_wrap_unit (mlf_refarith_dev.hpp): back from the layer's wrapped axis, cut = 1 - shift rounded first
+          if (sh == sh) v = fmod(v + (1.0 - sh), 1.0);
         }
         zs[r * d + k] = v;
         out_of_cube = out_of_cube || !((v > 0.0) && (v < 1.0));
@@ -332,7 +333,7 @@ __global__ void k_untransform_rows(const double *t, long long n, int d, const do
     double v = acc + ctr[c];
     if (wrap_shift) {
       const double sh = wrap_shift[c];
-      if (sh == sh) v = fmod(v + (1.0 - sh), 1.0);   // cut = 1 - shift
+      if (sh == sh) v = fmod(v + (1.0 - sh), 1.0);   // the inverse wrap, as above: cut = 1 - shift, not mlf_wrap_unit
     }
     w[p * d + c] = v;
     ok = ok && (v > 0.0) && (v < 1.0);

@@ -20,6 +20,8 @@
 
 #include <math.h>
 
+#include "mlf_refarith_dev.hpp"
+
 namespace mlf {
 
 // Completion protocol.  The caller spins on a host-visible flag instead of waiting for the kernel's completion signal
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(256) void k_inside_small(SmallArgs a) {
       double w = x;
       if (a.wrap) {
         const double sh = a.wrap[tid];
-        if (sh == sh) w = fmod(w + sh, 1.0);
+        if (sh == sh) w = mlf_wrap_unit(w, sh);
       }
       dw[tid] = w - a.lay_ctr[tid];
     }
@@ -134,26 +136,12 @@ __global__ __launch_bounds__(256) void k_inside_small(SmallArgs a) {
     }
   }
   __syncthreads();
-  bool decided = false, inside = false;
-  if (a.chol_ok) {
-    qt = red[0][0] + red[0][1];
-    n2 = red[1][0] + red[1][1];
-    const double eps = a.eps_scale * n2;
-    if (qt + eps < a.enlarge) {
-      decided = true;
-      inside = true;
-    } else if (qt - eps > a.enlarge) {
-      decided = true;
-    }
-  }
-  if (!decided) {   // workgroup-uniform: inside the band (or no factorisation): the reference's own order
+  const int band = mlf_ell_band(red[0][0] + red[0][1], red[1][0] + red[1][1], a.eps_scale, a.enlarge, a.chol_ok);
+  bool inside = band > 0;
+  if (band == 0) {   // workgroup-uniform: inside the band (or no factorisation): the reference's own order
     if (tid == 0) {
-      double acc = 0.0;
-      for (int j = 0; j < d; ++j) {
-        const double dj = dl[j];
-        const double *arow = a.ell_A + (size_t)j * a.dp;
-        for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * dl[k];
-      }
+      const auto delta = [&](int k) { return dl[k]; };
+      const double acc = mlf_tregion_q<0>(d, delta, delta, [&](int j, int k) { return a.ell_A[(size_t)j * a.dp + k]; });
       gate_s = acc <= a.enlarge ? 1 : 0;
     }
     __syncthreads();

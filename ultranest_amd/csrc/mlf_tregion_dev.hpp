@@ -15,6 +15,9 @@
 
 // q of one row.  delta_j(j), any j < d: p_j - c_j.  delta_k(k): the same values for the inner index -- k < KN where KN > 0
 // (a compile-time bound >= d: the row sits in registers, zero beyond d, and mat(j, k) is zero padded), else k < d.
+// KN = mlf_tregion_plain: k < d one term at a time -- the cold branch of a kernel that has no registers to spare for the
+// operands fetched ahead.
+constexpr int mlf_tregion_plain = -1;
 template <int KN, class DeltaJ, class DeltaK, class Mat>
 __device__ __forceinline__ double mlf_tregion_q(int d, DeltaJ delta_j, DeltaK delta_k, Mat mat) {
   double acc = 0.0;
@@ -27,15 +30,17 @@ __device__ __forceinline__ double mlf_tregion_q(int d, DeltaJ delta_j, DeltaK de
       // operands of 8 terms fetched ahead of their use (adjacent wave-uniform loads merge into wide scalar loads and their
       // latency is paid once per group); the terms enter the accumulator one by one, k ascending, as above
       int k = 0;
-      for (; k + 8 <= d; k += 8) {
-        double a[8], dk[8];
+      if constexpr (KN == 0) {
+        for (; k + 8 <= d; k += 8) {
+          double a[8], dk[8];
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          a[t] = mat(j, k + t);
-          dk[t] = delta_k(k + t);
+          for (int t = 0; t < 8; ++t) {
+            a[t] = mat(j, k + t);
+            dk[t] = delta_k(k + t);
+          }
+#pragma unroll
+          for (int t = 0; t < 8; ++t) acc += (dj * a[t]) * dk[t];
         }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc += (dj * a[t]) * dk[t];
       }
       for (; k < d; ++k) acc += (dj * mat(j, k)) * delta_k(k);
     }

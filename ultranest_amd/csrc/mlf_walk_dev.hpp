@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "mlf_philox_dev.hpp"
+#include "mlf_refarith_dev.hpp"
 #include "mlf_walk.hpp"
 
 namespace mlf {
@@ -19,14 +20,14 @@ __device__ __forceinline__ bool inside_open_unit(double x) { return 0.0 < x && x
 __device__ __forceinline__ void whiten_point(const WalkLayer &ly, const double *x, int d, int c, double &out) {
   if (ly.kind == 1) {
     double v = x[c];
-    if (ly.wrap && !isnan(ly.wrap[c])) v = fmod(v + ly.wrap[c], 1.0);
+    if (ly.wrap && !isnan(ly.wrap[c])) v = mlf_wrap_unit(v, ly.wrap[c]);
     out = (v - ly.ctr[c]) / ly.mat[c];
     return;
   }
   double acc = 0.0;
   for (int k = 0; k < d; ++k) {
     double v = x[k];
-    if (ly.wrap && !isnan(ly.wrap[k])) v = fmod(v + ly.wrap[k], 1.0);
+    if (ly.wrap && !isnan(ly.wrap[k])) v = mlf_wrap_unit(v, ly.wrap[k]);
     acc = __builtin_fma(v - ly.ctr[k], ly.mat[(size_t)k * d + c], acc);
   }
   out = acc;
@@ -310,8 +311,8 @@ __device__ __forceinline__ WalkState direction_state(int d) {
 __device__ __forceinline__ double move_distance_regs(const WalkLayer &ly, int d, int lane, double vo, double vn) {
   if (lane < d) {
     if (ly.wrap && !isnan(ly.wrap[lane])) {
-      vo = fmod(vo + ly.wrap[lane], 1.0);
-      vn = fmod(vn + ly.wrap[lane], 1.0);
+      vo = mlf_wrap_unit(vo, ly.wrap[lane]);
+      vn = mlf_wrap_unit(vn, ly.wrap[lane]);
     }
     vo -= ly.ctr[lane];
     vn -= ly.ctr[lane];

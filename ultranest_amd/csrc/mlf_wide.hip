@@ -23,6 +23,8 @@
 
 #include <math.h>
 
+#include "mlf_refarith_dev.hpp"
+
 namespace mlf {
 
 namespace {
@@ -251,7 +253,7 @@ __global__ void k_prep_wide(PrepArgs a, int dp) {
   if (a.do_ell) {
     for (int k = 0; k < d; ++k) dl[k * PB + tid] = row[k] - a.ell_ctr[k];
     double acc = 0.0;
-    for (int j = 0; j < d; ++j) {
+    for (int j = 0; j < d; ++j) {   // this kernel's main loop: it restates mlf_tregion_q (mlf_tregion_dev.hpp)
       const double dj = dl[j * PB + tid];
       const double *arow = a.ell_A + (size_t)j * dp;
       for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * dl[k * PB + tid];
@@ -268,7 +270,7 @@ __global__ void k_prep_wide(PrepArgs a, int dp) {
       double w = row[k];
       if (a.wrap_shift) {
         const double sh = a.wrap_shift[k];
-        if (sh == sh) w = fmod(w + sh, 1.0);   // NaN marks an unwrapped dimension
+        if (sh == sh) w = mlf_wrap_unit(w, sh);   // NaN marks an unwrapped dimension
       }
       dl[k * PB + tid] = w - a.lay_ctr[k];
     }
@@ -295,7 +297,7 @@ __global__ void k_quadmax_wide(QuadMaxArgs a, int dp) {
   for (int k = 0; k < d; ++k) dl[k * RB + tid] = row[k] - ctr[k];
   if (__any(use)) {
     double acc = 0.0;
-    for (int j = 0; j < d; ++j) {
+    for (int j = 0; j < d; ++j) {   // this kernel's main loop: it restates mlf_tregion_q (mlf_tregion_dev.hpp)
       const double dj = dl[j * RB + tid];
       const double *arow = A + (size_t)j * dp;
       for (int k = 0; k < d; ++k) acc += (dj * arow[k]) * dl[k * RB + tid];
