@@ -21,6 +21,9 @@
 //      with  lo = sigma*sqrt(r2)(1-2^-30) - Delta,  hi = sigma*sqrt(r2)(1+2^-30) + Delta,
 //            Delta = 2^-11(1+2^-9)(max|sigma a'| + |sigma b'|) + 2 sqrt(K) 2^-24 + 2^-40(...)   [input rounding]
 //            T_lo = lo^2 - Eacc,  T_hi = hi^2 + Eacc,  Eacc = 2^-15 (|ah|max+|bh|)^2 + 2^-22      [f32 accumulation]
+//      The bounded per-proposal stages (k_prep_sweep, k_prep4) put the MEASURED rounding residues in the place of the first term
+//      of Delta -- ea_max of the live points (k_quant_refs, stats[4]) + this proposal's own -- and c(K) in the place of 2^-15
+//      (filter_thresholds4r, mlf_filter_dev.hpp): half as many proposals in the band at N = 4000, d = 50.
 //   4. pairs with T_lo < Dt <= T_hi (or NaN) are appended to a list and re-evaluated exactly
 //      (k_recheck: the reference's sequential sub/mul/add in binary64, no FMA).
 //   Queries whose scaled coordinates do not fit binary16 are routed to the exact scan kernel;
@@ -45,7 +48,7 @@ typedef __attribute__((ext_vector_type(16))) float float16v;
 
 // ---------------------------------------------------------------- live-point statistics -----
 // centre c[k] = mean_i a_ik, amax = max |a_ik - c_k|, sigma = 2^-ceil(log2 amax), namax = max_i |sigma (a_i - c)|.
-// stats: [0]=sigma [1]=namax [2]=amax [3]=finite flag; c follows at [8..].
+// stats: [0]=sigma [1]=namax [2]=amax [3]=finite flag [4]=ea_max (k_quant_refs); c follows at [8..].
 // Three short launches over many workgroups (a single-workgroup version of the same passes took 0.2 ms: one CU,
 // whatever its inner loops looked like).  Everything is deterministic: partial sums are added in a fixed order by
 // every consumer, maxima are order independent.  scratch: kStatBlocks * 128 doubles + 2 u64.
@@ -127,6 +130,7 @@ __global__ void k_ref_finish(unsigned long long *maxima, double *stats) {
   stats[1] = nmax * (1.0 + 1e-12);
   stats[2] = amax_all;
   stats[3] = (amax_all < 1e300) ? 1.0 : 0.0;
+  stats[4] = 0.0;   // ea_max: a running maximum of k_quant_refs, which follows this launch whenever the statistics are renewed
 }
 
 // ---------------------------------------------------------------- live points -> f16 fragments
@@ -155,7 +159,7 @@ __global__ __launch_bounds__(256) void k_quant_refs(const double *refR, int n, i
   const int src = (ordered && have) ? perm[i] : (have ? i : 0);
   const double *row = refR + (size_t)src * dp;
   double v[2][8];
-  double na = 0.0;
+  double na = 0.0, ea2 = 0.0;
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int k0 = 8 * (sub + 16 * u);
@@ -168,12 +172,28 @@ __global__ __launch_bounds__(256) void k_quant_refs(const double *refR, int n, i
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       if (have && k0 + j < d) {
-        const half_t h = (half_t)(float)(sigma * (v[u][j] - stats[8 + k0 + j]));
+        const double xa = sigma * (v[u][j] - stats[8 + k0 + j]);
+        const half_t h = (half_t)(float)xa;
         const double hv = (double)(float)h;
         na += hv * hv;  // exact: 22-bit products, <= 128 terms -- any order of the sum gives the same bits
+        const double res = hv - xa;   // exact: a value and its binary16 rounding (a multiple of xa's last place, below 2^-10 |xa|)
+        ea2 += res * res;
       }
   }
   for (int o = 8; o > 0; o >>= 1) na += __shfl_xor(na, o, 16);
+  // ea_max (stats[4], filter_thresholds4r): the largest |ah - xa|_2 of a live point, rounded up -- (1 + 2^-40) covers the <= 130
+  // roundings of the binary64 sum of non-negative terms and the root, 2^-500 the squares that underflow.  Non-negative doubles
+  // order like their bit patterns; k_ref_finish has zeroed the word; a NaN (non-finite rows) becomes +inf: no certain decision.
+  // The storage-order pass alone reports (the mask-mode operand holds the same rows); one atomic per wave (its four rows).
+  if (!ordered) {
+    for (int o = 8; o > 0; o >>= 1) ea2 += __shfl_xor(ea2, o, 16);
+    double ea = have ? sqrt(ea2 * (1.0 + 0x1p-40)) * (1.0 + 0x1p-40) + 0x1p-500 : 0.0;
+    if (!(ea >= 0.0)) ea = INFINITY;
+    ea = fmax(ea, __shfl_xor(ea, 16, 64));
+    ea = fmax(ea, __shfl_xor(ea, 32, 64));
+    if ((threadIdx.x & 63) == 0 && ea > 0.0)
+      atomicMax(reinterpret_cast<unsigned long long *>(const_cast<double *>(stats) + 4), (unsigned long long)__double_as_longlong(ea));
+  }
   half_t p[3];
   if (have) {
     split3(na, p);

@@ -83,4 +83,45 @@ __device__ __forceinline__ bool filter_thresholds4(float namax, float nb, float 
   return t_hi < 30000.0f;   // false for NaN
 }
 
+// filter_thresholds4 with the binary16 rounding of both operands MEASURED instead of charged at its worst case
+// (k_prep_sweep, k_prep4; DESIGN.md 4b "measured residues").  With v = sigma (a' - b'), w = ah - bh:
+//   |ah - sigma a'| <= ea_max + 2^-40 |sigma a'|   ea_max = max over the live points of |ah - xa|_2, xa = the binary64
+//                                                  sigma (a - c) that was rounded (k_quant_refs sums the squares of the exact
+//                                                  differences in binary64, x (1 + 2^-40), root, rounded up); 2^-40: the
+//                                                  rounding of the centring, as before
+//   |bh - sigma b'| <= eb + zeta                   eb = |bh - bq|_2 of THIS proposal: the packing loop sums the squares of
+//                                                  v - fl16(v), v = -2 bq (exact in binary32: fl16(v) is v's neighbour on a
+//                                                  coarser grid), eb = 0.5 sqrt(sum) x up -- < 32 roundings of 2^-24 in a sum
+//                                                  of non-negative terms and one of the root
+// Both residues are what the conversions actually left -- binary16 subnormals, underflow to zero and the double rounding
+// through binary32 on the live side included -- so the terms 2^-11 (1 + 2^-9) w0 and 2 sqrt(K) 2^-24 of filter_thresholds4 go:
+//   Delta = ea_max + eb + 2^-40 w0 + (1 + 2^-10) zeta.
+// nbn (>= |sigma b'|, from |bh|) keeps its worst-case form: it only enters w0.
+// Accumulation: Dt is a sum of K = 16 KS exact products in binary32.  In the pessimistic model of DESIGN 4b (one rounding per
+// product, every partial sum bounded by S = sum |products|) the error is at most K 2^-24 S (1 + K 2^-24), and
+// S <= (|ah| + |bh|)^2 (1 + 2^-11) (the norm pieces may alternate in sign) with |ah| <= namax + ea_max: the coefficient is
+// c(K) (1 + 2^-9), c(K) = the power of two >= K 2^-24 and not below 2^-18 (K <= 64: 2^-18; K <= 128: 2^-17; filter_thresholds4
+// charges 2^-15, the bound at K = 512).  The other terms of Eacc (norm pieces: 2^-22; nb computed in binary32: 2^-18 nb) stay.
+template <int KS>
+__device__ __forceinline__ bool filter_thresholds4r(float ea_max, float eb, float namax, float nb, float zeta, float sqrt_k,
+                                                    float sr_lo, float sr_hi, float *lo_f, float *hi_f) {
+  constexpr int K = 16 * KS;
+  constexpr float ck = (K <= 64 ? 0x1p-18f : (K <= 128 ? 0x1p-17f : (K <= 256 ? 0x1p-16f : 0x1p-15f))) * (1.0f + 0x1p-9f);
+  static_assert(K <= 512, "c(K) is stated up to 512 columns");
+  const float up = 1.0f + 0x1p-18f, dn = 1.0f - 0x1p-18f;
+  const float nbh = __builtin_sqrtf(nb) * up;
+  const float nbn = ((nbh + sqrt_k * 0x1p-25f) * (1.0f + 0x1p-10f) + zeta) * up;
+  const float w0 = namax + nbn;
+  const float delta = (ea_max + eb + 0x1p-40f * w0 + (1.0f + 0x1p-10f) * zeta) * up;
+  const float w = w0 + ea_max + 0x1p-8f;
+  const float eacc = (ck * w * w + 0x1p-22f + 0x1p-18f * nb) * up;
+  const float lo = (sr_lo * dn - delta) * dn;
+  const float hi = (sr_hi * up + delta) * up;
+  const float t_lo = (lo * lo) * dn - eacc * up;
+  *lo_f = (lo > 0.0f && t_lo >= 0.0f) ? t_lo : -INFINITY;   // never negative and finite (see filter_thresholds)
+  const float t_hi = ((hi * hi) * up + eacc) * up;
+  *hi_f = t_hi;
+  return t_hi < 30000.0f;   // false for NaN
+}
+
 }  // namespace mlf

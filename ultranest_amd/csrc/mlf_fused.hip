@@ -263,6 +263,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
 
   const float sqrt_k = __builtin_sqrtf((float)(16 * KS));
   const float namax = (float)a.p.stats[1] * up;
+  const float ea_max = (float)a.p.stats[4] * up + 0x1p-100f;   // measured binary16 residue of the live points (k_quant_refs)
   float cs2 = 0.0f;
   for (int e = 0; e < 32 * NT; ++e) cs2 = __builtin_fmaf(csl[e], csl[e], cs2);
   const float csn = 0.5f * __builtin_sqrtf(cs2) * up;
@@ -500,6 +501,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
       }
       if (live && h == 0) a.p.gate[p] = ins_any ? 1 : 0;
       float nbq = 0.0f;
+      float2v ebq2 = {0.0f, 0.0f};
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -512,6 +514,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
           const float f0 = (float)cv.v[0], f1 = (float)cv.v[1];
           nbq = __builtin_fmaf(f0, f0, nbq);
           nbq = __builtin_fmaf(f1, f1, nbq);
+          // what the conversion left, exactly (filter_thresholds4r: eb); as a pair, for the packed binary32 instructions
+          const float2v e2 = (float2v){v0, v1} - (float2v){f0, f1};
+          ebq2 = __builtin_elementwise_fma(e2, e2, ebq2);
           if (t * 8 + m < KS * 4) pk[t * 8 + m] = cv.u;
         }
       const float nb = 0.25f * half_sum(nbq);
@@ -519,7 +524,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
       if (rt == 1 && (!sig_ok || !(nb <= 29000.0f))) rt = 2;
       if (rt == 1) {
         const float zeta = (zeta_scale * dnorm + zeta0) * up;
-        if (!filter_thresholds4(namax, nb, zeta, sqrt_k, sr_lo, sr_hi, &lo_f, &hi_f)) {
+        // 2^-60: squares of residues below 2^-74 underflow
+        const float eb = 0.5f * __builtin_sqrtf(half_sum(ebq2[0] + ebq2[1])) * up + 0x1p-60f;
+        if (!filter_thresholds4r<KS>(ea_max, eb, namax, nb, zeta, sqrt_k, sr_lo, sr_hi, &lo_f, &hi_f)) {
           rt = 2;
           lo_f = hi_f = -1.0f;
         }

@@ -165,10 +165,11 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
   __syncthreads();
 
   // uniform per-kernel quantities (binary32, rounded outward)
-  float namax = 0.0f, zeta_scale = 0.0f, zeta0 = 0.0f, sr_lo = 0.0f, sr_hi = 0.0f, kappa = 0.0f;
+  float namax = 0.0f, ea_max = 0.0f, zeta_scale = 0.0f, zeta0 = 0.0f, sr_lo = 0.0f, sr_hi = 0.0f, kappa = 0.0f;
   const float sqrt_k = __builtin_sqrtf((float)(16 * KS));
   if (quant) {
     namax = (float)a.stats[1] * up;
+    ea_max = (float)a.stats[4] * up + 0x1p-100f;   // measured binary16 residue of the live points (k_quant_refs)
     float cs2 = 0.0f;
     for (int e = 0; e < 32 * NT; ++e) cs2 = __builtin_fmaf(csl[e], csl[e], cs2);
     const float csn = 0.5f * __builtin_sqrtf(cs2) * up;
@@ -337,6 +338,7 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
     float16v tt[NT];
     unsigned pk[NT * 8];
     float nbq = 0.0f;
+    float2v ebq2 = {0.0f, 0.0f};
     if (quant) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -403,6 +405,9 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
           const float f0 = (float)cv.v[0], f1 = (float)cv.v[1];
           nbq = __builtin_fmaf(f0, f0, nbq);
           nbq = __builtin_fmaf(f1, f1, nbq);
+          // what the conversion left, exactly (filter_thresholds4r: eb); as a pair, for the packed binary32 instructions
+          const float2v e2 = (float2v){v0, v1} - (float2v){f0, f1};
+          ebq2 = __builtin_elementwise_fma(e2, e2, ebq2);
           pk[t * 8 + m] = cv.u;
         }
       const float nb = 0.25f * half_sum(nbq);   // |bh|^2
@@ -411,7 +416,9 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
       float lo_f = -1.0f, hi_f = -1.0f;
       if (rt == 1) {
         const float zeta = (zeta_scale * dnorm + zeta0) * up;
-        if (!filter_thresholds4(namax, nb, zeta, sqrt_k, sr_lo, sr_hi, &lo_f, &hi_f)) {
+        // 2^-60: squares of residues below 2^-74 underflow
+        const float eb = 0.5f * __builtin_sqrtf(half_sum(ebq2[0] + ebq2[1])) * up + 0x1p-60f;
+        if (!filter_thresholds4r<KS>(ea_max, eb, namax, nb, zeta, sqrt_k, sr_lo, sr_hi, &lo_f, &hi_f)) {
           rt = 2;
           lo_f = hi_f = -1.0f;
         }

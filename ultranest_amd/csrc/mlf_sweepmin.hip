@@ -23,7 +23,8 @@
 //   k_sweep_min<KS, QW, PF>   first range: slot = query; later range: compacted set + carried minima.
 //                             not last: keeps the queries without a certain hit (with their minimum);
 //                             last:     keeps the UNCERTAIN ones (minimum in (T_lo, T_hi]).
-//   k_uncertain<KS, NCH>      resident grid, one workgroup of 8 waves per set of 128 uncertain queries: band pairs ->
+//   k_uncertain<KS, NCH>      resident grid, one workgroup of 8 waves per set of 64, 96 or 128 uncertain queries (the smallest
+//                             that still gives every set a workgroup of its own, read from the device count): band pairs ->
 //                             LDS list, queries whitened into LDS, pairs decided; the ellipsoid band of k_prep4 rides
 //                             in trailing workgroups.
 // Integer minima on the bit patterns: for non-negative values the order of the floats; a negative Dt (possible within
@@ -349,11 +350,11 @@ __device__ __forceinline__ const lds_t<T> *lds_ptr(const T *p) {
   return (const lds_t<T> *)p;
 }
 
-template <int KS>
+template <int KS, int QW>
 __device__ __attribute__((noinline)) void uncertain_sweep(const void *refF_, int ntiles32_, const void *qF_, const float *thi_, long long set_,
                                                           long long ngroups_, long long nslots_, unsigned *plist_, unsigned *lcount_,
                                                           int wv_, int lane) {
-  constexpr int QW = 4;
+  static_assert(QW >= 2 && QW <= 4, "a set is two to four query groups");
   lds_t<unsigned> *plist = lds_ptr(plist_);
   lds_t<unsigned> *lcount = lds_ptr(lcount_);
   const void *refF = uni(refF_);
@@ -420,9 +421,17 @@ __device__ __attribute__((noinline)) void uncertain_sweep(const void *refF_, int
       }
     }
   };
+  auto mm1 = [&](const half8(&A)[KS], int g) __attribute__((always_inline)) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const float16v z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[s], bq[g][s], s == 0 ? z : acc[g], 0, 0, 0);
+    }
+  };
   auto tile = [&](const half8(&A)[KS], int t) __attribute__((always_inline)) {
     mm(A, 0, 1);
-    mm(A, 2, 3);
+    if constexpr (QW == 4) mm(A, 2, 3);
+    if constexpr (QW == 3) mm1(A, 2);
 #pragma unroll
     for (int g = 0; g < QW; ++g) list_group(g, t);
   };
@@ -552,8 +561,10 @@ __device__ __attribute__((noinline)) void whiten16_mfma(const double *tl_, int l
 }
 
 // The uncertain queries: band pairs found, queries whitened, pairs decided -- in ONE launch, a workgroup of 8 waves per
-// set of 128 uncertain queries (resident grid, sets taken in turn):
-//   1. wave w sweeps its eighth of the live tiles against the set's four query groups; every value at or below T_hi goes
+// set of QW x 32 uncertain queries (resident grid, sets taken in turn).  The launch lasts as long as ONE set's chain, so QW is
+// the smallest of 2, 3, 4 that gives every set its own workgroup (stage cycles at C5, sets of 128 -> 64: sweep 39 300 -> 22 000,
+// rows 17 700 -> 9 600, whitening 10 500 -> 8 100, pairs 10 500 -> 9 100, the matrix copy 7 500 either way):
+//   1. wave w sweeps its eighth of the live tiles against the set's query groups; every value at or below T_hi goes
 //      to the workgroup's pair list in LDS (slot from an LDS counter; values at or below T_lo too -- the earlier ranges
 //      said there is none, and if this sweep should disagree the exact arithmetic decides),
 //   2. the 128 queries are whitened in the reference's arithmetic -- k_whiten_rows' chain (delta_k = x_k - c_k, k-ascending
@@ -565,7 +576,6 @@ __device__ __attribute__((noinline)) void whiten16_mfma(const double *tl_, int l
 // round trips whatever the number of pairs).  The ellipsoid band of k_prep4 rides in trailing workgroups.
 template <int KS, int NCH>
 __global__ __launch_bounds__(512, 1) void k_uncertain(UncertainArgs a) {
-  constexpr int QW = 4;
   extern __shared__ __attribute__((aligned(16))) double lds_u[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int d = a.d, ds = uncertain_row_stride(d);
@@ -589,7 +599,13 @@ __global__ __launch_bounds__(512, 1) void k_uncertain(UncertainArgs a) {
     for (int k = 0; k < 8; ++k) a.seg_count[uncertain_stamp_base() + k] = 0u;
   }
   const long long nslots = (long long)*a.nslots_dev;
-  if ((long long)blockIdx.x * 128 >= nslots) {   // no set for this workgroup
+  const long long ngroups = (nslots + 31) / 32;
+  // Groups per set, from the count: the launch is one chain per set (sweep, rows, whitening, pairs), and a chain over half the
+  // queries has half the work in every stage -- so the sets are as small as ONE round of the workgroups allows:
+  // QW = clamp(ceil(groups / workgroups), 2, 4).  Past four groups per workgroup the sets stay at four and are taken in turn.
+  const int qw = ngroups > 3ll * nsweepblk ? 4 : (ngroups > 2ll * nsweepblk ? 3 : 2);
+  const int sz = 32 * qw;   // queries of a set
+  if ((long long)blockIdx.x * sz >= nslots) {   // no set for this workgroup
     if (threadIdx.x == 0) a.seg_count[blockIdx.x] = 0u;
     return;
   }
@@ -609,21 +625,25 @@ __global__ __launch_bounds__(512, 1) void k_uncertain(UncertainArgs a) {
     for (int it = 0; it < 8; ++it)
       if (threadIdx.x + it * 512 < nt) tl[threadIdx.x + it * 512] = v[it];
   }
-  const long long ngroups = (nslots + 31) / 32;
-  const long long nsets = (ngroups + QW - 1) / QW;
+  const long long nsets = (ngroups + qw - 1) / qw;
   unsigned listed_total = 0u;
 
   for (long long set = blockIdx.x; set < nsets; set += nsweepblk) {
     __syncthreads();   // the LDS of the set before is free
     if (threadIdx.x == 0) *lcount = 0u;
     if (threadIdx.x < 128) {
-      const long long slot = set * 128 + threadIdx.x;
-      qid[threadIdx.x] = slot < nslots ? a.qmap[slot] : -1;
+      const long long slot = set * sz + threadIdx.x;
+      qid[threadIdx.x] = ((int)threadIdx.x < sz && slot < nslots) ? a.qmap[slot] : -1;
     }
     __syncthreads();
     stamp();
-    // ---- 1. this wave's tiles against the four groups (band pairs -> plist)
-    uncertain_sweep<KS>(a.refF, a.ntiles32, a.qF, a.thi, set, ngroups, nslots, plist, lcount, wv, lane);
+    // ---- 1. this wave's tiles against the set's groups (band pairs -> plist)
+    if (qw == 2)
+      uncertain_sweep<KS, 2>(a.refF, a.ntiles32, a.qF, a.thi, set, ngroups, nslots, plist, lcount, wv, lane);
+    else if (qw == 3)
+      uncertain_sweep<KS, 3>(a.refF, a.ntiles32, a.qF, a.thi, set, ngroups, nslots, plist, lcount, wv, lane);
+    else
+      uncertain_sweep<KS, 4>(a.refF, a.ntiles32, a.qF, a.thi, set, ngroups, nslots, plist, lcount, wv, lane);
     stamp();
     // ---- 2. the set's queries: rows as handed over -> LDS (one round trip for all 128), then whitened in place (this
     // wave: queries 16 wv .. 16 wv + 15, eight at a time)
@@ -636,20 +656,21 @@ __global__ __launch_bounds__(512, 1) void k_uncertain(UncertainArgs a) {
       for (int it = 0; it < 16; ++it) {
         const int e = threadIdx.x + it * 512;
         const int ql = e / d, k = e - ql * d;
-        const int q = e < 128 * d ? qid[ql] : -1;
+        const int q = e < sz * d ? qid[ql] : -1;
         v[it] = q >= 0 ? a.pts[(long long)q * d + k] - a.lay_ctr[k] : 0.0;   // delta_k = x_k - c_k: one rounding, as in k_prep
       }
 #pragma unroll
       for (int it = 0; it < 16; ++it) {
         const int e = threadIdx.x + it * 512;
         const int ql = e / d, k = e - ql * d;
-        if (e < 128 * d) tq[ql * ds + k] = v[it];
+        if (e < sz * d) tq[ql * ds + k] = v[it];
       }
     }
     __syncthreads();
     stamp();
-    // d <= 64 here (launch_uncertain): 4 NK >= dp
-    if (a.dp <= 16) whiten16_mfma<4>(tl, a.ldt8, d, a.dp, tq, wv, lane);
+    // d <= 64 here (launch_uncertain): 4 NK >= dp; a wave whose sixteen rows lie behind the set has nothing to whiten
+    if (16 * __builtin_amdgcn_readfirstlane(wv) >= sz) {
+    } else if (a.dp <= 16) whiten16_mfma<4>(tl, a.ldt8, d, a.dp, tq, wv, lane);
     else if (a.dp <= 32) whiten16_mfma<8>(tl, a.ldt8, d, a.dp, tq, wv, lane);
     else if (a.dp <= 52) whiten16_mfma<13>(tl, a.ldt8, d, a.dp, tq, wv, lane);
     else whiten16_mfma<16>(tl, a.ldt8, d, a.dp, tq, wv, lane);
