@@ -737,6 +737,112 @@ def test_proposals_on_the_ellipsoid_boundary_on_every_route(route, K, oracle):
         reg.close()
 
 
+_STAGE_ENLARGE = 1.7
+# route -> (options, check).  400 live points are 13 tiles: "filter_phases" = 2 opens the min-only ranges there, whose first
+# launch is k_prep_sweep; without it the batch takes k_prep4 and one k_sweep; "mid_max_queries" above the batch: k_inside_mid
+_STAGE_ROUTES = {
+    "k_prep4": ({"filter_min_queries": 1, "mid_max_queries": 0, "fused_first_range": 0}, "sweep"),
+    "k_prep_sweep": ({"filter_min_queries": 1, "mid_max_queries": 0, "filter_phase_min_queries": 1, "filter_phases": 2,
+                      "fused_first_range": 1}, "ranges"),
+    "k_inside_mid": ({"filter_min_queries": 1, "mid_max_queries": 131072}, "stamps"),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _stage_inputs(d):
+    """400 live points, 4096 proposals.  The wrapping ellipsoid has the layer's axes, 25 / sigma times their length (sigma: the
+    power of two that scales the whitened live points for binary16) and ten times that along the longest one -- as far as the
+    bounded stage takes an ellipsoid (region_prep4_setup: d g |L|_F / min L_ii <= 0.02, checked here) -- so that it holds points
+    whose scaled whitened coordinates do not fit binary16.  Every second proposal is scaled onto q = enlarge within +-3e-16
+    relative (the ellipsoid band), a quarter sits next to live points, a quarter between 0.2 and 1.5 radii; three rows (first
+    group, middle, last group) lie far out on the long axis, inside the ellipsoid: |sigma t|^2 > 2 x 29000, the exact scan's."""
+    from oracle import oracle
+    rs = np.random.RandomState(9900 + d)
+    n, p = 400, 4096
+    u = 0.5 + 0.05 * rs.normal(size=(n, d))
+    ctr = u.mean(axis=0)
+    cov = np.cov(u, rowvar=0) * (d + 2) + 1e-6 * np.eye(d)
+    ev, evec = np.linalg.eigh(cov)
+    T = evec * ev ** -0.5
+    tl = oracle.affine_transform(u, ctr, T)
+    c = tl.mean(axis=0)
+    sigma = 2.0 ** -np.frexp(np.abs(tl - c).max())[1]
+    long_ev = ev * (25.0 / sigma) ** 2
+    long_ev[-1] *= 100.0
+    inv = (evec / long_ev) @ evec.T
+    inv = 0.5 * (inv + inv.T)
+    L = np.linalg.cholesky(inv)
+    g = (12.0 * ((d + (d & 1) + 15) // 16) + 8.0) * 2.0 ** -24 * (1 + 2.0 ** -8) + 2.0 ** -21.6 + 2.0 ** -21.9
+    assert d * g * np.linalg.norm(L) / np.diag(L).min() <= 0.02 * 0.9
+    dl = rs.normal(size=(p, d)) * 0.05
+    q = np.einsum('ij,jk,ik->i', dl, inv, dl)
+    scale = np.sqrt(_STAGE_ENLARGE / q)
+    kind = np.arange(p) % 4
+    on = kind % 2 == 0
+    scale[on] *= 1.0 + rs.uniform(-3e-16, 3e-16, size=on.sum())
+    scale[~on] *= rs.uniform(0.2, 1.5, size=(~on).sum())
+    pts = ctr + dl * scale[:, None]
+    near = kind == 1
+    pts[near] = u[rs.randint(n, size=near.sum())] + 0.9 * 0.05 * rs.normal(size=(near.sum(), d))
+    far = np.array([4, 2050, 4094])
+    pts[far] = ctr + np.outer(np.array([0.8, -0.9, 0.95]) * np.sqrt(long_ev[-1] * _STAGE_ENLARGE), evec[:, -1])
+    on[far] = False
+    dq = pts - ctr
+    q = np.einsum('ij,jk,ik->i', dq, inv, dq)
+    in_band = np.abs(q - _STAGE_ENLARGE) <= 2.0 ** -34 * np.sqrt((inv ** 2).sum()) * (dq ** 2).sum(axis=1)
+    assert in_band[on].sum() >= 1000, (d, int(in_band.sum()))
+    tp = oracle.affine_transform(pts, ctr, T)
+    nb = sigma ** 2 * ((tp - c) ** 2).sum(axis=1)
+    assert (nb[far] > 2 * 29000).all() and (np.delete(nb, far) < 29000 / 2).all(), (nb[far], np.delete(nb, far).max())
+    dd = ((tl[:200, None, :] - tl[None, :200, :]) ** 2).sum(axis=2)
+    np.fill_diagonal(dd, np.inf)
+    r2 = 1.5 * float(np.quantile(dd.min(axis=1), 0.8))
+    gate = oracle.inside_ellipsoid(pts, ctr, inv, _STAGE_ENLARGE).astype(bool)
+    want = oracle.region_inside(pts, tl, ctr, T, ctr, inv, _STAGE_ENLARGE, r2).astype(bool)
+    assert gate[far].all() and 0.2 < gate.mean() < 0.9 and 0.05 < want.mean() < 0.9 and not want[far].any()
+    assert want[near].mean() > 0.2 and not want.all()
+    return tl, ctr, T, inv, pts, r2, want
+
+
+@pytest.mark.parametrize("d", [7, 8, 50])
+@pytest.mark.parametrize("route", sorted(_STAGE_ROUTES))
+def test_bounded_stage_decisions_on_each_of_its_three_kernels(route, d, K):
+    """the decisions of mlf_prep4_dev.hpp as k_prep4, k_prep_sweep and k_inside_mid call them, with d == DP (8, 50) and d < DP
+    (7), proposals in the ellipsoid band and proposals routed to the exact scan: every mask is the exact scan's (filter = 0)
+    and the oracle's.  The options are set on this handle only and steer the batch to the kernel named.
+    What the suite did not reach before (read from the test sources): proposals in the ellipsoid band at d < DP on k_prep4 and
+    k_inside_mid (test_proposals_on_the_ellipsoid_boundary_on_every_route has them at d = 50 only, test_fused_diet_gpu.py at
+    d = 49 on k_prep_sweep only), and on any of the three a proposal INSIDE the ellipsoid that the pre-filter hands to the exact
+    scan (test_gpu_filter.py's far and non-finite rows fail the ellipsoid; its all-exact-scan case is d = 4 = DP).  A region that
+    holds such rows needs its own geometry, so this is a test of its own beside the boundary one, not a case of it."""
+    opts, check = _STAGE_ROUTES[route]
+    opts = dict(opts, time_filter_launches=1)
+    tl, ctr, T, inv, pts, r2, want = _stage_inputs(d)
+    reg = K.DeviceRegion()
+    try:
+        reg.set(tl, 0, ctr, T, None, ctr, inv, _STAGE_ENLARGE, r2)
+        for k_, v_ in opts.items():
+            reg.set_option(k_, v_)
+        got = reg.inside(pts)
+        launches = reg.timing_filter_launches()[0]
+        stats = reg.debug_stats()
+        assert np.array_equal(got, want), (route, d, np.flatnonzero(got != want)[:5])
+        # the path the batch took, as far as the library reports it
+        assert launches == {"sweep": 1, "ranges": 3, "stamps": 0}[check], (launches, stats)
+        assert (stats["range_cuts"][0] > 0) == (check == "ranges")
+        if check == "stamps":
+            assert "stamp7" in stats
+        else:      # the stage listed the boundary proposals for the binary64 test (k_inside_mid decides them on the spot)
+            assert stats["ellipsoid_band"] >= 1000
+        reg.set_option("filter", 0)
+        exact = reg.inside(pts)
+        assert np.array_equal(got, exact), (route, d, np.flatnonzero(got != exact)[:5])
+    finally:
+        for k_ in list(opts) + ["filter"]:
+            reg.set_option(k_)
+        reg.close()
+
+
 def test_wide_reference_classes_at_d_200(K, oracle):
     """the drop-in classes above 128 dimensions: AffineLayer + MLFriends, bootstrapped radius / enlargement (moments on the
     device, LAPACK inverse on the host, quadratic form on the device), create_ellipsoid, inside"""

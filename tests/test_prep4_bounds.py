@@ -132,27 +132,34 @@ class EllSetup:
         return hi, lo, f32(dn2 * f32(1.0 / self.sx**2))
 
 
+def ellipsoid_decision_tail(qs, dn2, c, enlarge):
+    """float32 restatement of prep4_ell_decide (csrc/mlf_prep4_dev.hpp): the binary32 decision from |y^|^2 and |x32|^2, scalars
+    or arrays; returns (sure_in, sure_out, dnorm, eta)"""
+    qs, dn2 = np.asarray(qs, dtype=np.float32), np.asarray(dn2, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        finite = (qs < f32(3e38)) & (dn2 < f32(3e38))
+        sq = np.sqrt(qs)
+        dnorm = np.sqrt(dn2) * UP + f32(2.0**-100)
+        eta = (c["g"] * (c["y0n"] + c["lf"] * dnorm) + c["el"] * dnorm + c["l_abs"]) * UP
+        de = dnorm + c["s0n"]
+        eps = c["eps_scale"] * (de * de) * UP
+        hi_ = sq * UP + eta
+        qhi = ((hi_ * hi_) * UP + eps) * UP
+        lo_ = (sq * DN - eta) * DN
+        qlo = ((lo_ * lo_) * DN - eps * UP) * DN
+        return finite & (qhi < dn32(enlarge)), finite & (lo_ > 0) & (qlo > up32(enlarge)), dnorm, eta
+
+
 def ellipsoid_decision(x, es, enlarge, tree):
     """restatement of the H3 part of k_prep4 for one proposal; returns (sure_in, sure_out, y^)"""
-    c = es.consts
     hi, lo, dn2 = es.operands(x)
     y = mfma16_chain(es.y0f, es.lh, es.ll, hi, lo, tree)
     qs = f32(0)
     for v in y:                                       # the device sums per lane and adds two halves: any order of n + 1 roundings
         qs = f32(np.float64(v) * np.float64(v) + np.float64(qs))
     qs = f32(qs * f32(1.0 / (es.sl * es.sx) ** 2))
-    finite = bool(qs < f32(3e38) and dn2 < f32(3e38))
-    sq = np.sqrt(qs)
-    dnorm = np.sqrt(dn2) * UP + f32(2.0**-100)
-    eta = (c["g"] * (c["y0n"] + c["lf"] * dnorm) + c["el"] * dnorm + c["l_abs"]) * UP
-    de = dnorm + c["s0n"]
-    eps = c["eps_scale"] * (de * de) * UP
-    hi_ = sq * UP + eta
-    qhi = ((hi_ * hi_) * UP + eps) * UP
-    lo_ = (sq * DN - eta) * DN
-    qlo = ((lo_ * lo_) * DN - eps * UP) * DN
-    return (finite and bool(qhi < dn32(enlarge)), finite and bool(lo_ > 0) and bool(qlo > up32(enlarge)),
-            y.astype(np.float64) / (es.sl * es.sx), float(eta))
+    sure_in, sure_out, _, eta = ellipsoid_decision_tail(qs, dn2, es.consts, enlarge)
+    return bool(sure_in), bool(sure_out), y.astype(np.float64) / (es.sl * es.sx), float(eta)
 
 
 @pytest.mark.parametrize("d,cond,shift", [(2, 1.0, 0.0), (5, 30.0, 1e-3), (20, 3.0, 0.0), (50, 1.5, 2e-3), (50, 40.0, 0.0),

@@ -17,7 +17,7 @@ PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libmlfriends_hip.so")
 OBJ = os.path.join(HERE, "build")
 SOURCES = ["mlf_scan.hip", "mlf_boot.hip", "mlf_prep.hip", "mlf_misc.hip", "mlf_filter.hip", "mlf_sweep.hip", "mlf_sweepmin.hip", "mlf_mid.hip", "mlf_fused.hip", "mlf_prep3.hip", "mlf_prep4.hip", "mlf_prep64.hip", "mlf_sample.hip", "mlf_walk.hip", "mlf_rwalk.hip", "mlf_sslice.hip", "mlf_walk_api.hip", "mlf_netiter.hip", "mlf_comm.hip", "mlf_small.hip", "mlf_wide.hip", "mlf_wide_filter.hip", "mlf_user.hip", "mlf_api.hip", "mlf_route.hip", "mlf_region.hip", "mlf_inside.hip", "mlf_region_sample.hip", "mlf_stateless.hip", "mlf_debug.hip"]
-HEADERS = ["mlf_common.hpp", "mlf_dpp_dev.hpp", "mlf_recheck_dev.hpp", "mlf_ell_exact.hpp", "mlf_misc.hpp", "mlf_filter.hpp", "mlf_filter_dev.hpp", "mlf_wide_filter.hpp", "mlf_prep3.hpp", "mlf_prep4.hpp", "mlf_prep64.hpp", "mlf_small.hpp", "mlf_sample.hpp", "mlf_walk.hpp", "mlf_walk_dev.hpp", "mlf_rwalk.hpp", "mlf_sslice.hpp", "mlf_ctx.hpp", "mlf_host.hpp", "mlf_philox_dev.hpp", "mlf_loglike_dev.hpp", "mlf_user_rows.hpp", "mlf_tregion_dev.hpp", "mlf_refarith_dev.hpp", os.path.join("..", "..", "include", "mlfriends_hip.h")]
+HEADERS = ["mlf_common.hpp", "mlf_dpp_dev.hpp", "mlf_recheck_dev.hpp", "mlf_ell_exact.hpp", "mlf_misc.hpp", "mlf_filter.hpp", "mlf_filter_dev.hpp", "mlf_wide_filter.hpp", "mlf_prep3.hpp", "mlf_prep4.hpp", "mlf_prep4_dev.hpp", "mlf_sweep_dev.hpp", "mlf_prep64.hpp", "mlf_small.hpp", "mlf_sample.hpp", "mlf_walk.hpp", "mlf_walk_dev.hpp", "mlf_rwalk.hpp", "mlf_sslice.hpp", "mlf_ctx.hpp", "mlf_host.hpp", "mlf_philox_dev.hpp", "mlf_loglike_dev.hpp", "mlf_user_rows.hpp", "mlf_tregion_dev.hpp", "mlf_refarith_dev.hpp", os.path.join("..", "..", "include", "mlfriends_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-strict-aliasing",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-result"]
 

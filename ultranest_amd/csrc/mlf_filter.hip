@@ -38,13 +38,13 @@
 #include "mlf_filter.hpp"
 #include "mlf_filter_dev.hpp"
 #include "mlf_sample.hpp"
+#include "mlf_sweep_dev.hpp"   // min3i
 
 #include <math.h>
 
 namespace mlf {
 
 typedef __attribute__((ext_vector_type(8))) _Float16 half8;
-typedef __attribute__((ext_vector_type(16))) float float16v;
 
 // ---------------------------------------------------------------- live-point statistics -----
 // centre c[k] = mean_i a_ik, amax = max |a_ik - c_k|, sigma = 2^-ceil(log2 amax), namax = max_i |sigma (a_i - c)|.
@@ -362,16 +362,6 @@ __global__ __launch_bounds__(256) void k_quant_queries(const double *q, long lon
       best[p] = kNone;
     }
   }
-}
-
-// Minimum of three MFMA results through their bit patterns (v_min3_i32): fminf() makes hipcc
-// canonicalise every operand first (one extra v_max per value), and an inline-asm v_min3_f32 would
-// read the MFMA result without the wait states the compiler only inserts for its own instructions.
-// Signed-integer order equals float order for values >= 0; a (tiny, rounding-induced) negative value
-// has a negative pattern and so still wins the minimum, which is all the threshold tests need.
-__device__ __forceinline__ int min3i(int a, int b, int c) {
-  const int m = a < b ? a : b;
-  return m < c ? m : c;
 }
 
 // ---------------------------------------------------------------- the MFMA filter ------------

@@ -1,11 +1,17 @@
 // mlf_filter_dev.hpp -- device helpers shared by the query quantisation kernels
-// (k_quant_queries in mlf_filter.hip, the fused stages k_prep3 / k_prep4)
+// (k_quant_queries in mlf_filter.hip, the fused stages k_prep3 / k_prep4).  The threshold functions are binary32 / binary64
+// arithmetic on scalars: they also build for the host once the HIP attributes are defined away (tests/prep4_decide_host.cpp);
+// the binary16 helpers are for the device compiler only.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <math.h>
+#include <stddef.h>
 
 namespace mlf {
 
+#if defined(__HIPCC__)
 typedef _Float16 half_t;
 
 __device__ __forceinline__ size_t frag_index(int row, int k, int ks) {
@@ -26,6 +32,7 @@ __device__ __forceinline__ void split3(double v, half_t *p) {
   p[1] = p2;
   p[2] = (half_t)(float)r2;
 }
+#endif
 
 // Certain-hit / certain-miss thresholds of one query (derivation: header of mlf_filter.hip and
 // DESIGN.md 4b).  nbn2 = |sigma (b - c)|^2 of the unrounded query.  Returns false if the query

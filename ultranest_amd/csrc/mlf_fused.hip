@@ -1,6 +1,6 @@
 // mlf_fused.hip -- the per-proposal stage of MLFriends.inside (H3 ellipsoid test + T1 whitening, mlfriends.pyx:882-912,
-// 737-743: k_prep4's bounded split-binary16 form, mlf_prep4.hip) and the FIRST live-point range of the min-only sweep
-// (k_sweep_min, mlf_sweepmin.hip) in ONE launch for the large batches.
+// 737-743: the bounded split-binary16 form of mlf_prep4.hip, its decisions stated in mlf_prep4_dev.hpp) and the FIRST
+// live-point range of the min-only sweep (k_sweep_min, mlf_sweepmin.hip) in ONE launch for the large batches.
 //
 // k_prep4 is HBM bound (reads 8 d bytes per proposal, 0.115 ms per 10^6 x 50 at 4.7 TB/s) and leaves the matrix cores 87 %
 // idle; k_sweep_min is matrix bound and leaves HBM idle; between them the binary16 operand makes a 128 MB write + 128 MB
@@ -16,17 +16,14 @@
 // (Round 2 measured this fusion with k_filter's loop: 395 against 112 + 273 us; with the min-only loop see DESIGN 4f.)
 #include "mlf_filter.hpp"
 #include "mlf_dpp_dev.hpp"
-#include "mlf_filter_dev.hpp"
 #include "mlf_prep4.hpp"
+#include "mlf_prep4_dev.hpp"
+#include "mlf_sweep_dev.hpp"
 
 #include <math.h>
 
 namespace mlf {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
-typedef float float2v __attribute__((ext_vector_type(2)));
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 typedef double double2v __attribute__((ext_vector_type(2)));
 
@@ -36,23 +33,16 @@ typedef double double2v __attribute__((ext_vector_type(2)));
 namespace {
 
 template <int DP, int NW = 8>
-struct F4 {
-  static constexpr int NS = (DP + 15) / 16;
-  static constexpr int KS = (DP + 6 + 15) / 16;
-  static constexpr int NT = (KS + 1) / 2;
-  static constexpr int NE = (DP + 31) / 32;
-  static constexpr int KMIN = DP <= 32 ? DP - 1 : (DP == 50 ? 49 : DP - 3);
-  static constexpr int NLT = NS + (NE > 1 ? NS - 2 : 0);
-  static constexpr int NPC = (DP + 3) / 4;
-  static constexpr size_t r16(size_t x) { return (x + 15) / 16 * 16; }
+struct F4 : Prep4Shape<DP> {
+  using S = Prep4Shape<DP>;
+  using S::r16;
   // row buffer of a wave: 8 waves per workgroup -- whole 1 KiB pieces (the last one overshoots the 32 rows); 4 waves per
   // workgroup -- exactly the 32 rows (the lanes of a piece that lie behind them are masked out of the request), so that TWO
   // such workgroups fit one CU's 160 KiB (d = 50: 2 x 80 960 B)
-  static constexpr size_t WAVE = NW == 8 ? r16((size_t)NPC * 1024 + 512) : r16((size_t)32 * DP * 8);
-  static constexpr size_t FRAG = (size_t)(2 * NT * NS + 2 * NLT) * 1024 + (size_t)(32 * NE + 32 * NT) * 4 + (size_t)(16 * NS) * 8;
+  static constexpr size_t WAVE = NW == 8 ? r16((size_t)S::NPC * 1024 + 512) : r16((size_t)32 * DP * 8);
   // + the workgroup's compaction counts (all LDS in the dynamic region); the operand reads of the padded coordinates
   // (k >= d, values discarded) reach up to 16 NS - d doubles behind the last wave's rows: they stay inside the allocation
-  static constexpr size_t LDS = r16(FRAG) + NW * WAVE + 64 + (NW == 8 ? 0 : 128);
+  static constexpr size_t LDS = r16(S::FRAG) + NW * WAVE + 64 + (NW == 8 ? 0 : 128);
 };
 
 // The matrix chains of a group as ONE list of steps (a step = one k-step of one output tile: two fragment reads, three matrix
@@ -79,31 +69,7 @@ struct F4Steps {
   static constexpr bool first_of_chain(int i) { return i >= NYE && kstep(i) == 0; }
 };
 
-__host__ __device__ constexpr int f4_column(int t, int i) {
-  return 32 * t + 16 * (i >> 4) + 8 * ((i >> 2) & 1) + 4 * ((i >> 3) & 1) + (i & 3);
-}
-// accumulator registers 2 m, 2 m + 1 of tile t hold, in BOTH halves of the wave, rows of T^T that belong to padded columns
-// (>= dp): their values are exact zeros (zero matrix rows, zero centre term)
-__host__ __device__ constexpr bool f4_pair_is_padding(int t, int m, int dp) {
-  for (int r = 2 * m; r < 2 * m + 2; ++r)
-    for (int h = 0; h < 2; ++h)
-      if (f4_column(t, (r & 3) + 8 * (r >> 2) + 4 * h) < dp) return false;
-  return true;
-}
-__device__ __forceinline__ float half_sum(float v) { return half_sum32(v); }
-__device__ __forceinline__ int min3i(int a, int b, int c) {
-  const int m = a < b ? a : b;
-  return m < c ? m : c;
-}
-constexpr int kPosInf = 0x7f800000;
-__device__ __forceinline__ int tree_min(const float16v &c, int run) {
-  const int m0 = min3i(__float_as_int(c[0]), __float_as_int(c[1]), __float_as_int(c[2]));
-  const int m1 = min3i(__float_as_int(c[3]), __float_as_int(c[4]), __float_as_int(c[5]));
-  const int m2 = min3i(__float_as_int(c[6]), __float_as_int(c[7]), __float_as_int(c[8]));
-  const int m3 = min3i(__float_as_int(c[9]), __float_as_int(c[10]), __float_as_int(c[11]));
-  const int m4 = min3i(__float_as_int(c[12]), __float_as_int(c[13]), __float_as_int(c[14]));
-  return min3i(min3i(m0, m1, m2), min3i(m3, m4, __float_as_int(c[15])), run);
-}
+// NM matrix instructions with NV vector instructions of the neighbouring reduction pinned between them (hand scheduled: stays here)
 template <int I, int NM, int NV>
 __device__ __forceinline__ void pin_step() {
   if constexpr (I < NM) {
@@ -153,7 +119,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
   double *xs = reinterpret_cast<double *>(area);
   const int d = FULL ? DP : a.p.d;
   const bool pregate = FULL ? (F & kFusedPre) != 0u : (a.variant & 4u) != 0u;
-  constexpr float up = 1.0f + 0x1p-18f, dn = 1.0f - 0x1p-18f;
   unsigned *wg_keep = reinterpret_cast<unsigned *>(ldsf + C::r16(C::FRAG) + NW * C::WAVE);   // [NW] + base
   unsigned &wg_base = wg_keep[8];
   // diagnostics (mlf_region_debug_fused_stamps): shader-clock stamps of ONE wave's stage boundaries
@@ -169,8 +134,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
   stamp(0);
 
   const double sigma = a.p.stats[0];
-  const bool sig_ok = sigma >= 0x1p-60 && sigma <= 0x1p60;
-  const float sig_f = sig_ok ? (float)sigma : 1.0f;
   if (blockIdx.x == 0 && tid == 0 && a.p.counters) {
     a.p.counters[0] = 0;
     a.p.counters[1] = 0;
@@ -204,7 +167,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
   if constexpr (!SQ)
     if (tid < 32 * NE) y0l[tid] = a.p.y0[tid];
   if (tid < 32 * NT) {
-    const int col = f4_column(tid >> 5, tid & 31);
+    const int col = prep4_column(tid >> 5, tid & 31);
     csl[tid] = col < DP ? 2.0f * (float)(sigma * a.p.stats[8 + col]) : 0.0f;
   }
   if (tid < 16 * NS) ctrl[tid] = tid < d ? (double)a.p.c.s_x * a.p.lay_ctr[tid] : 0.0;
@@ -261,22 +224,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
   __syncthreads();   // fragments and constants are in LDS
   stamp(1);
 
-  const float sqrt_k = __builtin_sqrtf((float)(16 * KS));
-  const float namax = (float)a.p.stats[1] * up;
-  const float ea_max = (float)a.p.stats[4] * up + 0x1p-100f;   // measured binary16 residue of the live points (k_quant_refs)
-  float cs2 = 0.0f;
-  for (int e = 0; e < 32 * NT; ++e) cs2 = __builtin_fmaf(csl[e], csl[e], cs2);
-  const float csn = 0.5f * __builtin_sqrtf(cs2) * up;
-  const float zeta_scale = sig_f * a.p.c.zt * up;
-  const float zeta0 = (a.p.c.g_chain * csn + sig_f * a.p.c.zt_abs) * up + 0x1p-100f;
-  const float kappa = -2.0f * sig_f * a.p.c.inv_st_sx;
-  const double sr = sigma * sqrt(a.p.r2);
-  const float sr_lo = (float)(sr * (1.0 - 0x1p-30)) * dn;
-  const float sr_hi = (float)(sr * (1.0 + 0x1p-30)) * up;
-  const float inv_sx2 = a.p.c.inv_sx * a.p.c.inv_sx, inv_slsx2 = a.p.c.inv_sl_sx * a.p.c.inv_sl_sx;
+  constexpr float up = kPrep4Up, dn = kPrep4Dn;   // (for the ellipsoid decision below)
+  Prep4Uniform u;
+  prep4_uniform(a.p.c, a.p.stats, a.p.r2, csl, sigma, DP, true, u);
   const double sxd = (double)a.p.c.s_x;
 
-  // ---- A. the per-proposal stage of this wave's four groups (k_prep4's body); fragments and thresholds stay in registers
+  // ---- A. the per-proposal stage of this wave's four groups (decisions: mlf_prep4_dev.hpp); fragments and thresholds stay in registers
   half8v bq[QW][KS];
   float tlo[QW], thi[QW];
   half8v hia[NS], loa[NS];
@@ -425,7 +378,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
         for (int t = 0; t < NT; ++t)
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (!f4_pair_is_padding(t, r >> 1, DP)) cs[t][r] = csl[32 * t + (r & 3) + 8 * (r >> 2) + 4 * h];
+            if (!prep4_pair_is_padding(t, r >> 1, DP)) cs[t][r] = csl[32 * t + (r & 3) + 8 * (r >> 2) + 4 * h];
         half8v fh[3], fl[3];
         auto read_step = [&](auto I) __attribute__((always_inline)) {
           constexpr int i = decltype(I)::value;
@@ -464,14 +417,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
           for (int t2 = 0; t2 < NT; ++t2)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-              if (!f4_pair_is_padding(t2, r >> 1, DP)) qs = __builtin_fmaf(tt[t2][r], tt[t2][r], qs);
+              if (!prep4_pair_is_padding(t2, r >> 1, DP)) qs = __builtin_fmaf(tt[t2][r], tt[t2][r], qs);
         }
       }
-      qs = half_sum(qs) * inv_slsx2;
-      const float dn2 = half_sum(dn2a) * inv_sx2;
+      qs = half_sum32(qs) * u.inv_slsx2;
+      const float dn2 = half_sum32(dn2a) * u.inv_sx2;
       bool sure_in = false, sure_out = false;
       float dnorm = 0.0f;
-      {
+      {   // prep4_ell_decide's text (mlf_prep4_dev.hpp) with the pre-gate folded in; local: through the call instances of this
+          // kernel took up to 10 more vector registers (profiles/prep4_dev_checks.md)
         const bool finite = qs < 3.0e38f && dn2 < 3.0e38f;
         const float sq = __builtin_sqrtf(qs);
         dnorm = __builtin_sqrtf(dn2) * up + 0x1p-100f;
@@ -506,46 +460,23 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void k_prep_sweep(FusedAr
       for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-          if (f4_pair_is_padding(t, m, DP)) continue;   // (compile time; pk was zeroed above; d = 50: 3 of the 16 pairs)
-          const float v0 = __builtin_fmaf(tt[t][2 * m], kappa, cs[t][2 * m]);
-          const float v1 = __builtin_fmaf(tt[t][2 * m + 1], kappa, cs[t][2 * m + 1]);
+          if (prep4_pair_is_padding(t, m, DP)) continue;   // (compile time; pk was zeroed above; d = 50: 3 of the 16 pairs)
+          const float v0 = __builtin_fmaf(tt[t][2 * m], u.kappa, cs[t][2 * m]);
+          const float v1 = __builtin_fmaf(tt[t][2 * m + 1], u.kappa, cs[t][2 * m + 1]);
           union { half2v v; unsigned u; } cv;
           cv.v = __builtin_convertvector((float2v){v0, v1}, half2v);
           const float f0 = (float)cv.v[0], f1 = (float)cv.v[1];
           nbq = __builtin_fmaf(f0, f0, nbq);
           nbq = __builtin_fmaf(f1, f1, nbq);
-          // what the conversion left, exactly (filter_thresholds4r: eb); as a pair, for the packed binary32 instructions
+          // what the conversion left, exactly (prep4_route: eb2); as a pair, for the packed binary32 instructions
           const float2v e2 = (float2v){v0, v1} - (float2v){f0, f1};
           ebq2 = __builtin_elementwise_fma(e2, e2, ebq2);
           if (t * 8 + m < KS * 4) pk[t * 8 + m] = cv.u;
         }
-      const float nb = 0.25f * half_sum(nbq);
-      int rt = ins_any ? 1 : 0;
-      if (rt == 1 && (!sig_ok || !(nb <= 29000.0f))) rt = 2;
-      if (rt == 1) {
-        const float zeta = (zeta_scale * dnorm + zeta0) * up;
-        // 2^-60: squares of residues below 2^-74 underflow
-        const float eb = 0.5f * __builtin_sqrtf(half_sum(ebq2[0] + ebq2[1])) * up + 0x1p-60f;
-        if (!filter_thresholds4r<KS>(ea_max, eb, namax, nb, zeta, sqrt_k, sr_lo, sr_hi, &lo_f, &hi_f)) {
-          rt = 2;
-          lo_f = hi_f = -1.0f;
-        }
-      }
-      const _Float16 p1 = (_Float16)nb;
-      const float r1 = nb - (float)p1;
-      const _Float16 p2 = (_Float16)r1;
-      const float r2 = r1 - (float)p2;
-      const _Float16 p3 = (_Float16)r2;
-      const _Float16 one = (_Float16)1.0f;
-      union { half2v v; unsigned u; } sp[3];
-      sp[0].v = (half2v){one, one};
-      sp[1].v = (half2v){one, p1};
-      sp[2].v = (half2v){p2, p3};
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const int c = DP + 2 * q;
-        if (h == ((c >> 3) & 1)) pk[4 * (c >> 4) + ((c & 7) >> 1)] = sp[q].u;
-      }
+      const float nb = 0.25f * half_sum32(nbq);
+      const int rt = prep4_route<Prep4Thresholds::kMeasured, KS>(
+          u, ins_any, nb, dnorm, [&]() __attribute__((always_inline)) { return half_sum32(ebq2[0] + ebq2[1]); }, lo_f, hi_f);
+      prep4_norm_pieces<DP>(nb, h, pk);
       if (rt != 1) {
 #pragma unroll
         for (int i = 0; i < KS * 4; ++i) pk[i] = 0u;

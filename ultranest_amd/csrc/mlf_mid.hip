@@ -1,15 +1,16 @@
 // mlf_mid.hip -- MLFriends.inside (reference mlfriends.pyx:1186-1211) for the batch sizes a real run draws
 // (ndraw_min = 128 ... ndraw_max = 65536, integrator.py:1050-1051; the callers: :1776-1804, :1854-1855) in ONE launch:
 //   H3 ellipsoid test + T1 whitening on the matrix cores (the bounded per-proposal stage of mlf_prep4.hip, same
-//   arithmetic, same error model), the MFMA pre-filter sweep of mlf_sweep.hip with its exact re-check
-//   (recheck_segment), the ellipsoid band in binary64, and the answers -- where the batched pipeline takes three
+//   arithmetic, same error model: its decisions are the functions of mlf_prep4_dev.hpp), the MFMA pre-filter sweep of
+//   mlf_sweep.hip with its exact re-check (recheck_segment), the ellipsoid band in binary64, and the answers -- where the
+//   batched pipeline takes three
 //   dependent launches (k_prep4 -> k_sweep -> k_scan tail: 31-37 us up to 16384 proposals, 62 us at 65536, each launch
 //   with its own ramp, and the binary16 operand a round trip through HBM in between).
 //
 // Workgroup = 8 waves = TWO sets of 4 query groups (256 proposals) x FOUR tile ranges (grid.y workgroups cover the 4
 // grid.y ranges of the live tiles):
-//   A. wave w runs the per-proposal stage of group 8 bx + w (k_prep4's body for one group: rows -> LDS as they lie,
-//      split binary16 operands, L^T delta and T^T delta on v_mfma_f32_32x32x16_f16, bounded ellipsoid decision,
+//   A. wave w runs the per-proposal stage of group 8 bx + w (mlf_prep4_dev.hpp's decisions for one group: rows -> LDS as
+//      they lie, split binary16 operands, L^T delta and T^T delta on v_mfma_f32_32x32x16_f16, bounded ellipsoid decision,
 //      thresholds).  Workgroups of the same two sets (blockIdx.y > 0) repeat this stage: 8 groups in ~6 us, cheaper than
 //      a hand-off through memory.  The workgroup with blockIdx.y == 0 also decides its band proposals in binary64 on the spot.
 //   B. the operand fragments a lane holds in registers after A ARE its 8-column pieces of the filter operand (the row
@@ -24,9 +25,11 @@
 //      the batch's scan flag: the (otherwise idle) exact-scan launch behind this one takes them.
 // All shared words are agent-scope atomics; the arrival counters return to zero by themselves.
 #include "mlf_filter.hpp"
-#include "mlf_filter_dev.hpp"
+#include "mlf_dpp_dev.hpp"
 #include "mlf_recheck_dev.hpp"
 #include "mlf_prep4.hpp"
+#include "mlf_prep4_dev.hpp"
+#include "mlf_sweep_dev.hpp"
 
 #include <math.h>
 
@@ -34,31 +37,21 @@
 
 namespace mlf {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
-typedef float float2v __attribute__((ext_vector_type(2)));
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 
 namespace {
 
 template <int DP>
-struct M4 {
-  static constexpr int NS = (DP + 15) / 16;
-  static constexpr int KS = (DP + 6 + 15) / 16;
-  static constexpr int NT = (KS + 1) / 2;
-  static constexpr int NE = (DP + 31) / 32;
-  static constexpr int KMIN = DP <= 32 ? DP - 1 : (DP == 50 ? 49 : DP - 3);
-  static constexpr int NLT = NS + (NE > 1 ? NS - 2 : 0);
-  static constexpr int NPC = (DP + 3) / 4;
-  static constexpr size_t r16(size_t x) { return (x + 15) / 16 * 16; }
-  static constexpr size_t STAGE = (size_t)NPC * 1024 + 512;                 // the group's rows as they lie
-  static constexpr size_t XCH = (size_t)KS * 1024 + 2 * 32 * 4 + 16;        // fragments, thresholds, gate / route bits
+struct M4 : Prep4Shape<DP> {
+  using S = Prep4Shape<DP>;
+  using S::FRAG;
+  using S::r16;
+  static constexpr size_t STAGE = (size_t)S::NPC * 1024 + 512;              // the group's rows as they lie
+  static constexpr size_t XCH = (size_t)S::KS * 1024 + 2 * 32 * 4 + 16;     // fragments, thresholds, gate / route bits
   static constexpr size_t kListCap = 128;                                   // band pairs of one (set, range)
   static constexpr size_t RCK = ((size_t)kTQ * ((DP + 1) | 1) + kTQ * 64) * 8 + 3 * 64 * 4;   // = recheck_w_lds(DP)
   static constexpr size_t TAIL = r16(RCK) + kListCap * 8 + 128 * 4;        // re-check scratch, list, best[]
   static constexpr size_t WAVE = r16(STAGE > XCH ? (STAGE > TAIL ? STAGE : TAIL) : (XCH > TAIL ? XCH : TAIL));
-  static constexpr size_t FRAG = (size_t)(2 * NT * NS + 2 * NLT) * 1024 + (size_t)(32 * NE + 32 * NT) * 4 + (size_t)(16 * NS) * 8;
   // the layer matrix in binary64 for the re-check, [DP][DP], behind the wave areas -- where the 160 KB allow it (d <= 52)
   static constexpr size_t TLB = (size_t)DP * DP * 8;
   static constexpr bool TL_OK = r16(FRAG) + 8 * WAVE + r16(TLB) <= 160 * 1024;
@@ -196,24 +189,6 @@ __device__ __forceinline__ void recheck_mid(const RecheckWArgs &a, const double 
   }
 }
 
-__host__ __device__ inline int m4_column(int t, int i) {
-  return 32 * t + 16 * (i >> 4) + 8 * ((i >> 2) & 1) + 4 * ((i >> 3) & 1) + (i & 3);
-}
-__device__ __forceinline__ float half_sum(float v) { return v + __shfl_xor(v, 32, 64); }
-__device__ __forceinline__ int min3i(int a, int b, int c) {
-  const int m = a < b ? a : b;
-  return m < c ? m : c;
-}
-constexpr int kPosInf = 0x7f800000;
-__device__ __forceinline__ int tree_min(const float16v &c, int run) {
-  const int m0 = min3i(__float_as_int(c[0]), __float_as_int(c[1]), __float_as_int(c[2]));
-  const int m1 = min3i(__float_as_int(c[3]), __float_as_int(c[4]), __float_as_int(c[5]));
-  const int m2 = min3i(__float_as_int(c[6]), __float_as_int(c[7]), __float_as_int(c[8]));
-  const int m3 = min3i(__float_as_int(c[9]), __float_as_int(c[10]), __float_as_int(c[11]));
-  const int m4 = min3i(__float_as_int(c[12]), __float_as_int(c[13]), __float_as_int(c[14]));
-  return min3i(min3i(m0, m1, m2), min3i(m3, m4, __float_as_int(c[15])), run);
-}
-
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned gu32;
 #define MLF_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
@@ -245,11 +220,8 @@ __global__ __launch_bounds__(512, 1) void k_inside_mid(MidArgs a) {
   unsigned char *area = area0 + (size_t)wv * C::WAVE;
   double *xs = reinterpret_cast<double *>(area);
   const int d = a.d;
-  constexpr float up = 1.0f + 0x1p-18f, dn = 1.0f - 0x1p-18f;
 
   const double sigma = a.stats[0];
-  const bool sig_ok = sigma >= 0x1p-60 && sigma <= 0x1p60;
-  const float sig_f = sig_ok ? (float)sigma : 1.0f;
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {   // nobody else touches these in this path
     a.counters[0] = 0;
     a.counters[1] = 0;
@@ -267,7 +239,7 @@ __global__ __launch_bounds__(512, 1) void k_inside_mid(MidArgs a) {
   }
   if (tid < 32 * NE) y0l[tid] = a.y0[tid];
   if (tid < 32 * NT) {
-    const int col = m4_column(tid >> 5, tid & 31);
+    const int col = prep4_column(tid >> 5, tid & 31);
     csl[tid] = col < DP ? 2.0f * (float)(sigma * a.stats[8 + col]) : 0.0f;
   }
   if (tid < 16 * NS) ctrl[tid] = tid < d ? (double)a.c.s_x * a.lay_ctr[tid] : 0.0;
@@ -299,19 +271,8 @@ __global__ __launch_bounds__(512, 1) void k_inside_mid(MidArgs a) {
   __syncthreads();   // fragments and constants are in LDS
   stamp();
 
-  // uniform quantities (binary32, rounded outward) -- k_prep4's
-  const float sqrt_k = __builtin_sqrtf((float)(16 * KS));
-  const float namax = (float)a.stats[1] * up;
-  float cs2 = 0.0f;
-  for (int e = 0; e < 32 * NT; ++e) cs2 = __builtin_fmaf(csl[e], csl[e], cs2);
-  const float csn = 0.5f * __builtin_sqrtf(cs2) * up;
-  const float zeta_scale = sig_f * a.c.zt * up;
-  const float zeta0 = (a.c.g_chain * csn + sig_f * a.c.zt_abs) * up + 0x1p-100f;
-  const float kappa = -2.0f * sig_f * a.c.inv_st_sx;
-  const double sr = sigma * sqrt(a.r2);
-  const float sr_lo = (float)(sr * (1.0 - 0x1p-30)) * dn;
-  const float sr_hi = (float)(sr * (1.0 + 0x1p-30)) * up;
-  const float inv_sx2 = a.c.inv_sx * a.c.inv_sx, inv_slsx2 = a.c.inv_sl_sx * a.c.inv_sl_sx;
+  Prep4Uniform u;
+  prep4_uniform(a.c, a.stats, a.r2, csl, sigma, DP, true, u);
 
   // ---- A. the per-proposal stage of this wave's group
   unsigned pk[KS * 4];
@@ -393,33 +354,22 @@ __global__ __launch_bounds__(512, 1) void k_inside_mid(MidArgs a) {
         tt[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, hia[s], tt[t], 0, 0, 0);
       }
     }
-    qs = half_sum(qs) * inv_slsx2;
-    const float dn2 = half_sum(dn2a) * inv_sx2;
+    qs = half_sum32(qs) * u.inv_slsx2;
+    const float dn2 = half_sum32(dn2a) * u.inv_sx2;
     bool sure_in = false, sure_out = false;
     float dnorm = 0.0f;
-    {
-      const bool finite = qs < 3.0e38f && dn2 < 3.0e38f;
-      const float sq = __builtin_sqrtf(qs);
-      dnorm = __builtin_sqrtf(dn2) * up + 0x1p-100f;
-      const float eta = (a.c.g_chain * (a.c.y0n + a.c.lf * dnorm) + a.c.el * dnorm + a.c.l_abs) * up;
-      const float de = dnorm + a.c.s0n;
-      const float eps = a.c.eps_scale * (de * de) * up;
-      const float hi = sq * up + eta;
-      const float qhi = ((hi * hi) * up + eps) * up;
-      const float lo = (sq * dn - eta) * dn;
-      const float qlo = ((lo * lo) * dn - eps * up) * dn;
-      sure_in = finite && qhi < a.c.enl_lo;
-      sure_out = finite && lo > 0.0f && qlo > a.c.enl_hi;
-    }
+    prep4_ell_decide(a.c, qs, dn2, dnorm, sure_in, sure_out);
     const bool band = live && !sure_in && !sure_out;
     const bool ins_any = live && !sure_out;   // band proposals: provisionally inside for the sweep
     float nbq = 0.0f;
+    // (the packing loop stays here, as in the other two kernels: hand scheduled.  This one also packs the pairs of padded columns
+    // -- prep4_pair_is_padding: exact zeros, the same operand -- and sums no residue: worst-case thresholds below)
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
-        const float v0 = __builtin_fmaf(tt[t][2 * m], kappa, csl[32 * t + ((2 * m) & 3) + 8 * ((2 * m) >> 2) + 4 * h]);
-        const float v1 = __builtin_fmaf(tt[t][2 * m + 1], kappa, csl[32 * t + ((2 * m + 1) & 3) + 8 * ((2 * m + 1) >> 2) + 4 * h]);
+        const float v0 = __builtin_fmaf(tt[t][2 * m], u.kappa, csl[32 * t + ((2 * m) & 3) + 8 * ((2 * m) >> 2) + 4 * h]);
+        const float v1 = __builtin_fmaf(tt[t][2 * m + 1], u.kappa, csl[32 * t + ((2 * m + 1) & 3) + 8 * ((2 * m + 1) >> 2) + 4 * h]);
         union { half2v v; unsigned u; } cv;
         cv.v = __builtin_convertvector((float2v){v0, v1}, half2v);
         const float f0 = (float)cv.v[0], f1 = (float)cv.v[1];
@@ -427,31 +377,10 @@ __global__ __launch_bounds__(512, 1) void k_inside_mid(MidArgs a) {
         nbq = __builtin_fmaf(f1, f1, nbq);
         if (t * 8 + m < KS * 4) pk[t * 8 + m] = cv.u;
       }
-    const float nb = 0.25f * half_sum(nbq);
-    int rt = ins_any ? 1 : 0;
-    if (rt == 1 && (!sig_ok || !(nb <= 29000.0f))) rt = 2;
-    if (rt == 1) {
-      const float zeta = (zeta_scale * dnorm + zeta0) * up;
-      if (!filter_thresholds4(namax, nb, zeta, sqrt_k, sr_lo, sr_hi, &lo_f, &hi_f)) {
-        rt = 2;
-        lo_f = hi_f = -1.0f;
-      }
-    }
-    const _Float16 p1 = (_Float16)nb;
-    const float r1 = nb - (float)p1;
-    const _Float16 p2 = (_Float16)r1;
-    const float r2 = r1 - (float)p2;
-    const _Float16 p3 = (_Float16)r2;
-    const _Float16 one = (_Float16)1.0f;
-    union { half2v v; unsigned u; } sp[3];
-    sp[0].v = (half2v){one, one};
-    sp[1].v = (half2v){one, p1};
-    sp[2].v = (half2v){p2, p3};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int c = DP + 2 * q;
-      if (h == ((c >> 3) & 1)) pk[4 * (c >> 4) + ((c & 7) >> 1)] = sp[q].u;
-    }
+    const float nb = 0.25f * half_sum32(nbq);
+    // worst-case thresholds: this kernel measures no eb and does not use ea_max yet ("measured residues": follow-up)
+    const int rt = prep4_route<Prep4Thresholds::kWorstCase, KS>(u, ins_any, nb, dnorm, 0.0f, lo_f, hi_f);
+    prep4_norm_pieces<DP>(nb, h, pk);
     if (rt != 1) {
 #pragma unroll
       for (int i = 0; i < KS * 4; ++i) pk[i] = 0u;

@@ -49,6 +49,10 @@
 // columns of its own fragment piece -- the f16 operand is packed in registers and stored with one contiguous 1 KiB wave
 // store per k-step, no transpose.  Rows arrive in LDS as they lie in HBM (global_load_lds, 16-byte pieces, no staging
 // registers); the next group's rows are in flight while the current one is processed.
+// The decisions of the stage -- shape, row order, uniform quantities, ellipsoid decision, route and thresholds, norm pieces --
+// are stated in mlf_prep4_dev.hpp for this kernel, k_prep_sweep (mlf_fused.hip) and k_inside_mid (mlf_mid.hip); what is written
+// out below is hand scheduled (fetches, operand and packing loops, matrix chains, ballot, stores), and the header's text of the
+// ellipsoid decision and of the route, which cost this kernel registers as calls.
 // -ffp-contract=off; FMAs only where written.
 #include "mlf_prep4.hpp"
 
@@ -57,54 +61,27 @@
 #include <vector>
 
 #include "mlf_dpp_dev.hpp"
-#include "mlf_filter_dev.hpp"
 #include "mlf_prep3.hpp"
+#include "mlf_prep4_dev.hpp"
 #include "mlf_ell_exact.hpp"
 #include "mlf_recheck_dev.hpp"
 
 namespace mlf {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
 typedef double double4v __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
-typedef float float2v __attribute__((ext_vector_type(2)));
 
 namespace {
 
 template <int DP>
-struct P4 {
-  static constexpr int NS = (DP + 15) / 16;             // k-steps of 16 coordinates (K = 16 NS)
-  static constexpr int KS = (DP + 6 + 15) / 16;         // filter k-steps of 16 binary16 columns
-  static constexpr int NT = (KS + 1) / 2;               // 32-row output tiles of the whitening
-  static constexpr int NE = (DP + 31) / 32;             // 32-row output tiles of L^T delta
-  static constexpr int KMIN = DP <= 32 ? DP - 1 : (DP == 50 ? 49 : DP - 3);   // every d served by this instance exceeds KMIN - 1
-  static constexpr int NLT = NS + (NE > 1 ? NS - 2 : 0);   // stored k-steps of the L^T fragments (tile 1: k >= 32)
-  static constexpr int NPC = (DP + 3) / 4;              // 1 KiB pieces (64 lanes x 16 bytes) that cover a group of 32 rows
-  static constexpr int WAVE_DOUBLES = NPC * 128 + 64;   // staging buffer per wave: the group's rows as they lie in HBM
-  static constexpr size_t lds_for(int waves) {
-    return (size_t)(2 * NT * NS + 2 * NLT) * 1024 + (size_t)(32 * NE + 32 * NT) * sizeof(float) +
-           (size_t)(16 * NS) * sizeof(double) + (size_t)waves * WAVE_DOUBLES * sizeof(double);
-  }
+struct P4 : Prep4Shape<DP> {
+  using S = Prep4Shape<DP>;
+  static constexpr int WAVE_DOUBLES = S::NPC * 128 + 64;   // staging buffer per wave: the group's rows as they lie in HBM
+  static constexpr size_t lds_for(int waves) { return S::FRAG + (size_t)waves * WAVE_DOUBLES * sizeof(double); }
   // waves of a workgroup: one workgroup per CU with as many waves (up to two per SIMD, the register budget) as
   // the 160 KiB of LDS hold staging buffers for -- the fragments are shared by the workgroup
   static constexpr int NW = lds_for(8) <= 160 * 1024 ? 8 : (lds_for(6) <= 160 * 1024 ? 6 : 4);
   static constexpr size_t lds_bytes() { return lds_for(NW); }
 };
-
-// filter column of row i of tile t of the whitening product
-__host__ __device__ constexpr int p4_column(int t, int i) {
-  return 32 * t + 16 * (i >> 4) + 8 * ((i >> 2) & 1) + 4 * ((i >> 3) & 1) + (i & 3);
-}
-// accumulator registers 2 m, 2 m + 1 of tile t hold, in BOTH halves of the wave, rows of T^T of padded columns (>= dp): zeros
-__host__ __device__ constexpr bool p4_pair_is_padding(int t, int m, int dp) {
-  for (int r = 2 * m; r < 2 * m + 2; ++r)
-    for (int h = 0; h < 2; ++h)
-      if (p4_column(t, (r & 3) + 8 * (r >> 2) + 4 * h) < dp) return false;
-  return true;
-}
-
-__device__ __forceinline__ float half_sum(float v) { return half_sum32(v); }
 
 }  // namespace
 
@@ -127,11 +104,8 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
   double *xs = ctrl + 16 * NS + wv * C::WAVE_DOUBLES;
   const int d = a.d;
   const bool quant = a.do_tr != 0;
-  constexpr float up = 1.0f + 0x1p-18f, dn = 1.0f - 0x1p-18f;
 
   const double sigma = quant ? a.stats[0] : 1.0;
-  const bool sig_ok = sigma >= 0x1p-60 && sigma <= 0x1p60;
-  const float sig_f = sig_ok ? (float)sigma : 1.0f;
   if (blockIdx.x == 0 && tid == 0 && a.counters) {
     a.counters[0] = 0;
     a.counters[1] = 0;
@@ -157,30 +131,15 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
   }
   if (tid < 32 * NE) y0l[tid] = a.y0[tid];   // already scaled by s_L s_x
   if (tid < 32 * NT) {
-    const int col = p4_column(tid >> 5, tid & 31);
+    const int col = prep4_column(tid >> 5, tid & 31);
     csl[tid] = (quant && col < DP) ? 2.0f * (float)(sigma * a.stats[8 + col]) : 0.0f;   // + 2 sigma c_s: the operand is -2 (sigma t - sigma c_s)
   }
   if (tid < 16 * NS) ctrl[tid] = tid < d ? (double)a.c.s_x * a.lay_ctr[tid] : 0.0;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces have landed
   __syncthreads();
 
-  // uniform per-kernel quantities (binary32, rounded outward)
-  float namax = 0.0f, ea_max = 0.0f, zeta_scale = 0.0f, zeta0 = 0.0f, sr_lo = 0.0f, sr_hi = 0.0f, kappa = 0.0f;
-  const float sqrt_k = __builtin_sqrtf((float)(16 * KS));
-  if (quant) {
-    namax = (float)a.stats[1] * up;
-    ea_max = (float)a.stats[4] * up + 0x1p-100f;   // measured binary16 residue of the live points (k_quant_refs)
-    float cs2 = 0.0f;
-    for (int e = 0; e < 32 * NT; ++e) cs2 = __builtin_fmaf(csl[e], csl[e], cs2);
-    const float csn = 0.5f * __builtin_sqrtf(cs2) * up;
-    zeta_scale = sig_f * a.c.zt * up;                                   // per unit |delta|
-    zeta0 = (a.c.g_chain * csn + sig_f * a.c.zt_abs) * up + 0x1p-100f;
-    kappa = -2.0f * sig_f * a.c.inv_st_sx;                              // accumulator -> -2 sigma t (powers of two: exact)
-    const double sr = sigma * sqrt(a.r2);
-    sr_lo = (float)(sr * (1.0 - 0x1p-30)) * dn;
-    sr_hi = (float)(sr * (1.0 + 0x1p-30)) * up;
-  }
-  const float inv_sx2 = a.c.inv_sx * a.c.inv_sx, inv_slsx2 = a.c.inv_sl_sx * a.c.inv_sl_sx;
+  Prep4Uniform u;
+  prep4_uniform(a.c, a.stats, a.r2, csl, sigma, DP, quant, u);
 
   const long long ngroups = quant ? a.nqpad / 32 : (a.np + 31) / 32;
   const long long wave_id = (long long)blockIdx.x * C::NW + wv;
@@ -353,12 +312,14 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
       }
     }
 
-    qs = half_sum(qs) * inv_slsx2;          // powers of two: exact scalings
-    const float dn2 = half_sum(dn2a) * inv_sx2;
+    qs = half_sum32(qs) * u.inv_slsx2;          // powers of two: exact scalings
+    const float dn2 = half_sum32(dn2a) * u.inv_sx2;
 
     bool sure_in = false, sure_out = false;
     float dnorm = 0.0f;
-    {
+    {   // prep4_ell_decide's text (mlf_prep4_dev.hpp); local, as prep4_route's below: through the calls instances of this kernel
+        // took 2 to 6 more vector registers (profiles/prep4_dev_checks.md)
+      constexpr float up = kPrep4Up, dn = kPrep4Dn;
       const bool finite = qs < 3.0e38f && dn2 < 3.0e38f;   // false for NaN
       const float sq = __builtin_sqrtf(qs);
       dnorm = __builtin_sqrtf(dn2) * up + 0x1p-100f;
@@ -394,51 +355,35 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
       for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-          if (p4_pair_is_padding(t, m, DP)) {   // (compile time) exact zeros in both halves of the wave
+          if (prep4_pair_is_padding(t, m, DP)) {   // (compile time) exact zeros in both halves of the wave
             pk[t * 8 + m] = 0u;
             continue;
           }
-          const float v0 = __builtin_fmaf(tt[t][2 * m], kappa, csl[32 * t + ((2 * m) & 3) + 8 * ((2 * m) >> 2) + 4 * h]);
-          const float v1 = __builtin_fmaf(tt[t][2 * m + 1], kappa, csl[32 * t + ((2 * m + 1) & 3) + 8 * ((2 * m + 1) >> 2) + 4 * h]);
+          const float v0 = __builtin_fmaf(tt[t][2 * m], u.kappa, csl[32 * t + ((2 * m) & 3) + 8 * ((2 * m) >> 2) + 4 * h]);
+          const float v1 = __builtin_fmaf(tt[t][2 * m + 1], u.kappa, csl[32 * t + ((2 * m + 1) & 3) + 8 * ((2 * m + 1) >> 2) + 4 * h]);
           union { half2v v; unsigned u; } cv;
           cv.v = __builtin_convertvector((float2v){v0, v1}, half2v);
           const float f0 = (float)cv.v[0], f1 = (float)cv.v[1];
           nbq = __builtin_fmaf(f0, f0, nbq);
           nbq = __builtin_fmaf(f1, f1, nbq);
-          // what the conversion left, exactly (filter_thresholds4r: eb); as a pair, for the packed binary32 instructions
+          // what the conversion left, exactly (prep4_route: eb2); as a pair, for the packed binary32 instructions
           const float2v e2 = (float2v){v0, v1} - (float2v){f0, f1};
           ebq2 = __builtin_elementwise_fma(e2, e2, ebq2);
           pk[t * 8 + m] = cv.u;
         }
-      const float nb = 0.25f * half_sum(nbq);   // |bh|^2
+      const float nb = 0.25f * half_sum32(nbq);   // |bh|^2
       int rt = ins_any ? 1 : 0;
-      if (rt == 1 && (!sig_ok || !(nb <= 29000.0f))) rt = 2;   // NaN / inf / does not fit binary16: exact scan
+      if (rt == 1 && (!u.sig_ok || !(nb <= 29000.0f))) rt = 2;   // NaN / inf / does not fit binary16: exact scan
       float lo_f = -1.0f, hi_f = -1.0f;
       if (rt == 1) {
-        const float zeta = (zeta_scale * dnorm + zeta0) * up;
-        // 2^-60: squares of residues below 2^-74 underflow
-        const float eb = 0.5f * __builtin_sqrtf(half_sum(ebq2[0] + ebq2[1])) * up + 0x1p-60f;
-        if (!filter_thresholds4r<KS>(ea_max, eb, namax, nb, zeta, sqrt_k, sr_lo, sr_hi, &lo_f, &hi_f)) {
+        const float zeta = (u.zeta_scale * dnorm + u.zeta0) * kPrep4Up;
+        const float eb = 0.5f * __builtin_sqrtf(half_sum32(ebq2[0] + ebq2[1])) * kPrep4Up + 0x1p-60f;
+        if (!filter_thresholds4r<KS>(u.ea_max, eb, u.namax, nb, zeta, u.sqrt_k, u.sr_lo, u.sr_hi, &lo_f, &hi_f)) {
           rt = 2;
           lo_f = hi_f = -1.0f;
         }
       }
-      // three pieces of |bh|^2 (x ones column of the live point) behind three ones (x its |ah|^2 pieces)
-      const _Float16 p1 = (_Float16)nb;
-      const float r1 = nb - (float)p1;
-      const _Float16 p2 = (_Float16)r1;
-      const float r2 = r1 - (float)p2;
-      const _Float16 p3 = (_Float16)r2;
-      const _Float16 one = (_Float16)1.0f;
-      union { half2v v; unsigned u; } sp[3];
-      sp[0].v = (half2v){one, one};
-      sp[1].v = (half2v){one, p1};
-      sp[2].v = (half2v){p2, p3};
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const int c = DP + 2 * q;   // compile-time after unrolling
-        if (h == ((c >> 3) & 1)) pk[4 * (c >> 4) + ((c & 7) >> 1)] = sp[q].u;
-      }
+      prep4_norm_pieces<DP>(nb, h, pk);
       const bool keep = rt == 1;   // otherwise every operand column of this query is zero
 #pragma unroll
       for (int s = 0; s < KS; ++s)
@@ -467,13 +412,8 @@ __global__ __launch_bounds__(64 * P4<DP>::NW, 1) void k_prep4(Prep4Args a) {
 // ---------------------------------------------------------------- host helpers -----------------
 bool prep4_usable(int d) { return d >= 1 && d <= 64; }
 
-static int p4_ns(int dp) { return (dp + 15) / 16; }
-static int p4_nt(int dp) { return (((dp + 6 + 15) / 16) + 1) / 2; }
-static int p4_ne(int dp) { return (dp + 31) / 32; }
-static int p4_nlt(int dp) { return p4_ns(dp) + (p4_ne(dp) > 1 ? p4_ns(dp) - 2 : 0); }
-
-size_t prep4_ltf_count(int dp) { return (size_t)2 * p4_nlt(dp) * 512; }   // binary16 values: hi block then lo block
-size_t prep4_ttf_count(int dp) { return (size_t)2 * p4_nt(dp) * p4_ns(dp) * 512; }
+size_t prep4_ltf_count(int dp) { return (size_t)2 * prep4_nlt(dp) * 512; }   // binary16 values: hi block then lo block
+size_t prep4_ttf_count(int dp) { return (size_t)2 * prep4_nt(dp) * prep4_ns(dp) * 512; }
 
 namespace {
 // split s * v into two binary16 pieces; returns the representation error s v - hi - lo
@@ -491,7 +431,7 @@ double split16(double v, double s, _Float16 *hi, _Float16 *lo) {
 // Returns |E|_F (representation error of the scaled matrix).
 double prep4_lt_fragments(const double *L, int d, int dp, double scale, uint16_t *out_bits) {
   _Float16 *out = reinterpret_cast<_Float16 *>(out_bits);
-  const int ns = p4_ns(dp), ne = p4_ne(dp), nlt = p4_nlt(dp);
+  const int ns = prep4_ns(dp), ne = prep4_ne(dp), nlt = prep4_nlt(dp);
   double e2 = 0.0;
   size_t f = 0;
   for (int t = 0; t < ne; ++t)
@@ -512,13 +452,13 @@ double prep4_lt_fragments(const double *L, int d, int dp, double scale, uint16_t
 // fragments of (s_T T)^T with the rows in filter-column order: tile t, k-step s; lane (i, hh) holds T[16 s + 8 hh + j][col(t, i)]
 double prep4_t_fragments(const double *T, int d, int dp, double scale, uint16_t *out_bits) {
   _Float16 *out = reinterpret_cast<_Float16 *>(out_bits);
-  const int ns = p4_ns(dp), nt = p4_nt(dp);
+  const int ns = prep4_ns(dp), nt = prep4_nt(dp);
   double e2 = 0.0;
   for (int t = 0; t < nt; ++t)
     for (int s = 0; s < ns; ++s)
       for (int l = 0; l < 64; ++l)
         for (int j = 0; j < 8; ++j) {
-          const int col = p4_column(t, l & 31), k = 16 * s + 8 * (l >> 5) + j;
+          const int col = prep4_column(t, l & 31), k = 16 * s + 8 * (l >> 5) + j;
           const double v = (col < d && k < d) ? T[(size_t)k * d + col] : 0.0;
           _Float16 hi, lo;
           const double e = split16(v, scale, &hi, &lo);

@@ -2,27 +2,9 @@
 // exact side kernels that go with it (ellipsoid band, exact whitening of the few queries that need it)
 #pragma once
 #include "mlf_common.hpp"
+#include "mlf_prep4_dev.hpp"   // Prep4Consts, the shape of an instance
 
 namespace mlf {
-
-// Host-side constants of one region for k_prep4 (error model: header of mlf_prep4.hip), all in binary32 and rounded
-// in the safe direction; the scales are powers of two.
-struct Prep4Consts {
-  float g_chain;     // g: relative error of one split-binary16 chain (accumulation + operand splitting + dropped product)
-  float y0n;         // >= | L^T (c_lay - c_ell) |
-  float lf;          // >= | L |_F                (A = L L^T, the ellipsoid matrix)
-  float el;          // >= | E_L |_F / s_L        (representation error of the two binary16 pieces of s_L L)
-  float l_abs;       // >= | L |_F sqrt(K) 2^-25 / s_x     (binary16 subnormals of the proposal operand)
-  float s0n;         // >= | c_lay - c_ell |
-  float eps_scale;   // >= 2^-34 | A |_F          (reference rounding + factorisation, as in k_prep3)
-  float enl_lo, enl_hi;   // enlarge rounded down / up
-  float zt;          // >= g | T |_F + | E_T |_F / s_T     (zeta per unit sigma |delta|)
-  float zt_abs;      // >= | T |_F sqrt(K) 2^-25 / s_x     (zeta's absolute term per unit sigma)
-  float s_x;         // scale of the centred proposal
-  float inv_sx;      // 1 / s_x
-  float inv_sl_sx;   // 1 / (s_L s_x): accumulator of the ellipsoid chain -> y
-  float inv_st_sx;   // 1 / (s_T s_x): accumulator of the whitening chain -> T^T delta
-};
 
 struct Prep4Args {
   const double *pts;      // (np, d) row-major proposals, 16-byte aligned

@@ -17,7 +17,7 @@ int filter_prepare_refs(FilterCtx &f, const double *refR, int n, int d, int dp, 
                         bool host_sync, bool mask_mode) {
   f.refs_ready = false;
   f.wide = false;
-  const int ks = (dp + 6 + 15) / 16;   // filter dimensionality = padded DP (zero columns are harmless)
+  const int ks = prep4_ks(dp);   // filter dimensionality = padded DP (zero columns are harmless)
   // above 9 k-steps (128 dimensions): the run-time-dimension operands of mlf_wide_filter.hip, which serve mask mode only
   const bool wide = ks > 9;
   if ((wide && (!mask_mode || ks > kWideFilterMaxKs)) || n < 1 ||

@@ -35,23 +35,16 @@
 #include "mlf_dpp_dev.hpp"
 #include "mlf_filter_dev.hpp"
 #include "mlf_recheck_dev.hpp"
+#include "mlf_sweep_dev.hpp"
 
 #include <math.h>
 
 namespace mlf {
 
 typedef __attribute__((ext_vector_type(8))) _Float16 half8;
-typedef __attribute__((ext_vector_type(16))) float float16v;
 typedef __attribute__((ext_vector_type(4))) unsigned uint4v;
 
 namespace {
-
-__device__ __forceinline__ int min3i(int a, int b, int c) {
-  const int m = a < b ? a : b;
-  return m < c ? m : c;
-}
-
-constexpr int kPosInf = 0x7f800000;
 
 template <int KS>
 __device__ __forceinline__ void load_tile(half8 (&A)[KS], __amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
@@ -61,15 +54,6 @@ __device__ __forceinline__ void load_tile(half8 (&A)[KS], __amdgpu_buffer_rsrc_t
     c.u = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff + s * 1024, 0);
     A[s] = c.h;
   }
-}
-
-__device__ __forceinline__ int tree_min(const float16v &c, int run) {
-  const int m0 = min3i(__float_as_int(c[0]), __float_as_int(c[1]), __float_as_int(c[2]));
-  const int m1 = min3i(__float_as_int(c[3]), __float_as_int(c[4]), __float_as_int(c[5]));
-  const int m2 = min3i(__float_as_int(c[6]), __float_as_int(c[7]), __float_as_int(c[8]));
-  const int m3 = min3i(__float_as_int(c[9]), __float_as_int(c[10]), __float_as_int(c[11]));
-  const int m4 = min3i(__float_as_int(c[12]), __float_as_int(c[13]), __float_as_int(c[14]));
-  return min3i(min3i(m0, m1, m2), min3i(m3, m4, __float_as_int(c[15])), run);
 }
 
 template <int I, int NM, int NV>

@@ -18,6 +18,7 @@
 // so the accumulation model of the bound is the one of the narrow kernels with more terms (wide_thresholds below).
 #include "mlf_wide_filter.hpp"
 #include "mlf_filter_dev.hpp"
+#include "mlf_sweep_dev.hpp"
 
 #include <math.h>
 
@@ -26,7 +27,6 @@ namespace mlf {
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) _Float16 half8;
-typedef __attribute__((ext_vector_type(16))) float float16v;
 
 struct half8pack {
   half_t h[8];
@@ -297,15 +297,10 @@ __global__ __launch_bounds__(256) void k_wide_quant_queries(WideQuantArgs a) {
 // at one moment would queue on one L2 channel).  Per tile: the k-loop in chunks of kWideKC k-steps -- the chunk's four 1 KiB
 // fragment loads of the live tile are in flight while the chunk before it feeds G matrix instructions per k-step from LDS
 // (ds_read_b128, lane-consecutive: conflict free) into G accumulator blocks -- then 8 integer min3 per group on the bit
-// patterns (mlf_filter.hip: min3i).  The waves' minima meet in LDS (atomicMin on the patterns: a negative Dt has a negative
+// patterns (mlf_sweep_dev.hpp: tree_min).  The waves' minima meet in LDS (atomicMin on the patterns: a negative Dt has a negative
 // pattern and wins, which is all the tests below need -- T_lo is never negative and finite).
 constexpr int kWideSweepThreads = 512;
 constexpr int kWideKC = 4;
-
-__device__ __forceinline__ int min3i(int a, int b, int c) {
-  const int m = a < b ? a : b;
-  return m < c ? m : c;
-}
 
 template <int G>
 __global__ __launch_bounds__(kWideSweepThreads) void k_wide_sweep(WideSweepArgs a) {
@@ -365,14 +360,7 @@ __global__ __launch_bounds__(kWideSweepThreads) void k_wide_sweep(WideSweepArgs 
     // all 16 values of a lane belong to ONE query (column = lane & 31) and 16 live points
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      const float16v &c = acc[g];
-      const int m0 = min3i(__float_as_int(c[0]), __float_as_int(c[1]), __float_as_int(c[2]));
-      const int m1 = min3i(__float_as_int(c[3]), __float_as_int(c[4]), __float_as_int(c[5]));
-      const int m2 = min3i(__float_as_int(c[6]), __float_as_int(c[7]), __float_as_int(c[8]));
-      const int m3 = min3i(__float_as_int(c[9]), __float_as_int(c[10]), __float_as_int(c[11]));
-      const int m4 = min3i(__float_as_int(c[12]), __float_as_int(c[13]), __float_as_int(c[14]));
-      const int m = min3i(min3i(m0, m1, m2), min3i(m3, m4, __float_as_int(c[15])), vmin[g]);
-      vmin[g] = m;
+      vmin[g] = tree_min(acc[g], vmin[g]);
     }
   }
 #pragma unroll
