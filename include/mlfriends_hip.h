@@ -717,6 +717,32 @@ int mlf_usermodel_destroy(mlf_usermodel *model);
 int mlf_usermodel_eval(mlf_usermodel *model, const double *u, size_t n, double *p_out, double *L_out);
 int mlf_usermodel_eval_dev(mlf_usermodel *model, const double *d_u, size_t n, const uint8_t *d_member, double *d_p,
                            double *d_L, void *stream);
+/* Covariance models: a Gaussian likelihood with a dense covariance that depends on the parameters,
+ *   L(p) = -1/2 r^T K^-1 r - 1/2 ln det K - (ncov/2) ln 2 pi,
+ * one workgroup of 256 threads per row factorising K in LDS (csrc/mlf_user_cov.hpp states the kernel and the arithmetic contract:
+ * the order of every rounded operation, the failure rule, the skipped rows).  The source defines, instead of mlf_user_loglike,
+ *   __device__ double mlf_user_cov(const double *p, int d, const double *aux, long long naux, int i, int j);   // 0 <= j <= i < ncov
+ *   __device__ double mlf_user_resid(const double *p, int d, const double *aux, long long naux, int i);        // 0 <= i < ncov
+ * The form is not one of the numbered variants above and has no row in their table: it is compiled and loaded by its own two
+ * entries, which take `gated` as a flag, and ncov is a constant of the program (-DMLF_USER_NCOV).
+ *   mlf_covmodel_lds_bytes   bytes of static LDS of the program at ncov (0 for an ncov that is no program); the launch adds the
+ *                     row's u and p (16 d bytes with a transform, else 8 d) and the sum must not exceed 163840.
+ *   mlf_covmodel_compile     as mlf_usermodel_compile; gated != 0: the program with the t-region gate (entry
+ *                     mlf_user_rows_cov_tregion, else mlf_user_rows_cov).  MLF_E_BADARG for an ncov above the LDS cap.
+ *   mlf_covmodel_create      yields an ordinary mlf_usermodel: mlf_usermodel_eval / _eval_dev, the refills and the walker entries
+ *                     run it as any handle (a gated one in a refill with a t-region only); mlf_usermodel_destroy frees it.  gated and
+ *                     ncov must be those of the compile (MLF_E_BADARG otherwise: the entry's name and the kernel's static LDS say).
+ *   mlf_covmodel_factor      n host rows u (cube rows for a handle with a transform, else parameters) -> tri_out, n rows of
+ *                     (ncov + 1)(ncov + 2) / 2 doubles: the packed lower triangle of the augmented factor, element (i, j) at
+ *                     i (i + 1) / 2 + j, rows 0 .. ncov-1 the Cholesky factor, row ncov z = Lfac^-1 r (its last entry unused, 0);
+ *                     NaN throughout for a row whose factorisation failed; L_out the n likelihoods.  MLF_E_STATE for a handle that
+ *                     is no ungated covariance model. */
+int mlf_covmodel_lds_bytes(int ncov);
+int mlf_covmodel_compile(const char *source, const char *include_dir, int has_transform, int gated, int ncov, void *code_out,
+                         size_t code_cap, size_t *code_size, char *log, size_t log_cap);
+int mlf_covmodel_create(const void *code, size_t nbytes, size_t d, int has_transform, int gated, int ncov, const double *aux,
+                        size_t naux, mlf_usermodel **out);
+int mlf_covmodel_factor(mlf_usermodel *model, const double *u, size_t n, double *tri_out, double *L_out);
 int mlf_region_refill_user(mlf_region *r, int method, size_t nsamples, uint64_t seed, uint64_t offset, double Lmin,
                            mlf_usermodel *model, double *out_u, double *out_p, double *out_L, size_t capacity,
                            size_t *nevaluated, size_t *nkept, uint64_t *next_offset);

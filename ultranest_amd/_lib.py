@@ -150,6 +150,10 @@ SIGNATURES = {
     "mlf_usermodel_gate_derived_lds_bytes": [_sz, _sz, _int],
     "mlf_region_refill_user_derived_gated": [_vp, _int, _sz, ctypes.c_uint64, ctypes.c_uint64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
                                              _vp, _vp],
+    "mlf_covmodel_lds_bytes": [_int],
+    "mlf_covmodel_compile": [ctypes.c_char_p, ctypes.c_char_p, _int, _int, _int, _vp, _sz, _vp, _vp, _sz],
+    "mlf_covmodel_create": [_vp, _sz, _sz, _int, _int, _int, _vp, _sz, _vp],
+    "mlf_covmodel_factor": [_vp, _vp, _sz, _vp, _vp],
     "mlf_walkers_finish_user": [_vp, _dbl, _vp, ctypes.c_int64, _vp],
     "mlf_walkers_step_user": [_vp, _dbl, _dbl, _int, _dbl, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp],
     "mlf_rwalk_create": [_vp, _sz, _sz, _sz],

@@ -62,7 +62,8 @@ struct TregionGate {
 };
 bool usermodel_gated(const mlf_usermodel *m);   // loaded as the MLF_USERMODEL_TREGION variant: launches with a gate only
 int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
-                   hipStream_t s, const TregionGate *gate = nullptr);
+                   hipStream_t s, const TregionGate *gate = nullptr, double *tri = nullptr);
+// (tri: a covariance model's rows of augmented factors, mlf_user_cov.hpp; NULL on every route, set by mlf_covmodel_factor alone)
 // a derive handle (MLF_USERMODEL_DERIVED): its number of derived columns (0 for every other handle) and one launch of its
 // mlf_user_derive_rows kernel on `s`: p (n, d) -> out (n, d + nderived), which must not overlap
 int usermodel_nderived(const mlf_usermodel *m);

@@ -1,5 +1,5 @@
 // mlf_user.hip -- user models (include/mlfriends_hip.h, section "user models"): a likelihood and prior transform written
-// as HIP device functions, compiled at run time by hiprtc around mlf_user_rows.hpp, loaded as a module on the library's
+// as HIP device functions, compiled at run time by hiprtc around mlf_user_rows.hpp (a covariance model: mlf_user_cov.hpp), loaded as a module on the library's
 // device and launched on the library's stream (ordered with the kernels around it: the refill and walker routes of
 // mlf_region_sample.hip / mlf_walk_api.hip call usermodel_rows between their own launches).
 //
@@ -20,6 +20,8 @@
 #include "mlf_ctx.hpp"
 #define MLF_USER_ROWS_HOST
 #include "mlf_user_rows.hpp"
+#define MLF_USER_COV_HOST
+#include "mlf_user_cov.hpp"
 
 using namespace mlf;
 
@@ -36,6 +38,10 @@ struct Variant {
                         // takes (nq, q_scratch) behind the gate's five; such a handle runs in mlf_region_refill_user_derived_gated only
   const char *compile_entry, *create_entry;   // the exported entries that accept the variant
   unsigned (*lds_bytes)(int d, int nq, bool p_buffer);   // dynamic LDS of a launch (0: the kernel's direct form)
+  unsigned threads;     // threads per workgroup
+  bool row_per_group;   // one workgroup per row (else one thread per row, `threads` rows per workgroup)
+  bool nterms_arg;      // the kernel takes `long long nterms` behind the first eight parameters
+  bool tri_arg;         // the kernel takes `double *tri` behind the first eight parameters (mlf_user_cov.hpp)
 };
 
 unsigned lds_rows(int d, int, bool p_buffer) { return mlf_user_rows_lds_bytes(d, p_buffer); }
@@ -50,23 +56,30 @@ constexpr char COMPILE_VARIANT[] = "mlf_usermodel_compile_variant", COMPILE_SUMS
                CREATE_SUM[] = "mlf_usermodel_create_sum", CREATE_DERIVED[] = "mlf_usermodel_create_derived",
                CREATE_GATE_DERIVED[] = "mlf_usermodel_create_gate_derived";
 constexpr Variant kVariants[] = {
-    //                                       gated summed multi derive gate_derived
-    {"mlf_user_rows",                        false, false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows},
-    {"mlf_user_rows_tregion",                true,  false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows},
-    {"mlf_user_rows_sum",                    false, true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum},
-    {"mlf_user_rows_sum_tregion",            true,  true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum},
-    {"mlf_user_rows_sums",                   false, true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum},
-    {"mlf_user_rows_sums_tregion",           true,  true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum},
-    {"mlf_user_derive_rows",                 false, false, false, true,  false, COMPILE_VARIANT, CREATE_DERIVED, lds_derive},
-    {"mlf_user_rows_tregion_derived",        true,  false, false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_gate_derived},
-    {"mlf_user_rows_sum_tregion_derived",    true,  true,  false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived},
-    {"mlf_user_rows_sums_tregion_derived",   true,  true,  true,  false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived},
+    //                                       gated summed multi derive gate_derived ... threads row_per_group nterms_arg tri_arg
+    {"mlf_user_rows",                        false, false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows, 64, false, false, false},
+    {"mlf_user_rows_tregion",                true,  false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows, 64, false, false, false},
+    {"mlf_user_rows_sum",                    false, true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum, 64, true, true, false},
+    {"mlf_user_rows_sum_tregion",            true,  true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum, 64, true, true, false},
+    {"mlf_user_rows_sums",                   false, true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum, 64, true, true, false},
+    {"mlf_user_rows_sums_tregion",           true,  true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum, 64, true, true, false},
+    {"mlf_user_derive_rows",                 false, false, false, true,  false, COMPILE_VARIANT, CREATE_DERIVED, lds_derive, 64, false, false, false},
+    {"mlf_user_rows_tregion_derived",        true,  false, false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_gate_derived, 64, false, false, false},
+    {"mlf_user_rows_sum_tregion_derived",    true,  true,  false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived, 64, true, true, false},
+    {"mlf_user_rows_sums_tregion_derived",   true,  true,  true,  false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived, 64, true, true, false},
 };
 static_assert(MLF_USERMODEL_DEFAULT == 0 && MLF_USERMODEL_TREGION == 1 && MLF_USERMODEL_SUM == 2 && MLF_USERMODEL_SUM_TREGION == 3 &&
                   MLF_USERMODEL_SUMS == 4 && MLF_USERMODEL_SUMS_TREGION == 5 && MLF_USERMODEL_DERIVED == 6 &&
                   MLF_USERMODEL_TREGION_DERIVED == 7 && MLF_USERMODEL_SUM_TREGION_DERIVED == 8 &&
                   MLF_USERMODEL_SUMS_TREGION_DERIVED == 9 && sizeof(kVariants) / sizeof(kVariants[0]) == 10,
               "kVariants is indexed by the MLF_USERMODEL_* numbers");
+
+// The covariance form (mlf_user_cov.hpp): not numbered, reached through mlf_covmodel_compile / _create alone; indexed by `gated`.
+constexpr char COMPILE_COV[] = "mlf_covmodel_compile", CREATE_COV[] = "mlf_covmodel_create";
+constexpr Variant kCovVariants[] = {
+    {"mlf_user_rows_cov",         false, false, false, false, false, COMPILE_COV, CREATE_COV, lds_sum, MLF_USER_COV_THREADS, true, false, true},
+    {"mlf_user_rows_cov_tregion", true,  false, false, false, false, COMPILE_COV, CREATE_COV, lds_sum, MLF_USER_COV_THREADS, true, false, true},
+};
 
 }  // namespace
 
@@ -78,6 +91,8 @@ struct mlf_usermodel {
   bool has_transform = false;
   long long nterms = 0;   // of a summed variant
   int nderived = 0;       // of the derive variant and the gate_derived ones
+  int ncov = 0;           // of a covariance model: the order of its matrix (a constant of its program)
+  DevBuf htri;            // staging of mlf_covmodel_factor
   long long naux = 0;
   DevBuf aux;
   DevBuf hu, hp, hL;   // staging of mlf_usermodel_eval (host arrays)
@@ -156,7 +171,7 @@ int usermodel_nderived(const mlf_usermodel *m) { return m->v->derive ? m->nderiv
 int usermodel_gate_nderived(const mlf_usermodel *m) { return m->v->gate_derived ? m->nderived : 0; }
 
 int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const uint8_t *member, double *p, double *L,
-                   hipStream_t s, const TregionGate *gate) {
+                   hipStream_t s, const TregionGate *gate, double *tri) {
   const Variant &v = *m->v;
   const int gate_nq = usermodel_gate_nderived(m);
   if (v.derive) return fail_arg(MLF_E_STATE, "a derive handle (mlf_usermodel_create_derived) evaluates nothing: it runs in the derive entries only");
@@ -171,8 +186,9 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
                                          : "a t-region over d + nderived columns needs a user model loaded as a _TREGION_DERIVED "
                                            "variant (mlf_usermodel_create_gate_derived)");
   if (n <= 0) return 0;
-  // default form: one thread per row, 64 rows per workgroup; summed form: one wave (= one workgroup) per row
-  const long long blocks = v.summed ? n : (n + 63) / 64;
+  if (tri != nullptr && !v.tri_arg) return fail_arg(MLF_E_STATE, "not a covariance model (mlf_covmodel_create): it has no factor");
+  // one workgroup per row (summed forms: a wave; covariance form: four), else one thread per row
+  const long long blocks = v.row_per_group ? n : (n + v.threads - 1) / v.threads;
   if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
   const unsigned lds = v.lds_bytes(m->d, gate_nq, p != nullptr && m->has_transform);
   // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
@@ -194,11 +210,13 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
   }
   int g_nq = gate_nq;
   double *g_scratch = gate ? gate->q_scratch : nullptr;
-  // the first eight, nterms in the ninth place of a summed model, the gate's five behind them when gated, (nq, q_scratch) behind
-  // those in a _TREGION_DERIVED variant
+  // the first eight, nterms in the ninth place of a summed model (tri of a covariance model), the gate's five behind them when
+  // gated, (nq, q_scratch) behind those in a _TREGION_DERIVED variant
   void *args[16] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
   int na = 8;
-  if (v.summed) args[na++] = &a_nterms;
+  if (v.nterms_arg) args[na++] = &a_nterms;
+  double *a_tri = tri;
+  if (v.tri_arg) args[na++] = &a_tri;
   if (gate) {
     void *g[] = {&g_A, &g_ctr, &g_fixed, &g_enlarge, &g_member2};
     for (void *x : g) args[na++] = x;
@@ -207,7 +225,7 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
     args[na++] = &g_nq;
     args[na++] = &g_scratch;
   }
-  CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
+  CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, v.threads, 1, 1, lds, s, args, nullptr));
   return 0;
 }
 
@@ -274,7 +292,7 @@ int check_create_args(const void *code, size_t nbytes, size_t d, size_t nderived
 
 // loads the code object as the variant `v` (arguments checked by the caller)
 int load_model(const void *code, size_t d, int has_transform, const Variant &v, size_t nterms, size_t nderived, const double *aux,
-               size_t naux, mlf_usermodel **out) {
+               size_t naux, mlf_usermodel **out, int ncov = 0) {
   if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   mlf_usermodel *m = new mlf_usermodel();
@@ -283,6 +301,7 @@ int load_model(const void *code, size_t d, int has_transform, const Variant &v, 
   m->has_transform = has_transform != 0;
   m->nterms = (long long)nterms;
   m->nderived = (int)nderived;
+  m->ncov = ncov;
   m->naux = (long long)naux;
   hipError_t e = hipModuleLoadData(&m->module, code);
   if (e == hipSuccess && hipModuleGetFunction(&m->fn, m->module, v.kernel) != hipSuccess) {
@@ -306,8 +325,9 @@ int load_model(const void *code, size_t d, int has_transform, const Variant &v, 
 }
 
 // hiprtc on `source` + the wrapper header as the variant `v` (nsums checked by the caller: 0 unless v.multi)
+// ncov: the order of a covariance form's matrix (0: every other variant), which compiles mlf_user_cov.hpp instead
 int compile_program(const char *source, const char *include_dir, int has_transform, const Variant &v, int nsums, void *code_out,
-                    size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
+                    size_t code_cap, size_t *code_size, char *log, size_t log_cap, int ncov = 0) {
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
@@ -316,12 +336,13 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
     return fail_arg(MLF_E_COMPILE, g_rtc.why.c_str());
   }
   const Rtc &r = g_rtc;
-  const std::string src = std::string(source) + "\n#include \"mlf_user_rows.hpp\"\n";
+  const std::string src = std::string(source) + (v.tri_arg ? "\n#include \"mlf_user_cov.hpp\"\n" : "\n#include \"mlf_user_rows.hpp\"\n");
   const std::string inc = std::string("-I") + include_dir;
   const std::string sums = "-DMLF_USER_NSUMS=" + std::to_string(nsums);
+  const std::string cov = "-DMLF_USER_NCOV=" + std::to_string(ncov);
   // every program gets the first eight; a variant's own options follow (so the other variants' programs are compiled as they were
   // before it existed; the derive program never calls the transform)
-  const char *opts[10] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
+  const char *opts[12] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
                           has_transform && !v.derive ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
                           v.gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
                           v.summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0"};
@@ -329,6 +350,7 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
   if (v.multi) opts[nopts++] = sums.c_str();
   if (v.derive) opts[nopts++] = "-DMLF_USER_DERIVED=1";
   if (v.gate_derived) opts[nopts++] = "-DMLF_USER_GATE_DERIVED=1";
+  if (v.tri_arg) opts[nopts++] = cov.c_str();
   hiprtcProgram prog = nullptr;
   hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
   if (res != HIPRTC_SUCCESS) {
@@ -450,6 +472,77 @@ int mlf_usermodel_derive_lds_bytes(size_t d, size_t nderived) {
   return (int)mlf_user_rows_derive_lds_bytes((int)d, (int)nderived);   // (at most MLF_USER_ROWS_LDS_BUDGET)
 }
 
+int mlf_covmodel_lds_bytes(int ncov) {
+  // (0: no such program.  The bound keeps the arithmetic below in range; the Python constructor holds static + dynamic to the CU's)
+  if (ncov < 1 || ncov > 1024) return 0;
+  return (int)mlf_user_rows_cov_lds_bytes(ncov);
+}
+
+namespace {
+int check_ncov(int ncov) {
+  if (ncov < 1 || ncov > 1024 || mlf_user_rows_cov_lds_bytes(ncov) > MLF_USER_COV_LDS_CAP)
+    return fail_arg(MLF_E_BADARG, "ncov: the augmented triangle of an ncov x ncov covariance must fit the LDS of one CU "
+                                  "(mlf_covmodel_lds_bytes(ncov) <= 163840)");
+  return 0;
+}
+}  // namespace
+
+int mlf_covmodel_compile(const char *source, const char *include_dir, int has_transform, int gated, int ncov, void *code_out,
+                         size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
+  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (int rc = check_ncov(ncov)) return rc;
+  return compile_program(source, include_dir, has_transform, kCovVariants[gated ? 1 : 0], 0, code_out, code_cap, code_size, log,
+                         log_cap, ncov);
+}
+
+int mlf_covmodel_create(const void *code, size_t nbytes, size_t d, int has_transform, int gated, int ncov, const double *aux,
+                        size_t naux, mlf_usermodel **out) {
+  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
+  *out = nullptr;
+  if (int rc = check_ncov(ncov)) return rc;
+  if (int rc = check_create_args(code, nbytes, d, 0)) return rc;
+  if ((size_t)mlf_user_rows_cov_lds_bytes(ncov) + 2 * d * sizeof(double) > MLF_USER_COV_LDS_CAP)
+    return fail_arg(MLF_E_BADARG, "ncov and d: the triangle and the row's u and p exceed the LDS of one CU");
+  if (int rc = load_model(code, d, has_transform, kCovVariants[gated ? 1 : 0], 0, 0, aux, naux, out, ncov)) return rc;
+  // ncov sizes the factor rows of mlf_covmodel_factor: it must be the program's own constant, which the kernel's static LDS names
+  // (mlf_user_rows_cov_lds_bytes grows strictly with n)
+  int shared = 0;
+  const hipError_t e = hipFuncGetAttribute(&shared, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, (*out)->fn);
+  if (e != hipSuccess || shared != (int)mlf_user_rows_cov_lds_bytes(ncov)) {
+    (void)hipGetLastError();
+    (void)mlf_usermodel_destroy(*out);
+    *out = nullptr;
+    if (e != hipSuccess) return fail_hip(e, "mlf_covmodel_create", "mlf_user.hip", __LINE__);
+    return fail_arg(MLF_E_BADARG, "ncov is not the ncov the code object was compiled with");
+  }
+  return 0;
+}
+
+int mlf_covmodel_factor(mlf_usermodel *m, const double *u, size_t n, double *tri_out, double *L_out) {
+  if (!m || !u || !tri_out || !L_out) return fail_arg(MLF_E_BADARG, "null pointer");
+  if (!m->v->tri_arg) return fail_arg(MLF_E_STATE, "not a covariance model (mlf_covmodel_create): it has no factor");
+  if (m->v->gated) return fail_arg(MLF_E_STATE, "the gated program of a covariance model runs in a refill with a t-region only");
+  if (n == 0) return 0;
+  const size_t tri_doubles = mlf_user_rows_cov_tri_doubles(m->ncov);
+  if (n > 0x7fffffffull || n > 0x7fffffffffffull / (tri_doubles + (size_t)m->d)) return fail_arg(MLF_E_BADARG, "batch too large");
+  hipStream_t s = ctx_stream();
+  const size_t rows = n * (size_t)m->d * sizeof(double), tri_bytes = n * tri_doubles * sizeof(double);
+  CK(m->hu.reserve(rows));
+  if (m->has_transform) CK(m->hp.reserve(rows));
+  CK(m->hL.reserve(n * sizeof(double)));
+  CK(m->htri.reserve(tri_bytes));
+  CK(hipMemcpyAsync(m->hu.p, u, rows, hipMemcpyHostToDevice, s));
+  // (with a transform the rows are cube rows and p its output; without one they are the parameters)
+  if (int rc = usermodel_rows(m, m->hu.as<double>(), (long long)n, nullptr, m->has_transform ? m->hp.as<double>() : nullptr,
+                              m->hL.as<double>(), s, nullptr, m->htri.as<double>()))
+    return rc;
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(tri_out, m->htri.p, tri_bytes, hipMemcpyDeviceToHost, s));
+  CK(hipMemcpyAsync(L_out, m->hL.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  CK(hipStreamSynchronize(s));
+  return 0;
+}
+
 int mlf_usermodel_destroy(mlf_usermodel *m) {
   if (!m) return 0;
   // the model's last launches may still be queued (the library's stream, or a caller's stream of eval_dev)
@@ -462,6 +555,7 @@ int mlf_usermodel_destroy(mlf_usermodel *m) {
   m->hu.release();
   m->hp.release();
   m->hL.release();
+  m->htri.release();
   delete m;
   if (e != hipSuccess) return fail_hip(e, "mlf_usermodel_destroy", "mlf_user.hip", __LINE__);
   return 0;

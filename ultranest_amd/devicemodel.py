@@ -6,8 +6,8 @@ device functions, the package compiles them at run time for gfx950 (hiprtc) arou
 (``csrc/mlf_user_rows.hpp``) and hands back a pair of vectorized callbacks::
 
     model = DeviceModel(ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None,
-                        nderived=None, derived_source=None, gate_derived=False)
-    model.loglike(theta)    # (n, ndim) -> (n,)       vectorized callback, evaluated on the GPU
+                        nderived=None, derived_source=None, gate_derived=False, ncov=None)
+    model.loglike(theta)    # (n, ndim) -> (n,)      vectorized callback, evaluated on the GPU
     model.transform(u)      # (n, ndim) -> (n, ndim)  vectorized callback (identity without a transform source)
 
 (with ``nderived=Q`` the transform returns ``(n, ndim + Q)`` and the likelihood accepts either width: "Derived parameters" below)
@@ -174,11 +174,68 @@ default form reads once per 64 rows).  So: the summed form for what the populati
 the whole-refill samplers, region refills of a few thousand draws, up to about 10^4 rows per call -- and for many terms; the
 default form for batches of 10^5 rows and more, or for a likelihood of a handful of terms.
 
+Gaussian likelihoods with a dense covariance (``ncov=n``)
+---------------------------------------------------------
+A Gaussian process over a light curve or a radial-velocity series, correlated noise, a red-noise kernel plus jitter: a Gaussian
+whose covariance depends on the parameters,
+
+    L(p) = -1/2 r(p)^T K(p)^-1 r(p) - 1/2 ln det K(p) - (n/2) ln 2 pi.
+
+A row needs an n x n Cholesky factorisation, which one thread cannot hold and the summed forms cannot express (the terms are
+coupled).  With ``ncov=n`` (a Python int >= 1, at most ``max_ncov(ndim, has_transform)``) the likelihood source defines, INSTEAD
+of ``mlf_user_loglike``::
+
+    __device__ double mlf_user_cov(const double *p, int d, const double *aux, long long naux, int i, int j);   // 0 <= j <= i < n
+    __device__ double mlf_user_resid(const double *p, int d, const double *aux, long long naux, int i);        // 0 <= i < n
+
+Both are pure functions of their arguments under the contract of every user function; only the lower triangle is asked for.  One
+workgroup of 256 threads then owns one row and factorises its matrix in LDS (``csrc/mlf_user_cov.hpp``).  Transform source,
+``aux``, the callbacks, ``eval_dev``, ``device_route``, ``nderived`` / ``derived_source`` and ``priors.PriorTransform(...).model(src,
+ncov=n)`` are unchanged and every route recognises the model as it does any other; its four programs (with or without transform,
+gated or not) are compiled with ``-DMLF_USER_NCOV=n`` around that header under their own cache keys (tag ``" cov=n"``).  ``ncov``
+combines with neither ``nterms`` / ``nsums`` nor ``gate_derived`` (``ValueError``; with derived columns and a t-region the batch takes
+the host sequence, as for any model without the flag), and the ``hotstart`` device forms refuse such an inner model.
+
+``model.cov_factor(theta, with_transform=False)`` returns ``(Lfac (m, n, n), z (m, n), L (m,))`` of host rows -- the Cholesky
+factor, ``z = Lfac^-1 r`` and the likelihood -- which is what GP prediction needs.
+
+The arithmetic contract (part of the interface; it does not depend on how the threads share the work):
+
+* augmented triangle: ``A`` is the packed lower triangle of an ``(n+1) x (n+1)`` matrix, ``A_ij = cov(i, j)`` for ``j <= i < n``,
+  ``A_nj = resid(j)``, ``A_nn`` unused;
+* factor: for ``k = 0 .. n-1`` in order the pivot is ``A_kk`` after its updates, ``L_kk = sqrt(A_kk)``, ``L_ik = A_ik / L_kk`` for
+  ``k < i <= n``, and every remaining ``A_ij`` (``k < j <= i``, ``j < n``) becomes ``A_ij - L_ik * L_jk``: one multiplication and one
+  subtraction, each rounded, no fused multiply-add.  Every element receives its subtractions in ascending ``k``, so its value is
+  independent of the schedule.  Row ``n`` of the factor is ``z``;
+* sums: ``quad = sum_k z_k * z_k`` and ``h = sum_k log(L_kk)``, both sequential from 0.0 in ascending ``k`` (the logarithms may be
+  taken in parallel; the additions are one lane's);
+* likelihood: ``L = ((-0.5 * quad) - h) - (double)n * 0.91893853320467274178``;
+* failure: the first pivot in ascending ``k`` that is not ``> 0`` decides -- a NaN pivot gives ``L = NaN``, any other ``L = -inf``;
+  nothing after it is computed and ``cov_factor`` returns that row's factor as NaN;
+* skipped rows: a row outside the membership mask, or one that fails the t-region gate, calls neither function and gets
+  ``L = -inf``; its ``p`` row is treated as in the summed form;
+* independence: ``L`` does not depend on the row's position, the batch size, the mask or the route.
+
+``tests/cov_reference.py`` restates the contract in numpy; the device's factor equals it bit for bit (square root, division,
+product and difference are IEEE operations on both sides).
+
+The cap.  The packed triangle, a copy of the current column and a flag word are static LDS (``cov_lds_bytes(n)``, the library's
+``mlf_covmodel_lds_bytes``); the row's u and p are dynamic LDS as in the summed form; together at most the 163,840 bytes a
+workgroup may declare on this device.  ``max_ncov(ndim, has_transform)`` is 199 at small ``ndim`` with this layout.  Larger
+matrices need the factor in HBM with LDS panels: a later step.  Structured covariances (banded, Toeplitz, low rank plus diagonal)
+want kernels of their own.
+
+Which form.  A likelihood of independent terms is a summed model; this form is for coupled data.  Measured with
+``usermodels.gp_sqexp`` against the same model as a vectorised numpy host callback (batched ``np.linalg.cholesky``, 16 threads;
+``scripts/cov_model_bench.py``, ``profiles/cov_model_bench.json``): at 1024 rows 145 (n = 32), 321 (64), 329 (128: 0.83 against
+272 ms) and 158 (199) times faster, at 16384 rows 228, 491, 347 and 166 times; a ``PopulationSimpleSliceSampler`` device refill
+(popsize 1024, 10 steps, n = 64) takes 5.3 ms against 1594 ms through the host callback.
+
 Forms
 -----
-Which program a handle runs is one ``Form(has_transform, gated, summed, nsums, derived)``: it checks the combination, gives the
+Which program a handle runs is one ``Form(has_transform, gated, summed, nsums, derived, ncov)``: it checks the combination, gives the
 library's variant number (``Form.variant``; the table in ``include/mlfriends_hip.h`` names each variant's kernel and the entries
-that compile and load it) and the option tags of the cache key.  ``_cache_key(source, form)`` is the only key, ``compile_form``
+that compile and load it; a covariance form is no numbered variant and has its own two entries) and the option tags of the cache key.  ``_cache_key(source, form)`` is the only key, ``compile_form``
 the only caller of the library's compile entries, ``_Handle`` the only handle class, and a model keeps its handles by ``Form``.
 
 Compiling needs no GPU; code objects are cached per process, keyed by a hash of the source, the options and the
@@ -196,11 +253,15 @@ from ._lib import check, f64, ptr
 
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 HEADER = os.path.join(INCLUDE_DIR, "mlf_user_rows.hpp")
+COV_HEADER = os.path.join(INCLUDE_DIR, "mlf_user_cov.hpp")          # what a covariance program includes instead of HEADER
 GATE_HEADER = os.path.join(INCLUDE_DIR, "mlf_tregion_dev.hpp")      # included by the gated variant only
 VARIANT_DEFAULT, VARIANT_TREGION, VARIANT_SUM, VARIANT_SUM_TREGION = 0, 1, 2, 3     # MLF_USERMODEL_* of include/mlfriends_hip.h
 VARIANT_SUMS, VARIANT_SUMS_TREGION = 4, 5
 VARIANT_DERIVED = 6
 VARIANT_TREGION_DERIVED, VARIANT_SUM_TREGION_DERIVED, VARIANT_SUMS_TREGION_DERIVED = 7, 8, 9
+# the covariance form is no numbered variant of the library (its entries take `gated` as a flag): Form.variant of such a form
+VARIANT_COV, VARIANT_COV_TREGION = 16, 17
+COV_LDS_CAP = 163840                                                                # bytes of LDS a workgroup may declare (gfx950)
 MAX_SUMS = 8                                                                        # MLF_USERMODEL_MAX_SUMS
 MAX_DIM = 1024                                                                      # MLF_MAX_DIM
 # what mlf_usermodel_compile passes to hiprtc besides -I, -DMLF_USER_HAS_TRANSFORM, -DMLF_USER_TREGION, -DMLF_USER_SUM and (with
@@ -247,14 +308,33 @@ def _check_nderived(ndim, nderived, derived_source):
     return nderived
 
 
-class Form(collections.namedtuple("Form", "has_transform gated summed nsums derived")):
+def cov_lds_bytes(ncov):
+    """Static LDS of a covariance program in bytes: ``mlf_user_rows_cov_lds_bytes`` of ``csrc/mlf_user_cov.hpp`` restated (the
+    packed augmented triangle, the column vector and the flag word, rounded up to 16), so that the constructor can refuse an
+    ``ncov`` before any library call; the library exports the original as ``mlf_covmodel_lds_bytes``."""
+    doubles = (ncov + 1) * (ncov + 2) // 2 + (ncov + 1) + 1
+    return (doubles + 1) // 2 * 16
+
+
+def max_ncov(ndim, has_transform):
+    """The largest ``ncov`` a model of `ndim` parameters can have: static LDS plus the launch's dynamic rows (u, and p where a
+    transform writes one) within the 163,840 bytes a workgroup may declare.  199 at small ndim with the layout of
+    ``csrc/mlf_user_cov.hpp``; 0 where even ``ncov = 1`` does not fit."""
+    rows = (2 if has_transform else 1) * int(ndim) * 8
+    n = 0
+    while cov_lds_bytes(n + 1) + rows <= COV_LDS_CAP:
+        n += 1
+    return n
+
+
+class Form(collections.namedtuple("Form", "has_transform gated summed nsums derived ncov")):
     """Which program of a model: with its transform or the identity; gated by a t-region; the summed form, with nsums=M several
     sums; derived="derive" the derive program (none of the others apply), derived="gate" the gate over derived parameters (a gated
-    program).  The one place that maps these to a MLF_USERMODEL_* number and to the option tags of a cache key.  ValueError for a
-    combination that is no program."""
+    program); ncov=n the covariance form (neither summed nor a gate over derived parameters).  The one place that maps these to a
+    MLF_USERMODEL_* number and to the option tags of a cache key.  ValueError for a combination that is no program."""
     __slots__ = ()
 
-    def __new__(cls, has_transform, gated=False, summed=False, nsums=None, derived=None):
+    def __new__(cls, has_transform, gated=False, summed=False, nsums=None, derived=None, ncov=None):
         nsums = _check_count("nsums", nsums, "sums of the summed form", MAX_SUMS)
         if nsums is not None and not summed:
             raise ValueError("nsums needs the summed form: give nterms (the number of data terms) as well")
@@ -262,10 +342,16 @@ class Form(collections.namedtuple("Form", "has_transform gated summed nsums deri
             raise ValueError("derived=True names the gate over the derived parameters: it needs gated=True")
         if derived not in (None, "gate") and (derived != "derive" or has_transform or gated or summed):
             raise ValueError("derived is None, 'gate' or 'derive' (the derive program: no transform, gate or sum), got %r" % (derived,))
-        return super(Form, cls).__new__(cls, bool(has_transform), bool(gated), bool(summed), nsums, derived)
+        ncov = _check_count("ncov", ncov, "rows of the covariance matrix")
+        if ncov is not None and (summed or derived is not None):
+            raise ValueError("ncov (the covariance form) combines with neither nterms / nsums (the summed forms) nor a derived "
+                             "kind of program (gate_derived; the derive program is the model's own)")
+        return super(Form, cls).__new__(cls, bool(has_transform), bool(gated), bool(summed), nsums, derived, ncov)
 
     @property
     def variant(self):
+        if self.ncov is not None:
+            return VARIANT_COV_TREGION if self.gated else VARIANT_COV
         if self.derived == "derive":
             return VARIANT_DERIVED
         kind = 2 if self.nsums is not None else 1 if self.summed else 0      # default, one sum, several sums
@@ -278,7 +364,7 @@ class Form(collections.namedtuple("Form", "has_transform gated summed nsums deri
         """what the options part of a cache key says behind ``repr((COMPILE_OPTIONS, has_transform))``"""
         return ((" tregion" if self.gated else "") + (" gate_derived" if self.derived == "gate" else "") +
                 (" sum" if self.summed else "") + ("" if self.nsums is None else " sums=%d" % self.nsums) +
-                (" derived" if self.derived == "derive" else ""))
+                (" derived" if self.derived == "derive" else "") + ("" if self.ncov is None else " cov=%d" % self.ncov))
 
 
 DERIVE = Form(False, derived="derive")
@@ -291,7 +377,8 @@ def _cache_key(source, form, *flags, **more):
         form = Form(form, *flags, **more)
     h = hashlib.sha256()
     header = b""
-    for path in (HEADER, GATE_HEADER) if form.gated else (HEADER,):
+    main = HEADER if form.ncov is None else COV_HEADER      # (a covariance program includes its own header instead)
+    for path in (main, GATE_HEADER) if form.gated else (main,):
         with open(path, "rb") as fh:
             header += fh.read()
     options = repr((COMPILE_OPTIONS, form.has_transform)) + form.tags
@@ -318,7 +405,9 @@ def compile_form(source, form):
         head = (source.encode(), INCLUDE_DIR.encode(), int(form.has_transform), v)
         tail = (buf, cap, ctypes.byref(size), log, len(log))
         compile_calls += 1
-        if form.derived == "gate":
+        if form.ncov is not None:
+            rc = L.mlf_covmodel_compile(*(head[:3] + (int(form.gated), form.ncov) + tail))
+        elif form.derived == "gate":
             rc = L.mlf_usermodel_compile_gate_derived(*(head + (form.nsums or 0,) + tail))
         elif form.nsums is not None:
             rc = L.mlf_usermodel_compile_sums(*(head + (form.nsums,) + tail))
@@ -382,12 +471,15 @@ class _Handle(object):
     """One loaded program (``mlf_usermodel``) on the library's device, created through the entry that owns its form's variant.
     nterms: the summed form; derived, nderived: one of the two derived kinds (``Form``)."""
 
-    def __init__(self, code, ndim, has_transform, aux, gated=False, nterms=None, nsums=None, derived=None, nderived=None):
-        form = Form(has_transform, gated, nterms is not None, nsums, derived)
+    def __init__(self, code, ndim, has_transform, aux, gated=False, nterms=None, nsums=None, derived=None, nderived=None,
+                 ncov=None):
+        form = Form(has_transform, gated, nterms is not None, nsums, derived, ncov)
         L, h = _lib.lib(), ctypes.c_void_p()
         head = (code, len(code), int(ndim))
         tail = (ptr(aux), len(aux), ctypes.byref(h))
-        if form == DERIVE:
+        if form.ncov is not None:
+            rc = L.mlf_covmodel_create(*(head + (int(form.has_transform), int(form.gated), form.ncov) + tail))
+        elif form == DERIVE:
             rc = L.mlf_usermodel_create_derived(*(head + (int(nderived),) + tail))
         else:
             head += (int(form.has_transform), form.variant)
@@ -425,12 +517,14 @@ class DeviceModel(object):
     derived_source (``mlf_user_derived``): Q derived columns behind the parameters, ``nparams == ndim + Q``; every route keeps
     its ndim-wide rows and the derive program extends the rows that are handed out.  gate_derived=True (with nderived): a region
     refill with a t-region over all ``ndim + Q`` columns runs on the device, at the cost of ``mlf_user_derived`` on every member
-    row of such a batch (module docstring); without it such a refill returns None and the batch takes the host sequence."""
+    row of such a batch (module docstring); without it such a refill returns None and the batch takes the host sequence.
+    ncov=n: a Gaussian likelihood with a dense n x n covariance; the source defines ``mlf_user_cov`` and ``mlf_user_resid`` instead
+    and one workgroup per row factorises the matrix in LDS under the documented arithmetic contract (``cov_factor``)."""
 
     _count = 0
 
     def __init__(self, ndim, loglike_source, transform_source=None, aux=None, name=None, nterms=None, nsums=None,
-                 nderived=None, derived_source=None, gate_derived=False):
+                 nderived=None, derived_source=None, gate_derived=False, ncov=None):
         self.ndim = int(ndim)
         if self.ndim <= 0:
             raise ValueError("ndim must be positive")
@@ -442,6 +536,17 @@ class DeviceModel(object):
         self.nterms = _check_count("nterms", nterms, "terms of the summed form")
         self.nsums = Form(False, summed=self.summed, nsums=nsums).nsums
         self.has_transform = transform_source is not None
+        self.ncov = _check_count("ncov", ncov, "rows of the covariance matrix")
+        if self.ncov is not None:
+            if self.summed:
+                raise ValueError("ncov (the covariance form) does not combine with nterms / nsums (the summed forms)")
+            if self.gate_derived:
+                raise ValueError("gate_derived has no covariance form (ncov): without the flag a refill with a t-region over "
+                                 "derived columns takes the host sequence")
+            most = max_ncov(self.ndim, self.has_transform)
+            if self.ncov > most:
+                raise ValueError("ncov = %d: the factor must fit the LDS of one CU, at most ncov = %d for ndim = %d %s a transform "
+                                 "(max_ncov)" % (self.ncov, most, self.ndim, "with" if self.has_transform else "without"))
         self.source = loglike_source if transform_source is None else loglike_source + "\n" + transform_source
         self.aux = np.empty(0) if aux is None else f64(np.ravel(aux)).copy()
         DeviceModel._count += 1
@@ -464,7 +569,7 @@ class DeviceModel(object):
         """(remembered: every route asks for its handle once per device call)"""
         key = (tr, gated, derived)
         if key not in self._forms:
-            self._forms[key] = DERIVE if derived == "derive" else Form(tr, gated, self.summed, self.nsums, derived)
+            self._forms[key] = DERIVE if derived == "derive" else Form(tr, gated, self.summed, self.nsums, derived, self.ncov)
         return self._forms[key]
 
     def _compile(self, tr, gated, derived=None):
@@ -500,7 +605,7 @@ class DeviceModel(object):
             code = {self._form(self.has_transform, False): self.code, DERIVE: self.derive_code}.get(form)
             # (a count that is not the form's stays out of the call)
             counts = dict(nterms=self.nterms if form.summed else None, nsums=form.nsums, derived=form.derived,
-                          nderived=self.nderived if form.derived else None)
+                          nderived=self.nderived if form.derived else None, ncov=form.ncov)
             h = self._handles[form] = _Handle(code or self._compile(tr, gated, derived), self.ndim, tr, self.aux, gated=gated,
                                               **{k: v for k, v in counts.items() if v is not None})
         return h.handle
@@ -532,6 +637,25 @@ class DeviceModel(object):
         if x.shape[0]:
             check(_lib.lib().mlf_usermodel_eval(self.handle(), ptr(x), x.shape[0], ptr(out), None))
         return out if self.nderived is None else self.derive(out)
+
+    def cov_factor(self, theta, with_transform=False):
+        """The factorisation behind the likelihood of a covariance model (``ncov=n``), for GP prediction: host rows ``(m, ndim)``
+        -- parameters, or cube rows with ``with_transform=True`` -- give ``(Lfac (m, n, n), z (m, n), L (m,))``: the lower
+        triangular Cholesky factor of K (zeros above the diagonal), ``z = Lfac^-1 r`` and the likelihood, exactly the values the
+        kernel computed (module docstring, "The arithmetic contract").  A row whose factorisation failed has NaN throughout
+        ``Lfac`` and ``z``."""
+        if self.ncov is None:
+            raise ValueError("%s is no covariance model (ncov)" % self.name)
+        x = self._rows(theta)
+        n, m = self.ncov, x.shape[0]
+        tri = np.empty((m, (n + 1) * (n + 2) // 2))
+        out = np.empty(m)
+        if m:
+            check(_lib.lib().mlf_covmodel_factor(self.handle(bool(with_transform)), ptr(x), m, ptr(tri), ptr(out)))
+        rows, cols = np.tril_indices(n + 1)      # row-major over the lower triangle: the packed order
+        full = np.zeros((m, n + 1, n + 1))
+        full[:, rows, cols] = tri
+        return np.ascontiguousarray(full[:, :n, :n]), np.ascontiguousarray(full[:, n, :n]), out
 
     def derive(self, p):
         """Host rows ``(n, ndim)`` of parameters -> ``(n, ndim + nderived)``: ``[p | q]`` with q from ``mlf_user_derived``."""

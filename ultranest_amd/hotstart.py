@@ -63,6 +63,9 @@ Three consequences of building the deformation into an ordinary model, for both 
     ``DeviceModel`` pair raises ``ValueError`` naming (a) and (b): they need a d x d product per row in one thread, and rows
     that stay ``ndim`` wide.
 
+A covariance model (``DeviceModel(..., ncov=n)``) has no device form under (a) or (b): its likelihood is not a function the
+wrappers can call from one thread.  Both raise ``ValueError`` naming the host form (host callbacks around the model's own).
+
 (d) ``from_results(model, results)`` builds (a) from a results dict (``weighted_samples``: ``upoints`` and ``weights``).
 """
 import math
@@ -278,7 +281,14 @@ def independent_tail(ctr, err, w, lo, c, consts):
     return np.concatenate([rec.ravel(), [consts[6], float(d)]])
 
 
+def _refuse_cov(name, model):
+    if getattr(model, "ncov", None) is not None:
+        raise ValueError("%s has no device form over a covariance model (ncov: %s): pass host callbacks for the host form, "
+                         "e.g. ``lambda x: model.loglike(x)`` and ``lambda u: model.transform(u)``" % (name, model.name))
+
+
 def _independent_device(model, with_transform, ctr, err, df):
+    _refuse_cov("get_extended_auxiliary_independent_problem", model)
     d = model.ndim
     if len(ctr) != d:
         raise ValueError("ctr has %d entries, the model %s has %d parameters" % (len(ctr), model.name, d))
@@ -454,6 +464,7 @@ def _check_samples(upoints, uweights):
 
 
 def _contbox_device(model, with_transform, ulos, uhis, uinterpspace):
+    _refuse_cov("get_auxiliary_contbox_parameterization", model)
     d = model.ndim
     if ulos.shape[1] != d:
         raise ValueError("upoints has %d columns, the model %s has %d parameters" % (ulos.shape[1], model.name, d))

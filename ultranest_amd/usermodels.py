@@ -34,6 +34,14 @@ Likelihoods of several sums and a final function (``DeviceModel(..., nterms=K, n
   staircase3_sum  M = 3: a = fabs(p[k % d] - c_k) on three scales, terms -floor(a * 8), floor(a * 4), -floor(a * 2): small
                   integers, so every partial sum is exact in any order; L = s0 - s1 * s1 / (1.0 - s2) with s2 <= 0 (+ - * /
                   only, the denominator is at least 1), so the two forms agree bit for bit
+
+Gaussian likelihoods with a dense covariance (``DeviceModel(..., ncov=n)``: one workgroup per row factorises the matrix in LDS):
+
+  gp_sqexp        a Gaussian process over ndata points: aux = inputs x_i, then data y_i; parameters ln amplitude, ln length scale,
+                  ln jitter, mean; K_ij = a^2 exp(-(x_i - x_j)^2 / (2 l^2)) + delta_ij s^2, r_i = y_i - mean; ``affine=True`` puts
+                  a uniform prior box on the four (GP_PRIOR_LO, GP_PRIOR_WIDTH)
+  gp_sqexp_twin   the same arithmetic in the same order (the contract of csrc/mlf_user_cov.hpp) as a default-form
+                  ``mlf_user_loglike`` over a private array, ndata <= 12: the two agree bit for bit on every route
 """
 import numpy as np
 
@@ -369,3 +377,89 @@ def staircase3_sum(ndim, ndata, seed=1, affine=False):
 def staircase3_twin(ndim, ndata, seed=1, affine=False):
     return _two_multisum_forms(STAIRCASE3_TERMS, "mlf_staircase3", "MLF_STAIRCASE3_K", 3, ndim, ndata,
                                staircase_data(ndim, ndata, seed, affine), affine, False, "staircase3")
+
+
+# ---- Gaussian likelihoods with a dense covariance (``DeviceModel(..., ncov=n)``: one workgroup per row) ----------------------------
+# gp_sqexp: a Gaussian process with a squared-exponential kernel plus jitter over ndata points.  aux = inputs x_i, then data y_i;
+# parameters ln amplitude, ln length scale, ln jitter, mean; K_ij = a^2 exp(-(x_i - x_j)^2 / (2 l^2)) + delta_ij s^2, r_i = y_i - mean.
+# Each entry recomputes a, l, s from p (pure functions of their arguments, as the contract asks).
+
+GP_SQEXP = r"""
+#define MLF_GP_N %d
+__device__ inline double mlf_gp_cov(const double *p, const double *aux, int i, int j) {
+  const double a = exp(p[0]), l = exp(p[1]);
+  const double dx = aux[i] - aux[j];
+  double v = (a * a) * exp(-(dx * dx) / (2.0 * (l * l)));
+  if (i == j) {
+    const double s = exp(p[2]);
+    v = v + s * s;
+  }
+  return v;
+}
+__device__ inline double mlf_gp_resid(const double *p, const double *aux, int i) { return aux[MLF_GP_N + i] - p[3]; }
+"""
+
+GP_COV_LOGLIKE = r"""
+__device__ double mlf_user_cov(const double *p, int d, const double *aux, long long naux, int i, int j) { return mlf_gp_cov(p, aux, i, j); }
+__device__ double mlf_user_resid(const double *p, int d, const double *aux, long long naux, int i) { return mlf_gp_resid(p, aux, i); }
+"""
+
+# the arithmetic contract of csrc/mlf_user_cov.hpp in one thread, over a private array
+GP_TWIN_LOGLIKE = r"""
+__device__ double mlf_user_loglike(const double *p, int d, const double *aux, long long naux) {
+  const int N = MLF_GP_N;
+  double A[(MLF_GP_N + 1) * (MLF_GP_N + 2) / 2], diag[MLF_GP_N];
+  for (int i = 0; i <= N; ++i)
+    for (int j = 0; j <= i; ++j)
+      A[i * (i + 1) / 2 + j] = i < N ? mlf_gp_cov(p, aux, i, j) : j < N ? mlf_gp_resid(p, aux, j) : 0.0;
+  for (int k = 0; k < N; ++k) {
+    const double piv = A[k * (k + 1) / 2 + k];
+    if (!(piv > 0.0)) return piv != piv ? piv : -__builtin_inf();
+    const double lkk = sqrt(piv);
+    diag[k] = lkk;
+    for (int i = k + 1; i <= N; ++i) A[i * (i + 1) / 2 + k] = A[i * (i + 1) / 2 + k] / lkk;
+    for (int i = k + 1; i <= N; ++i)
+      for (int j = k + 1; j <= i && j < N; ++j) {
+        const double m = A[i * (i + 1) / 2 + k] * A[j * (j + 1) / 2 + k];
+        A[i * (i + 1) / 2 + j] = A[i * (i + 1) / 2 + j] - m;
+      }
+  }
+  double quad = 0.0, h = 0.0;
+  for (int k = 0; k < N; ++k) quad = quad + A[N * (N + 1) / 2 + k] * A[N * (N + 1) / 2 + k];
+  for (int k = 0; k < N; ++k) h = h + log(diag[k]);
+  return ((-0.5 * quad) - h) - (double)N * 0.91893853320467274178;
+}
+"""
+
+# the prior box of gp_sqexp(affine=True): ln a in [-1, 1], ln l in [-1, 2], ln s in [-2, 0], mean in [-1, 1]
+GP_PRIOR_LO = (-1.0, -1.0, -2.0, -1.0)
+GP_PRIOR_WIDTH = (2.0, 3.0, 2.0, 2.0)
+GP_TRANSFORM = r"""
+__device__ void mlf_user_transform(const double *u, double *p, int d, const double *aux, long long naux) {
+  p[0] = u[0] * 2.0 + -1.0;
+  p[1] = u[1] * 3.0 + -1.0;
+  p[2] = u[2] * 2.0 + -2.0;
+  p[3] = u[3] * 2.0 + -1.0;
+}
+"""
+
+
+def gp_data(ndata, seed=1):
+    """(x (ndata) ascending in [0, 10), y (ndata)) of gp_sqexp and its twin: a sine with noise of 0.3"""
+    rs = np.random.RandomState(seed)
+    x = np.sort(rs.uniform(0.0, 10.0, size=ndata))
+    return x, np.sin(x) + 0.3 * rs.normal(size=ndata)
+
+
+def gp_sqexp(ndata, seed=1, affine=False):
+    """covariance form: one workgroup per row factorises the ndata x ndata kernel matrix in LDS"""
+    return DeviceModel(4, GP_SQEXP % ndata + GP_COV_LOGLIKE, GP_TRANSFORM if affine else None, aux=np.concatenate(gp_data(ndata, seed)),
+                       name="gp_sqexp%d" % ndata, ncov=int(ndata))
+
+
+def gp_sqexp_twin(ndata, seed=1, affine=False):
+    """default form of gp_sqexp: the same arithmetic in the same order in one thread per row, over a private array (ndata <= 12)"""
+    if not 1 <= ndata <= 12:
+        raise ValueError("gp_sqexp_twin holds the factor in a thread's private memory: ndata must be 1 to 12, got %r" % (ndata,))
+    return DeviceModel(4, GP_SQEXP % ndata + GP_TWIN_LOGLIKE, GP_TRANSFORM if affine else None, aux=np.concatenate(gp_data(ndata, seed)),
+                       name="gp_sqexp_twin%d" % ndata)
