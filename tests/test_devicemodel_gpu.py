@@ -96,10 +96,10 @@ def test_rosenbrock_against_the_builtin_kernels(d):
         assert ref.excess(L)[0] <= 1 and ref.excess(Lb)[0] <= 1, (d, n, ref.excess(L), ref.excess(Lb))
 
 
-@pytest.mark.parametrize("d", [10, 101, 63, 64])
+@pytest.mark.parametrize("d", [10, 101, 63, 64, 1])
 def test_eval_dev_member_rows_only(d):
     """device pointers (torch tensors): rows outside the mask get L = -inf and keep their p row; the others are the host
-    entry's values"""
+    entry's values, which are numpy's (d = 1: the staging steps by 64 rows and 0 columns)"""
     import torch
     from ultranest_amd import _lib
     F = usermodels.funnel(d)
@@ -119,6 +119,9 @@ def test_eval_dev_member_rows_only(d):
     _lib.check(_lib.lib().mlf_synchronize())
     p, L = tp.cpu().numpy(), tL.cpu().numpy()
     want_p = F.transform(u)
+    data = usermodels.funnel_data(d)
+    assert _close(want_p, _funnel_transform_np(u))
+    assert _close(F.loglike(want_p), _funnel_np(want_p, data), scale=_funnel_scale(want_p, data))
     assert np.array_equal(p[member], want_p[member]) and (p[~member] == 7.0).all()
     assert np.array_equal(L[member], F.loglike(want_p[member])) and np.isneginf(L[~member]).all()
 

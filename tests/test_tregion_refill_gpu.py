@@ -20,7 +20,7 @@ N = 30000      # not a multiple of 64 or 256
 
 def _region_of(kind, u, seed=2):
     import ultranest_amd.mlfriends as m
-    layer = m.AffineLayer()
+    layer = m.AffineLayer() if u.shape[1] > 1 else m.ScalingLayer()      # (the affine layer inverts a covariance MATRIX)
     layer.optimize(u, u)
     region = getattr(m, kind)(u, layer)
     region.maxradiussq, region.enlarge = region.compute_enlargement(nbootstraps=10, rng=np.random.RandomState(seed))
@@ -163,26 +163,38 @@ def test_builtin_gated_refill_in_more_dimensions(kind, d):
 # ---- 2. user route ---------------------------------------------------------------------------------------------------
 
 def _user_case(which):
+    """(model, transform callback, live points, region kind).  400 live points in 70 dimensions: MLFriends accepts about ten of
+    30000 draws from its wrapping ellipsoid (none from 100 dimensions on), too few for the recipe's median and gap; from 63
+    dimensions on the single-ellipsoid region hands the kernel a full batch"""
     if which == "rosenbrock7":            # staged form with the p buffer
         M = usermodels.rosenbrock(7)
-        return M, M.transform, np.clip(0.5 + 0.12 * np.random.RandomState(4).normal(size=(400, 7)), 0.01, 0.99)
+        return M, M.transform, np.clip(0.5 + 0.12 * np.random.RandomState(4).normal(size=(400, 7)), 0.01, 0.99), "MLFriends"
     if which == "funnel51":               # staged, near the LDS budget
         M = usermodels.funnel(51)
-        return M, M.transform, 0.5 + 0.03 * np.random.RandomState(5).normal(size=(400, 51))
+        return M, M.transform, 0.5 + 0.03 * np.random.RandomState(5).normal(size=(400, 51)), "MLFriends"
     if which == "rosenbrock70":           # direct form
         M = usermodels.rosenbrock(70)
-        return M, M.transform, 0.5 + 0.03 * np.random.RandomState(7).normal(size=(400, 70))
+        return M, M.transform, 0.5 + 0.03 * np.random.RandomState(7).normal(size=(400, 70)), "RobustEllipsoidRegion"
+    if which in ("funnel63", "funnel64"):  # the last staged and the first direct d with a p buffer
+        d = int(which[6:])
+        M = usermodels.funnel(d)
+        return M, M.transform, 0.5 + 0.03 * np.random.RandomState(5).normal(size=(400, d)), "RobustEllipsoidRegion"
+    if which == "rosenbrock4_65draws":    # a second, partial wave (the live set of test_builtin_gated_refill_of_65_draws)
+        M = usermodels.rosenbrock(4)
+        return M, M.transform, _blob(400, 4, 77), "MLFriends"
+    if which == "gauss1":                 # d = 1: the staging steps by 64 rows and 0 columns
+        M = usermodels.gauss(1, affine=True)
+        return M, M.transform, _blob(400, 1, 77), "MLFriends"
     M = usermodels.gauss(7)               # no transform: no p buffer
-    return M, lk.identity_transform, np.clip(0.5 + 0.12 * np.random.RandomState(4).normal(size=(400, 7)), 0.01, 0.99)
+    return M, lk.identity_transform, np.clip(0.5 + 0.12 * np.random.RandomState(4).normal(size=(400, 7)), 0.01, 0.99), "MLFriends"
 
 
-@pytest.mark.parametrize("which", ["rosenbrock7", "funnel51", "rosenbrock70", "gauss7_identity"])
+@pytest.mark.parametrize("which", ["rosenbrock7", "funnel51", "rosenbrock70", "gauss7_identity", "funnel63", "funnel64",
+                                   "rosenbrock4_65draws", "gauss1"])
 def test_user_gated_refill_equals_the_host_sequence(which):
     from ultranest_amd import kernels
-    M, transform, u = _user_case(which)
-    # 400 live points in 70 dimensions: MLFriends accepts about ten of 30000 draws from its wrapping ellipsoid (none from 100
-    # dimensions on), too few for the recipe's median and gap; the single-ellipsoid region hands the kernel a full batch
-    region = _region_of("RobustEllipsoidRegion" if which == "rosenbrock70" else "MLFriends", u)
+    M, transform, u, kind = _user_case(which)
+    region = _region_of(kind, u)
     calls = []
     orig = kernels.DeviceRegion.refill_user
 
@@ -192,14 +204,14 @@ def test_user_gated_refill_equals_the_host_sequence(which):
 
     kernels.DeviceRegion.refill_user = counting
     try:
-        _check(region, "sample_from_wrapping_ellipsoid", transform, M.loglike)
+        _check(region, "sample_from_wrapping_ellipsoid", transform, M.loglike, n=65 if which.endswith("65draws") else N)
     finally:
         kernels.DeviceRegion.refill_user = orig
     assert len(calls) == 1
 
 
 def test_user_and_builtin_gated_rosenbrock_agree_bit_for_bit():
-    M, _, u = _user_case("rosenbrock7")
+    M, _, u, _ = _user_case("rosenbrock7")
     out = []
     for transform, loglike in [(lk.rosenbrock_transform, lk.rosenbrock_loglike), (M.transform, M.loglike)]:
         region = _region_of("MLFriends", u)
@@ -249,7 +261,7 @@ def test_fixed_dimension_is_checked_for_equality():
 
 @pytest.mark.parametrize("route", ["builtin", "user"])
 def test_neutral_gate_changes_nothing(route):
-    M, _, u = _user_case("rosenbrock7")
+    M, _, u, _ = _user_case("rosenbrock7")
     transform, loglike = (M.transform, M.loglike) if route == "user" else (lk.rosenbrock_transform, lk.rosenbrock_loglike)
     region = _region_of("MLFriends", u)
     Lmin = np.sort(lk.rosenbrock_loglike(lk.rosenbrock_transform(u)))[40]
@@ -263,7 +275,7 @@ def test_neutral_gate_changes_nothing(route):
 
 @pytest.mark.parametrize("route", ["builtin", "user"])
 def test_device_copy_follows_update_center_and_is_cleared(route):
-    M, _, u = _user_case("rosenbrock7")
+    M, _, u, _ = _user_case("rosenbrock7")
     transform, loglike = (M.transform, M.loglike) if route == "user" else (lk.rosenbrock_transform, lk.rosenbrock_loglike)
     region = _region_of("MLFriends", u)
     got, host, tregion, Lmin = _check(region, "sample_from_wrapping_ellipsoid", transform, loglike)
@@ -286,7 +298,7 @@ def test_a_user_model_of_the_other_variant_is_refused():
     model loaded ungated, or the reverse, is an error with a message, and so is a code object loaded as the variant it was not
     compiled as: none of them launches."""
     from ultranest_amd import devicemodel as dm
-    M, _, u = _user_case("rosenbrock7")
+    M, _, u, _ = _user_case("rosenbrock7")
     region = _region_of("MLFriends", u)
     tregion = _tregion(M.transform(np.asarray(region.u)))
     got = _gated(region, "sample_from_wrapping_ellipsoid", N, -1e300, M.transform, M.loglike, tregion)

@@ -27,21 +27,30 @@ using namespace mlf;
 
 namespace {
 
-// THE FORM TABLE: what each MLF_USERMODEL_* variant is, indexed by its number.  Nothing else in the library tells variants apart.
+// THE FORM TABLE: what each program form is, one row per number: the MLF_USERMODEL_* variants, and behind them the covariance pair,
+// whose numbers only mlf_covmodel_compile / _create use (Form.variant of devicemodel.py).  Nothing else in the library tells the
+// forms apart.
+enum Shape {
+  THREAD_PER_ROW,   // workgroups of one wave, one row per thread
+  WAVE_PER_ROW,     // one wave (= one workgroup) per row: the summed forms, `long long nterms` behind the first eight parameters
+  GROUP_PER_ROW,    // one workgroup of MLF_USER_COV_THREADS per row: the covariance form (mlf_user_cov.hpp), `double *tri` there
+};
 struct Variant {
-  const char *kernel;   // the only kernel of the variant's program (mlf_user_rows.hpp)
+  int number;
+  const char *kernel;   // the only kernel of the variant's program (mlf_user_rows.hpp, mlf_user_cov.hpp)
+  Shape shape;
   bool gated;           // the kernel takes the t-region gate's five parameters behind the others
-  bool summed;          // one wave (= one workgroup) per row instead of one thread, nterms behind the first eight parameters
   bool multi;           // several sums: their number is a constant of the program (-DMLF_USER_NSUMS)
   bool derive;          // p (n, d) -> [p | q] (n, d + nderived); such a handle runs in the derive entries only
   bool gate_derived;    // (gated is set too) the kernel computes nderived columns per member row, gates over d + nderived columns and
                         // takes (nq, q_scratch) behind the gate's five; such a handle runs in mlf_region_refill_user_derived_gated only
   const char *compile_entry, *create_entry;   // the exported entries that accept the variant
   unsigned (*lds_bytes)(int d, int nq, bool p_buffer);   // dynamic LDS of a launch (0: the kernel's direct form)
-  unsigned threads;     // threads per workgroup
-  bool row_per_group;   // one workgroup per row (else one thread per row, `threads` rows per workgroup)
-  bool nterms_arg;      // the kernel takes `long long nterms` behind the first eight parameters
-  bool tri_arg;         // the kernel takes `double *tri` behind the first eight parameters (mlf_user_cov.hpp)
+
+  constexpr bool summed() const { return shape == WAVE_PER_ROW; }
+  constexpr bool cov() const { return shape == GROUP_PER_ROW; }
+  constexpr unsigned threads() const { return cov() ? MLF_USER_COV_THREADS : 64; }   // per workgroup
+  constexpr unsigned rows_per_group() const { return shape == THREAD_PER_ROW ? threads() : 1; }
 };
 
 unsigned lds_rows(int d, int, bool p_buffer) { return mlf_user_rows_lds_bytes(d, p_buffer); }
@@ -52,33 +61,34 @@ unsigned lds_sum_gate_derived(int d, int nq, bool p_buffer) { return mlf_user_ro
 
 // the exported entries' names: an entry owns the variants whose row names it
 constexpr char COMPILE_VARIANT[] = "mlf_usermodel_compile_variant", COMPILE_SUMS[] = "mlf_usermodel_compile_sums",
-               COMPILE_GATE_DERIVED[] = "mlf_usermodel_compile_gate_derived", CREATE_VARIANT[] = "mlf_usermodel_create_variant",
-               CREATE_SUM[] = "mlf_usermodel_create_sum", CREATE_DERIVED[] = "mlf_usermodel_create_derived",
-               CREATE_GATE_DERIVED[] = "mlf_usermodel_create_gate_derived";
+               COMPILE_GATE_DERIVED[] = "mlf_usermodel_compile_gate_derived", COMPILE_COV[] = "mlf_covmodel_compile",
+               CREATE_VARIANT[] = "mlf_usermodel_create_variant", CREATE_SUM[] = "mlf_usermodel_create_sum",
+               CREATE_DERIVED[] = "mlf_usermodel_create_derived", CREATE_GATE_DERIVED[] = "mlf_usermodel_create_gate_derived",
+               CREATE_COV[] = "mlf_covmodel_create";
+constexpr int COVMODEL = 16, COVMODEL_TREGION = 17;
 constexpr Variant kVariants[] = {
-    //                                       gated summed multi derive gate_derived ... threads row_per_group nterms_arg tri_arg
-    {"mlf_user_rows",                        false, false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows, 64, false, false, false},
-    {"mlf_user_rows_tregion",                true,  false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows, 64, false, false, false},
-    {"mlf_user_rows_sum",                    false, true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum, 64, true, true, false},
-    {"mlf_user_rows_sum_tregion",            true,  true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum, 64, true, true, false},
-    {"mlf_user_rows_sums",                   false, true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum, 64, true, true, false},
-    {"mlf_user_rows_sums_tregion",           true,  true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum, 64, true, true, false},
-    {"mlf_user_derive_rows",                 false, false, false, true,  false, COMPILE_VARIANT, CREATE_DERIVED, lds_derive, 64, false, false, false},
-    {"mlf_user_rows_tregion_derived",        true,  false, false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_gate_derived, 64, false, false, false},
-    {"mlf_user_rows_sum_tregion_derived",    true,  true,  false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived, 64, true, true, false},
-    {"mlf_user_rows_sums_tregion_derived",   true,  true,  true,  false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived, 64, true, true, false},
+    //                                                                                       gated  multi  derive gate_derived
+    {MLF_USERMODEL_DEFAULT, "mlf_user_rows", THREAD_PER_ROW,                                 false, false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows},
+    {MLF_USERMODEL_TREGION, "mlf_user_rows_tregion", THREAD_PER_ROW,                         true,  false, false, false, COMPILE_VARIANT, CREATE_VARIANT, lds_rows},
+    {MLF_USERMODEL_SUM, "mlf_user_rows_sum", WAVE_PER_ROW,                                   false, false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum},
+    {MLF_USERMODEL_SUM_TREGION, "mlf_user_rows_sum_tregion", WAVE_PER_ROW,                   true,  false, false, false, COMPILE_VARIANT, CREATE_SUM, lds_sum},
+    {MLF_USERMODEL_SUMS, "mlf_user_rows_sums", WAVE_PER_ROW,                                 false, true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum},
+    {MLF_USERMODEL_SUMS_TREGION, "mlf_user_rows_sums_tregion", WAVE_PER_ROW,                 true,  true,  false, false, COMPILE_SUMS, CREATE_SUM, lds_sum},
+    {MLF_USERMODEL_DERIVED, "mlf_user_derive_rows", THREAD_PER_ROW,                          false, false, true,  false, COMPILE_VARIANT, CREATE_DERIVED, lds_derive},
+    {MLF_USERMODEL_TREGION_DERIVED, "mlf_user_rows_tregion_derived", THREAD_PER_ROW,         true,  false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_gate_derived},
+    {MLF_USERMODEL_SUM_TREGION_DERIVED, "mlf_user_rows_sum_tregion_derived", WAVE_PER_ROW,   true,  false, false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived},
+    {MLF_USERMODEL_SUMS_TREGION_DERIVED, "mlf_user_rows_sums_tregion_derived", WAVE_PER_ROW, true,  true,  false, true,  COMPILE_GATE_DERIVED, CREATE_GATE_DERIVED, lds_sum_gate_derived},
+    {COVMODEL, "mlf_user_rows_cov", GROUP_PER_ROW,                                           false, false, false, false, COMPILE_COV, CREATE_COV, lds_sum},
+    {COVMODEL_TREGION, "mlf_user_rows_cov_tregion", GROUP_PER_ROW,                           true,  false, false, false, COMPILE_COV, CREATE_COV, lds_sum},
 };
-static_assert(MLF_USERMODEL_DEFAULT == 0 && MLF_USERMODEL_TREGION == 1 && MLF_USERMODEL_SUM == 2 && MLF_USERMODEL_SUM_TREGION == 3 &&
-                  MLF_USERMODEL_SUMS == 4 && MLF_USERMODEL_SUMS_TREGION == 5 && MLF_USERMODEL_DERIVED == 6 &&
-                  MLF_USERMODEL_TREGION_DERIVED == 7 && MLF_USERMODEL_SUM_TREGION_DERIVED == 8 &&
-                  MLF_USERMODEL_SUMS_TREGION_DERIVED == 9 && sizeof(kVariants) / sizeof(kVariants[0]) == 10,
-              "kVariants is indexed by the MLF_USERMODEL_* numbers");
+constexpr int kLastPublicVariant = MLF_USERMODEL_SUMS_TREGION_DERIVED;   // the numbers above it are known to their own entries only
 
-// The covariance form (mlf_user_cov.hpp): not numbered, reached through mlf_covmodel_compile / _create alone; indexed by `gated`.
-constexpr char COMPILE_COV[] = "mlf_covmodel_compile", CREATE_COV[] = "mlf_covmodel_create";
-constexpr Variant kCovVariants[] = {
-    {"mlf_user_rows_cov",         false, false, false, false, false, COMPILE_COV, CREATE_COV, lds_sum, MLF_USER_COV_THREADS, true, false, true},
-    {"mlf_user_rows_cov_tregion", true,  false, false, false, false, COMPILE_COV, CREATE_COV, lds_sum, MLF_USER_COV_THREADS, true, false, true},
+// what the entries bring besides the variant: each is 0 where its rule (check_counts) says so
+struct Counts {
+  int nsums = 0;         // of a variant with several sums (a compile entry's)
+  int ncov = 0;          // of a covariance model: the order of its matrix (a constant of its program)
+  size_t nterms = 0;     // of a summed variant (a create entry's)
+  size_t nderived = 0;   // of the derive variant and the gate_derived ones (a create entry's)
 };
 
 }  // namespace
@@ -160,6 +170,17 @@ void put_log(char *log, size_t cap, const std::string &text) {
   log[k] = '\0';
 }
 
+// the model's kernel over n > 0 rows: the grid from the row's shape, its dynamic LDS (nderived is 0 in every row whose LDS does
+// not depend on it), the launch
+int launch_rows(const mlf_usermodel *m, long long n, bool p_buffer, void **args, hipStream_t s) {
+  const Variant &v = *m->v;
+  const long long blocks = (n + v.rows_per_group() - 1) / v.rows_per_group();
+  if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
+  const unsigned lds = v.lds_bytes(m->d, m->nderived, p_buffer);
+  CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, v.threads(), 1, 1, lds, s, args, nullptr));
+  return 0;
+}
+
 }  // namespace
 
 namespace mlf {
@@ -186,11 +207,7 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
                                          : "a t-region over d + nderived columns needs a user model loaded as a _TREGION_DERIVED "
                                            "variant (mlf_usermodel_create_gate_derived)");
   if (n <= 0) return 0;
-  if (tri != nullptr && !v.tri_arg) return fail_arg(MLF_E_STATE, "not a covariance model (mlf_covmodel_create): it has no factor");
-  // one workgroup per row (summed forms: a wave; covariance form: four), else one thread per row
-  const long long blocks = v.row_per_group ? n : (n + v.threads - 1) / v.threads;
-  if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
-  const unsigned lds = v.lds_bytes(m->d, gate_nq, p != nullptr && m->has_transform);
+  if (tri != nullptr && !v.cov()) return fail_arg(MLF_E_STATE, "not a covariance model (mlf_covmodel_create): it has no factor");
   // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
   const double *a_u = u;
   long long a_n = n;
@@ -214,9 +231,9 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
   // gated, (nq, q_scratch) behind those in a _TREGION_DERIVED variant
   void *args[16] = {&a_u, &a_n, &a_d, &a_member, &a_aux, &a_naux, &a_p, &a_L};
   int na = 8;
-  if (v.nterms_arg) args[na++] = &a_nterms;
+  if (v.summed()) args[na++] = &a_nterms;
   double *a_tri = tri;
-  if (v.tri_arg) args[na++] = &a_tri;
+  if (v.cov()) args[na++] = &a_tri;
   if (gate) {
     void *g[] = {&g_A, &g_ctr, &g_fixed, &g_enlarge, &g_member2};
     for (void *x : g) args[na++] = x;
@@ -225,16 +242,12 @@ int usermodel_rows(const mlf_usermodel *m, const double *u, long long n, const u
     args[na++] = &g_nq;
     args[na++] = &g_scratch;
   }
-  CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, v.threads, 1, 1, lds, s, args, nullptr));
-  return 0;
+  return launch_rows(m, n, p != nullptr && m->has_transform, args, s);
 }
 
 int usermodel_derive_rows(const mlf_usermodel *m, const double *p, long long n, double *out, hipStream_t s) {
   if (!m->v->derive) return fail_arg(MLF_E_STATE, "not a derive handle (mlf_usermodel_create_derived)");
   if (n <= 0) return 0;
-  const long long blocks = (n + 63) / 64;   // one thread per row, 64 rows per workgroup
-  if (blocks > 0x7fffffffLL) return fail_arg(MLF_E_BADARG, "user model: too many rows for one launch");
-  const unsigned lds = m->v->lds_bytes(m->d, m->nderived, false);
   // the kernel's parameters, in order and with its exact types (mlf_user_rows.hpp)
   const double *a_p = p;
   long long a_n = n;
@@ -243,8 +256,7 @@ int usermodel_derive_rows(const mlf_usermodel *m, const double *p, long long n, 
   long long a_naux = m->naux;
   double *a_out = out;
   void *args[7] = {&a_p, &a_n, &a_d, &a_nq, &a_aux, &a_naux, &a_out};
-  CK(hipModuleLaunchKernel(m->fn, (unsigned)blocks, 1, 1, 64, 1, 1, lds, s, args, nullptr));
-  return 0;
+  return launch_rows(m, n, false, args, s);
 }
 
 }  // namespace mlf
@@ -254,26 +266,32 @@ namespace {
 // the row of `variant` where the exported entry `mine` (one of the names above) owns it; else NULL, and the message names the
 // entry that does
 const Variant *owned(int variant, const char *mine, const char *Variant::*owner) {
-  if (variant < 0 || variant >= (int)(sizeof(kVariants) / sizeof(kVariants[0]))) {
+  const Variant *v = nullptr;
+  for (const Variant &row : kVariants)
+    if (row.number == variant) v = &row;
+  if (v && v->*owner == mine) return v;
+  if (!v || variant > kLastPublicVariant) {
     fail_arg(MLF_E_BADARG, "unknown user-model variant");
     return nullptr;
   }
-  const Variant *v = &kVariants[variant];
-  if (v->*owner == mine) return v;
   fail_arg(MLF_E_BADARG, (std::string(mine) + ": user-model variant " + std::to_string(variant) + " (entry " + v->kernel +
                           ") goes through " + v->*owner).c_str());
   return nullptr;
 }
 
-// the counts against the row, each rule once.  A compile entry brings the number of sums (the entries without one: 0), a create
-// entry (nsums NULL) the numbers of terms and of derived columns (the entries without one: 0).
-int check_counts(const Variant &v, const int *nsums, size_t nterms = 0, size_t nderived = 0) {
-  if (nsums) {
-    if (v.multi ? (*nsums < 1 || *nsums > MLF_USERMODEL_MAX_SUMS) : *nsums != 0)
+// the counts against the row, each rule once.  Both kinds of entry bring ncov; a compile entry the number of sums besides, a
+// create entry the numbers of terms and of derived columns (the entries without one: 0).
+int check_counts(const Variant &v, const Counts &c, bool compile) {
+  if (v.cov() ? (c.ncov < 1 || c.ncov > 1024 || mlf_user_rows_cov_lds_bytes(c.ncov) > MLF_USER_COV_LDS_CAP) : c.ncov != 0)
+    return fail_arg(MLF_E_BADARG, "ncov: the augmented triangle of an ncov x ncov covariance must fit the LDS of one CU "
+                                  "(mlf_covmodel_lds_bytes(ncov) <= 163840)");
+  if (compile) {
+    if (v.multi ? (c.nsums < 1 || c.nsums > MLF_USERMODEL_MAX_SUMS) : c.nsums != 0)
       return fail_arg(MLF_E_BADARG, "nsums must be 1 to 8 for a variant with several sums (_SUMS), else 0");
     return 0;
   }
-  if (v.summed ? (nterms == 0 || nterms > 0x7fffffffffffffffull) : nterms != 0)
+  const size_t nterms = c.nterms, nderived = c.nderived;
+  if (v.summed() ? (nterms == 0 || nterms > 0x7fffffffffffffffull) : nterms != 0)
     return fail_arg(MLF_E_BADARG, "nterms: a summed user model has at least one term, every other variant 0");
   if ((v.derive || v.gate_derived) ? nderived == 0 : nderived != 0)
     return fail_arg(MLF_E_BADARG, "nderived: a derive program and a gate over derived parameters have at least one derived "
@@ -282,26 +300,28 @@ int check_counts(const Variant &v, const int *nsums, size_t nterms = 0, size_t n
 }
 
 // the checks every create entry makes before it touches the device
-int check_create_args(const void *code, size_t nbytes, size_t d, size_t nderived) {
+int check_create_args(const void *code, size_t nbytes, size_t d, const Counts &c) {
   if (d == 0) return fail_arg(MLF_E_BADARG, "dimensionality must be positive");
   if (d > MLF_MAX_DIM) return fail_arg(MLF_E_DIM, "user model: dimensionality above MLF_MAX_DIM");
   if (nbytes < 64 || memcmp(code, "\x7f" "ELF", 4) != 0) return fail_arg(MLF_E_BADARG, "not a code object (ELF)");
-  if (nderived > MLF_MAX_DIM - d) return fail_arg(MLF_E_DIM, "user model: parameters and derived parameters above MLF_MAX_DIM");
+  if (c.nderived > MLF_MAX_DIM - d) return fail_arg(MLF_E_DIM, "user model: parameters and derived parameters above MLF_MAX_DIM");
+  if (c.ncov && (size_t)mlf_user_rows_cov_lds_bytes(c.ncov) + 2 * d * sizeof(double) > MLF_USER_COV_LDS_CAP)
+    return fail_arg(MLF_E_BADARG, "ncov and d: the triangle and the row's u and p exceed the LDS of one CU");
   return 0;
 }
 
 // loads the code object as the variant `v` (arguments checked by the caller)
-int load_model(const void *code, size_t d, int has_transform, const Variant &v, size_t nterms, size_t nderived, const double *aux,
-               size_t naux, mlf_usermodel **out, int ncov = 0) {
+int load_model(const void *code, size_t d, int has_transform, const Variant &v, const Counts &c, const double *aux, size_t naux,
+               mlf_usermodel **out) {
   if (int rc = ensure_ctx()) return rc;
   hipStream_t s = ctx_stream();
   mlf_usermodel *m = new mlf_usermodel();
   m->v = &v;
   m->d = (int)d;
   m->has_transform = has_transform != 0;
-  m->nterms = (long long)nterms;
-  m->nderived = (int)nderived;
-  m->ncov = ncov;
+  m->nterms = (long long)c.nterms;
+  m->nderived = (int)c.nderived;
+  m->ncov = c.ncov;
   m->naux = (long long)naux;
   hipError_t e = hipModuleLoadData(&m->module, code);
   if (e == hipSuccess && hipModuleGetFunction(&m->fn, m->module, v.kernel) != hipSuccess) {
@@ -324,10 +344,10 @@ int load_model(const void *code, size_t d, int has_transform, const Variant &v, 
   return 0;
 }
 
-// hiprtc on `source` + the wrapper header as the variant `v` (nsums checked by the caller: 0 unless v.multi)
-// ncov: the order of a covariance form's matrix (0: every other variant), which compiles mlf_user_cov.hpp instead
-int compile_program(const char *source, const char *include_dir, int has_transform, const Variant &v, int nsums, void *code_out,
-                    size_t code_cap, size_t *code_size, char *log, size_t log_cap, int ncov = 0) {
+// hiprtc on `source` + the wrapper header as the variant `v` (counts checked by the caller); a covariance form compiles
+// mlf_user_cov.hpp instead
+int compile_program(const char *source, const char *include_dir, int has_transform, const Variant &v, const Counts &c,
+                    void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
   *code_size = 0;
   put_log(log, log_cap, "");
   std::lock_guard<std::mutex> lock(g_rtc_mutex);
@@ -336,21 +356,20 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
     return fail_arg(MLF_E_COMPILE, g_rtc.why.c_str());
   }
   const Rtc &r = g_rtc;
-  const std::string src = std::string(source) + (v.tri_arg ? "\n#include \"mlf_user_cov.hpp\"\n" : "\n#include \"mlf_user_rows.hpp\"\n");
+  const std::string src = std::string(source) + (v.cov() ? "\n#include \"mlf_user_cov.hpp\"\n" : "\n#include \"mlf_user_rows.hpp\"\n");
   const std::string inc = std::string("-I") + include_dir;
-  const std::string sums = "-DMLF_USER_NSUMS=" + std::to_string(nsums);
-  const std::string cov = "-DMLF_USER_NCOV=" + std::to_string(ncov);
-  // every program gets the first eight; a variant's own options follow (so the other variants' programs are compiled as they were
-  // before it existed; the derive program never calls the transform)
+  const std::string sums = "-DMLF_USER_NSUMS=" + std::to_string(c.nsums);
+  const std::string cov = "-DMLF_USER_NCOV=" + std::to_string(c.ncov);
+  // every program gets the first eight; a variant's own options follow (the derive program never calls the transform)
   const char *opts[12] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
                           has_transform && !v.derive ? "-DMLF_USER_HAS_TRANSFORM=1" : "-DMLF_USER_HAS_TRANSFORM=0",
                           v.gated ? "-DMLF_USER_TREGION=1" : "-DMLF_USER_TREGION=0",
-                          v.summed ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0"};
+                          v.summed() ? "-DMLF_USER_SUM=1" : "-DMLF_USER_SUM=0"};
   int nopts = 8;
   if (v.multi) opts[nopts++] = sums.c_str();
   if (v.derive) opts[nopts++] = "-DMLF_USER_DERIVED=1";
   if (v.gate_derived) opts[nopts++] = "-DMLF_USER_GATE_DERIVED=1";
-  if (v.tri_arg) opts[nopts++] = cov.c_str();
+  if (v.cov()) opts[nopts++] = cov.c_str();
   hiprtcProgram prog = nullptr;
   hiprtcResult res = r.create(&prog, src.c_str(), "mlf_user_model.hip", 0, nullptr, nullptr);
   if (res != HIPRTC_SUCCESS) {
@@ -390,25 +409,25 @@ int compile_program(const char *source, const char *include_dir, int has_transfo
 }
 
 // every exported compile entry: the pointers, "is this variant mine", the counts, one compile
-int compile_entry(const char *mine, const char *source, const char *include_dir, int has_transform, int variant, int nsums,
+int compile_entry(const char *mine, const char *source, const char *include_dir, int has_transform, int variant, const Counts &c,
                   void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
   if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
   const Variant *v = owned(variant, mine, &Variant::compile_entry);
   if (!v) return MLF_E_BADARG;
-  if (int rc = check_counts(*v, &nsums)) return rc;
-  return compile_program(source, include_dir, has_transform, *v, nsums, code_out, code_cap, code_size, log, log_cap);
+  if (int rc = check_counts(*v, c, true)) return rc;
+  return compile_program(source, include_dir, has_transform, *v, c, code_out, code_cap, code_size, log, log_cap);
 }
 
 // every exported create entry: the pointers, "is this variant mine", the counts, d and the code object, one load
-int create_entry(const char *mine, const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
-                 size_t nderived, const double *aux, size_t naux, mlf_usermodel **out) {
+int create_entry(const char *mine, const void *code, size_t nbytes, size_t d, int has_transform, int variant, const Counts &c,
+                 const double *aux, size_t naux, mlf_usermodel **out) {
   if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
   *out = nullptr;
   const Variant *v = owned(variant, mine, &Variant::create_entry);
   if (!v) return MLF_E_BADARG;
-  if (int rc = check_counts(*v, nullptr, nterms, nderived)) return rc;
-  if (int rc = check_create_args(code, nbytes, d, nderived)) return rc;
-  return load_model(code, d, has_transform, *v, nterms, nderived, aux, naux, out);
+  if (int rc = check_counts(*v, c, false)) return rc;
+  if (int rc = check_create_args(code, nbytes, d, c)) return rc;
+  return load_model(code, d, has_transform, *v, c, aux, naux, out);
 }
 
 }  // namespace
@@ -423,17 +442,17 @@ int mlf_usermodel_compile(const char *source, const char *include_dir, int has_t
 
 int mlf_usermodel_compile_variant(const char *source, const char *include_dir, int has_transform, int variant, void *code_out,
                                   size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  return compile_entry(COMPILE_VARIANT, source, include_dir, has_transform, variant, 0, code_out, code_cap, code_size, log, log_cap);
+  return compile_entry(COMPILE_VARIANT, source, include_dir, has_transform, variant, Counts{}, code_out, code_cap, code_size, log, log_cap);
 }
 
 int mlf_usermodel_compile_sums(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
                                void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  return compile_entry(COMPILE_SUMS, source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log, log_cap);
+  return compile_entry(COMPILE_SUMS, source, include_dir, has_transform, variant, Counts{nsums}, code_out, code_cap, code_size, log, log_cap);
 }
 
 int mlf_usermodel_compile_gate_derived(const char *source, const char *include_dir, int has_transform, int variant, int nsums,
                                        void *code_out, size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  return compile_entry(COMPILE_GATE_DERIVED, source, include_dir, has_transform, variant, nsums, code_out, code_cap, code_size, log,
+  return compile_entry(COMPILE_GATE_DERIVED, source, include_dir, has_transform, variant, Counts{nsums}, code_out, code_cap, code_size, log,
                        log_cap);
 }
 
@@ -444,22 +463,22 @@ int mlf_usermodel_create(const void *code, size_t nbytes, size_t d, int has_tran
 
 int mlf_usermodel_create_variant(const void *code, size_t nbytes, size_t d, int has_transform, int variant, const double *aux,
                                  size_t naux, mlf_usermodel **out) {
-  return create_entry(CREATE_VARIANT, code, nbytes, d, has_transform, variant, 0, 0, aux, naux, out);
+  return create_entry(CREATE_VARIANT, code, nbytes, d, has_transform, variant, Counts{}, aux, naux, out);
 }
 
 int mlf_usermodel_create_sum(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
                              const double *aux, size_t naux, mlf_usermodel **out) {
-  return create_entry(CREATE_SUM, code, nbytes, d, has_transform, variant, nterms, 0, aux, naux, out);
+  return create_entry(CREATE_SUM, code, nbytes, d, has_transform, variant, Counts{0, 0, nterms}, aux, naux, out);
 }
 
 int mlf_usermodel_create_derived(const void *code, size_t nbytes, size_t d, size_t nderived, const double *aux, size_t naux,
                                  mlf_usermodel **out) {
-  return create_entry(CREATE_DERIVED, code, nbytes, d, 0, MLF_USERMODEL_DERIVED, 0, nderived, aux, naux, out);
+  return create_entry(CREATE_DERIVED, code, nbytes, d, 0, MLF_USERMODEL_DERIVED, Counts{0, 0, 0, nderived}, aux, naux, out);
 }
 
 int mlf_usermodel_create_gate_derived(const void *code, size_t nbytes, size_t d, int has_transform, int variant, size_t nterms,
                                       size_t nderived, const double *aux, size_t naux, mlf_usermodel **out) {
-  return create_entry(CREATE_GATE_DERIVED, code, nbytes, d, has_transform, variant, nterms, nderived, aux, naux, out);
+  return create_entry(CREATE_GATE_DERIVED, code, nbytes, d, has_transform, variant, Counts{0, 0, nterms, nderived}, aux, naux, out);
 }
 
 int mlf_usermodel_gate_derived_lds_bytes(size_t d, size_t nderived, int has_p_buffer) {
@@ -478,32 +497,17 @@ int mlf_covmodel_lds_bytes(int ncov) {
   return (int)mlf_user_rows_cov_lds_bytes(ncov);
 }
 
-namespace {
-int check_ncov(int ncov) {
-  if (ncov < 1 || ncov > 1024 || mlf_user_rows_cov_lds_bytes(ncov) > MLF_USER_COV_LDS_CAP)
-    return fail_arg(MLF_E_BADARG, "ncov: the augmented triangle of an ncov x ncov covariance must fit the LDS of one CU "
-                                  "(mlf_covmodel_lds_bytes(ncov) <= 163840)");
-  return 0;
-}
-}  // namespace
-
 int mlf_covmodel_compile(const char *source, const char *include_dir, int has_transform, int gated, int ncov, void *code_out,
                          size_t code_cap, size_t *code_size, char *log, size_t log_cap) {
-  if (!source || !include_dir || !code_size) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (int rc = check_ncov(ncov)) return rc;
-  return compile_program(source, include_dir, has_transform, kCovVariants[gated ? 1 : 0], 0, code_out, code_cap, code_size, log,
-                         log_cap, ncov);
+  return compile_entry(COMPILE_COV, source, include_dir, has_transform, gated ? COVMODEL_TREGION : COVMODEL, Counts{0, ncov},
+                       code_out, code_cap, code_size, log, log_cap);
 }
 
 int mlf_covmodel_create(const void *code, size_t nbytes, size_t d, int has_transform, int gated, int ncov, const double *aux,
                         size_t naux, mlf_usermodel **out) {
-  if (!out || !code || (naux && !aux)) return fail_arg(MLF_E_BADARG, "null pointer");
-  *out = nullptr;
-  if (int rc = check_ncov(ncov)) return rc;
-  if (int rc = check_create_args(code, nbytes, d, 0)) return rc;
-  if ((size_t)mlf_user_rows_cov_lds_bytes(ncov) + 2 * d * sizeof(double) > MLF_USER_COV_LDS_CAP)
-    return fail_arg(MLF_E_BADARG, "ncov and d: the triangle and the row's u and p exceed the LDS of one CU");
-  if (int rc = load_model(code, d, has_transform, kCovVariants[gated ? 1 : 0], 0, 0, aux, naux, out, ncov)) return rc;
+  if (int rc = create_entry(CREATE_COV, code, nbytes, d, has_transform, gated ? COVMODEL_TREGION : COVMODEL, Counts{0, ncov}, aux,
+                            naux, out))
+    return rc;
   // ncov sizes the factor rows of mlf_covmodel_factor: it must be the program's own constant, which the kernel's static LDS names
   // (mlf_user_rows_cov_lds_bytes grows strictly with n)
   int shared = 0;
@@ -520,7 +524,7 @@ int mlf_covmodel_create(const void *code, size_t nbytes, size_t d, int has_trans
 
 int mlf_covmodel_factor(mlf_usermodel *m, const double *u, size_t n, double *tri_out, double *L_out) {
   if (!m || !u || !tri_out || !L_out) return fail_arg(MLF_E_BADARG, "null pointer");
-  if (!m->v->tri_arg) return fail_arg(MLF_E_STATE, "not a covariance model (mlf_covmodel_create): it has no factor");
+  if (!m->v->cov()) return fail_arg(MLF_E_STATE, "not a covariance model (mlf_covmodel_create): it has no factor");
   if (m->v->gated) return fail_arg(MLF_E_STATE, "the gated program of a covariance model runs in a refill with a t-region only");
   if (n == 0) return 0;
   const size_t tri_doubles = mlf_user_rows_cov_tri_doubles(m->ncov);

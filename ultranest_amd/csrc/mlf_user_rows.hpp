@@ -135,8 +135,6 @@ __host__ __device__ inline unsigned mlf_user_rows_derive_lds_bytes(int d, int nq
   return bytes <= MLF_USER_ROWS_LDS_BUDGET ? (unsigned)bytes : 0u;
 }
 
-#if defined(MLF_USER_ROWS_HOST) || (defined(MLF_USER_GATE_DERIVED) && MLF_USER_GATE_DERIVED)
-// (for the library and the gate-derived programs only: the text every other program compiles is what it was)
 // bytes of dynamic LDS a launch of mlf_user_rows_tregion_derived needs (0: the direct form): 64 u rows and, where a transform
 // writes p, 64 p rows of pitch d | 1, and 64 q rows of pitch nq | 1
 __host__ __device__ inline unsigned mlf_user_rows_gate_derived_lds_bytes(int d, int nq, bool has_p_buffer) {
@@ -149,7 +147,6 @@ __host__ __device__ inline unsigned mlf_user_rows_gate_derived_lds_bytes(int d, 
 __host__ __device__ inline unsigned mlf_user_rows_sum_gate_derived_lds_bytes(int d, int nq, bool has_p_buffer) {
   return mlf_user_rows_sum_lds_bytes(d, has_p_buffer) + (unsigned)nq * 8u;
 }
-#endif
 
 #ifndef MLF_USER_ROWS_HOST
 
@@ -174,13 +171,29 @@ __host__ __device__ inline unsigned mlf_user_rows_sum_gate_derived_lds_bytes(int
 #if MLF_USER_GATE_DERIVED
 #define MLF_TREGION_SPLIT_ROW
 #endif
+// The two optional tails of an entry's parameter list, the gate's five and behind them the q pair of a gate over derived
+// parameters, and the entry's name.  Entries that differ in their parameter lists differ in their names: a code object loaded
+// as another variant has no such entry (mlf_usermodel_create_variant) instead of a launch with the wrong arguments
 #if MLF_USER_TREGION
 #include "mlf_tregion_dev.hpp"
-// the two forms differ in their parameter lists, so they differ in their names: a code object loaded as the other variant has
-// no such entry (mlf_usermodel_create_variant) instead of a launch with the wrong arguments
-#define MLF_USER_ROWS_ENTRY mlf_user_rows_tregion
+#define MLF_USER_GATE_PARAMS                                                                                                  \
+  , const double *__restrict__ tr_A, const double *__restrict__ tr_ctr, const double *__restrict__ tr_fixed, double tr_enlarge, \
+      unsigned char *member2
+#define MLF_USER_GATE_ARGS , tr_A, tr_ctr, tr_fixed, tr_enlarge, member2
 #else
-#define MLF_USER_ROWS_ENTRY mlf_user_rows
+#define MLF_USER_GATE_PARAMS
+#define MLF_USER_GATE_ARGS
+#endif
+#if MLF_USER_GATE_DERIVED
+#define MLF_USER_Q_PARAMS , int nq, double *q_scratch
+#define MLF_USER_ENTRY(base) base##_tregion_derived
+#else
+#define MLF_USER_Q_PARAMS
+#if MLF_USER_TREGION
+#define MLF_USER_ENTRY(base) base##_tregion
+#else
+#define MLF_USER_ENTRY(base) base
+#endif
 #endif
 
 namespace mlf_user_detail {
@@ -190,10 +203,9 @@ constexpr int kLoads = 16;
 
 __device__ inline double neg_inf() { return -__builtin_inf(); }
 
-// rows of one wave: global block [0, total) -> LDS rows of pitch d + 1.  Element e = row * d + col; (row, col) of the lane's
+// rows of one wave: global block [0, total) -> LDS rows of pitch ds >= d.  Element e = row * d + col; (row, col) of the lane's
 // next element is stepped by 64 elements at a time (no integer division per element).
-__device__ inline void stage_in(const double *src, int total, int d, double *lds, int lane) {
-  const int ds = d + 1;
+__device__ inline void stage_in(const double *src, int total, int d, int ds, double *lds, int lane) {
   const int qstep = 64 / d, rstep = 64 % d;
   int row = lane / d, col = lane % d;
   for (int e0 = 0; e0 < total; e0 += 64 * kLoads) {
@@ -217,9 +229,8 @@ __device__ inline void stage_in(const double *src, int total, int d, double *lds
   }
 }
 
-// LDS rows of pitch d + 1 -> global block [0, total); only the rows whose bit is set in `rows` are written
-__device__ inline void stage_out(double *dst, int total, int d, const double *lds, unsigned long long rows, int lane) {
-  const int ds = d + 1;
+// LDS rows of pitch ds >= d -> global block [0, total); only the rows whose bit is set in `rows` are written
+__device__ inline void stage_out(double *dst, int total, int d, int ds, const double *lds, unsigned long long rows, int lane) {
   const int qstep = 64 / d, rstep = 64 % d;
   int row = lane / d, col = lane % d;
   for (int e = lane; e < total; e += 64) {
@@ -232,48 +243,6 @@ __device__ inline void stage_out(double *dst, int total, int d, const double *ld
     }
   }
 }
-
-#if MLF_USER_GATE_DERIVED
-// stage_in / stage_out at the caller's row pitch ds >= d (the gate-derived form: an odd pitch for every d).  Functions of their
-// own, so that the text the other programs compile -- and with it their code objects -- stays what it was.
-__device__ inline void stage_in_pitch(const double *src, int total, int d, int ds, double *lds, int lane) {
-  const int qstep = 64 / d, rstep = 64 % d;
-  int row = lane / d, col = lane % d;
-  for (int e0 = 0; e0 < total; e0 += 64 * kLoads) {
-    double v[kLoads];
-#pragma unroll
-    for (int i = 0; i < kLoads; ++i) {
-      const int e = e0 + 64 * i + lane;
-      v[i] = e < total ? src[e] : 0.0;
-    }
-#pragma unroll
-    for (int i = 0; i < kLoads; ++i) {
-      const int e = e0 + 64 * i + lane;
-      if (e < total) lds[row * ds + col] = v[i];
-      row += qstep;
-      col += rstep;
-      if (col >= d) {
-        col -= d;
-        row += 1;
-      }
-    }
-  }
-}
-
-__device__ inline void stage_out_pitch(double *dst, int total, int d, int ds, const double *lds, unsigned long long rows, int lane) {
-  const int qstep = 64 / d, rstep = 64 % d;
-  int row = lane / d, col = lane % d;
-  for (int e = lane; e < total; e += 64) {
-    if ((rows >> row) & 1ull) dst[e] = lds[row * ds + col];
-    row += qstep;
-    col += rstep;
-    if (col >= d) {
-      col -= d;
-      row += 1;
-    }
-  }
-}
-#endif
 
 __device__ inline void transform_row(const double *x, double *y, int d, const double *aux, long long naux) {
 #if MLF_USER_HAS_TRANSFORM
@@ -282,6 +251,19 @@ __device__ inline void transform_row(const double *x, double *y, int d, const do
   (void)aux;
   (void)naux;
   for (int k = 0; k < d; ++k) y[k] = x[k];
+#endif
+}
+
+// the gate of a row whose p is ready (x): true without a gate; over derived parameters q = mlf_user_derived(p) first, then the
+// t-region test over [p | q] (q, nq: read in that mode alone)
+__device__ inline bool gate_row(const double *x, int d, double *q, int nq, const double *aux, long long naux MLF_USER_GATE_PARAMS) {
+#if MLF_USER_GATE_DERIVED
+  mlf_user_derived(x, d, q, nq, aux, naux);
+  return mlf_tregion_inside_split(x, d, q, nq, tr_A, tr_ctr, tr_fixed, tr_enlarge);
+#elif MLF_USER_TREGION
+  return mlf_tregion_inside(x, d, tr_A, tr_ctr, tr_fixed, tr_enlarge);
+#else
+  return true;
 #endif
 }
 
@@ -303,7 +285,7 @@ extern "C" __global__ __launch_bounds__(64) void mlf_user_derive_rows(const doub
     const int ds = d + 1, qs = nq + 1;
     double *a = mlf_user_lds;        // 64 rows of p
     double *b = a + 64 * ds;         // 64 rows of q
-    stage_in(p + j0 * d, nrows * d, d, a, lane);
+    stage_in(p + j0 * d, nrows * d, d, ds, a, lane);
     __syncthreads();
     if (lane < nrows) mlf_user_derived(a + lane * ds, d, b + lane * qs, nq, aux, naux);
     __syncthreads();
@@ -329,80 +311,24 @@ extern "C" __global__ __launch_bounds__(64) void mlf_user_derive_rows(const doub
   }
 }
 
-#elif MLF_USER_GATE_DERIVED && !MLF_USER_SUM
-
-extern "C" __global__ __launch_bounds__(64) void mlf_user_rows_tregion_derived(
-    const double *u, long long n, int d, const unsigned char *member, const double *aux, long long naux, double *p, double *L,
-    const double *__restrict__ tr_A, const double *__restrict__ tr_ctr, const double *__restrict__ tr_fixed, double tr_enlarge,
-    unsigned char *member2, int nq, double *q_scratch) {
-  using namespace mlf_user_detail;
-  const int lane = threadIdx.x;
-  const long long j0 = (long long)blockIdx.x * 64;
-  if (j0 >= n) return;
-  const long long left = n - j0;
-  const int nrows = left >= 64 ? 64 : (int)left;
-  const long long i = j0 + lane;
-  const bool mine = lane < nrows && (member == nullptr || member[i] != 0);
-  const unsigned long long live = __ballot(mine);
-  if (live == 0) {   // no member row in this block: nothing is read
-    if (lane < nrows) {
-      if (L != nullptr) L[i] = neg_inf();
-      member2[i] = 0;
-    }
-    return;
-  }
-  double like = neg_inf();
-  bool pass = false;
-  const bool p_buffer = p != nullptr && MLF_USER_HAS_TRANSFORM;
-  if (mlf_user_rows_gate_derived_lds_bytes(d, nq, p_buffer) != 0) {
-    extern __shared__ __attribute__((aligned(16))) double mlf_user_lds[];
-    const int ds = d | 1, qs = nq | 1;              // odd pitches: lane = row accesses without bank conflicts
-    double *a = mlf_user_lds;                       // 64 rows of u
-    double *b = p_buffer ? a + 64 * ds : a;         // 64 rows of p (the u rows themselves without a transform)
-    double *c = b + 64 * ds;                        // 64 rows of q
-    stage_in_pitch(u + j0 * d, nrows * d, d, ds, a, lane);
-    __syncthreads();
-    if (mine) {
-      const double *x = a + lane * ds;
-      if (p_buffer) {
-        double *y = b + lane * ds;
-        transform_row(x, y, d, aux, naux);
-        x = y;
-      }
-      double *q = c + lane * qs;
-      mlf_user_derived(x, d, q, nq, aux, naux);
-      pass = mlf_tregion_inside_split(x, d, q, nq, tr_A, tr_ctr, tr_fixed, tr_enlarge);
-      if (L != nullptr && pass) like = mlf_user_loglike(x, d, aux, naux);
-    }
-    __syncthreads();
-    if (p != nullptr) stage_out_pitch(p + j0 * d, nrows * d, d, ds, b, live, lane);
-  } else if (mine) {
-    const double *x = u + i * d;
-    if (p != nullptr) {
-      double *y = p + i * d;
-      transform_row(x, y, d, aux, naux);
-      x = y;
-    }
-    double *q = q_scratch + i * nq;
-    mlf_user_derived(x, d, q, nq, aux, naux);
-    pass = mlf_tregion_inside_split(x, d, q, nq, tr_A, tr_ctr, tr_fixed, tr_enlarge);
-    if (L != nullptr && pass) like = mlf_user_loglike(x, d, aux, naux);
-  }
-  if (lane < nrows) member2[i] = pass ? 1 : 0;   // pass implies mine
-  if (L != nullptr && lane < nrows) L[i] = like;
-}
-
 #elif !MLF_USER_SUM
 
-extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const double *u, long long n, int d, const unsigned char *member,
-                                                                const double *aux, long long naux, double *p, double *L
-#if MLF_USER_TREGION
-                                                                ,
-                                                                const double *__restrict__ tr_A, const double *__restrict__ tr_ctr,
-                                                                const double *__restrict__ tr_fixed, double tr_enlarge,
-                                                                unsigned char *member2
-#endif
-) {
+namespace mlf_user_detail {
+
+// the step of a thread-per-row entry whose p row is ready (x): (derived q ->) gate -> the likelihood if the row passes and L is
+// asked for, else -inf
+__device__ inline double evaluate_row(const double *x, int d, double *q, int nq, const double *aux, long long naux, bool want_L,
+                                      bool &pass MLF_USER_GATE_PARAMS) {
+  pass = gate_row(x, d, q, nq, aux, naux MLF_USER_GATE_ARGS);
+  return want_L && pass ? mlf_user_loglike(x, d, aux, naux) : neg_inf();
+}
+
+}  // namespace mlf_user_detail
+
+// the thread-per-row entries: mlf_user_rows, mlf_user_rows_tregion and mlf_user_rows_tregion_derived
+extern "C" __global__ __launch_bounds__(64) void MLF_USER_ENTRY(mlf_user_rows)(
+    const double *u, long long n, int d, const unsigned char *member, const double *aux, long long naux, double *p,
+    double *L MLF_USER_GATE_PARAMS MLF_USER_Q_PARAMS) {
   using namespace mlf_user_detail;
   const int lane = threadIdx.x;
   const long long j0 = (long long)blockIdx.x * 64;
@@ -419,17 +345,26 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const doubl
 #endif
     return;
   }
-  double like = neg_inf();
-#if MLF_USER_TREGION
-  bool pass = false;
-#endif
   const bool p_buffer = p != nullptr && MLF_USER_HAS_TRANSFORM;
-  if (mlf_user_rows_lds_bytes(d, p_buffer) != 0) {
+  // what the gate over derived parameters adds to the gated form: odd pitches (lane = row accesses without bank conflicts for
+  // every d) and a q row per lane, in LDS behind the p rows or, on the direct form, in q_scratch (without it q is a pointer that
+  // gate_row never reads)
+#if MLF_USER_GATE_DERIVED
+  const int ds = d | 1, qs = nq | 1;
+  const unsigned staged = mlf_user_rows_gate_derived_lds_bytes(d, nq, p_buffer);
+#else
+  const int ds = d + 1, qs = 0, nq = 0;
+  double *const q_scratch = nullptr;
+  const unsigned staged = mlf_user_rows_lds_bytes(d, p_buffer);
+#endif
+  double like = neg_inf();
+  bool pass = false;
+  if (staged != 0) {
     extern __shared__ __attribute__((aligned(16))) double mlf_user_lds[];
-    const int ds = d + 1;
     double *a = mlf_user_lds;                       // 64 rows of u
     double *b = p_buffer ? a + 64 * ds : a;         // 64 rows of p (the u rows themselves without a transform)
-    stage_in(u + j0 * d, nrows * d, d, a, lane);
+    double *c = b + 64 * ds;                        // 64 rows of q
+    stage_in(u + j0 * d, nrows * d, d, ds, a, lane);
     __syncthreads();
     if (mine) {
       const double *x = a + lane * ds;
@@ -438,15 +373,10 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const doubl
         transform_row(x, y, d, aux, naux);
         x = y;
       }
-#if MLF_USER_TREGION
-      pass = mlf_tregion_inside(x, d, tr_A, tr_ctr, tr_fixed, tr_enlarge);
-      if (L != nullptr && pass) like = mlf_user_loglike(x, d, aux, naux);
-#else
-      if (L != nullptr) like = mlf_user_loglike(x, d, aux, naux);
-#endif
+      like = evaluate_row(x, d, c + lane * qs, nq, aux, naux, L != nullptr, pass MLF_USER_GATE_ARGS);
     }
     __syncthreads();
-    if (p != nullptr) stage_out(p + j0 * d, nrows * d, d, b, live, lane);
+    if (p != nullptr) stage_out(p + j0 * d, nrows * d, d, ds, b, live, lane);
   } else if (mine) {
     const double *x = u + i * d;
     if (p != nullptr) {
@@ -454,12 +384,7 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const doubl
       transform_row(x, y, d, aux, naux);
       x = y;
     }
-#if MLF_USER_TREGION
-    pass = mlf_tregion_inside(x, d, tr_A, tr_ctr, tr_fixed, tr_enlarge);
-    if (L != nullptr && pass) like = mlf_user_loglike(x, d, aux, naux);
-#else
-    if (L != nullptr) like = mlf_user_loglike(x, d, aux, naux);
-#endif
+    like = evaluate_row(x, d, q_scratch + i * nq, nq, aux, naux, L != nullptr, pass MLF_USER_GATE_ARGS);
   }
 #if MLF_USER_TREGION
   if (lane < nrows) member2[i] = pass ? 1 : 0;   // pass implies mine
@@ -467,40 +392,24 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_ROWS_ENTRY(const doubl
   if (L != nullptr && lane < nrows) L[i] = like;
 }
 
-#else  // MLF_USER_SUM
+#else  // MLF_USER_SUM: the wave-per-row entries
 
 #ifdef MLF_USER_NSUMS
 static_assert(MLF_USER_NSUMS >= 1 && MLF_USER_NSUMS <= 8, "MLF_USER_NSUMS: 1 to 8 sums");
-#if MLF_USER_GATE_DERIVED
-#define MLF_USER_SUM_ENTRY mlf_user_rows_sums_tregion_derived
-#elif MLF_USER_TREGION
-#define MLF_USER_SUM_ENTRY mlf_user_rows_sums_tregion
+#define MLF_USER_SUM_ENTRY MLF_USER_ENTRY(mlf_user_rows_sums)
 #else
-#define MLF_USER_SUM_ENTRY mlf_user_rows_sums
-#endif
-#elif MLF_USER_GATE_DERIVED
-#define MLF_USER_SUM_ENTRY mlf_user_rows_sum_tregion_derived
-#elif MLF_USER_TREGION
-#define MLF_USER_SUM_ENTRY mlf_user_rows_sum_tregion
-#else
-#define MLF_USER_SUM_ENTRY mlf_user_rows_sum
+#define MLF_USER_SUM_ENTRY MLF_USER_ENTRY(mlf_user_rows_sum)
 #endif
 
-extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(const double *u, long long n, int d, const unsigned char *member,
-                                                               const double *aux, long long naux, double *p, double *L,
-                                                               long long nterms
-#if MLF_USER_TREGION
-                                                               ,
-                                                               const double *__restrict__ tr_A, const double *__restrict__ tr_ctr,
-                                                               const double *__restrict__ tr_fixed, double tr_enlarge,
-                                                               unsigned char *member2
-#endif
-#if MLF_USER_GATE_DERIVED
-                                                               ,
-                                                               int nq, double *q_scratch
-#endif
-) {
+extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(
+    const double *u, long long n, int d, const unsigned char *member, const double *aux, long long naux, double *p, double *L,
+    long long nterms MLF_USER_GATE_PARAMS MLF_USER_Q_PARAMS) {
   using namespace mlf_user_detail;
+#if MLF_USER_GATE_DERIVED
+  (void)q_scratch;   // (the direct default form's: here q lives in LDS, behind the p row)
+#else
+  const int nq = 0;
+#endif
   const int lane = threadIdx.x;
   const long long i = blockIdx.x;   // one wave, one row
   if (i >= n) return;
@@ -526,29 +435,21 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(const double
     __syncthreads();   // the other lanes read lane 0's p row from LDS
   }
 #endif
-#if MLF_USER_GATE_DERIVED
-  (void)q_scratch;       // (the direct default form's: here q lives in LDS)
-  double *q = b + d;     // the q row, behind the p row (behind the u row where no transform writes one)
+#if MLF_USER_TREGION
   int inside = 0;
-  if (lane == 0) {
-    mlf_user_derived(b, d, q, nq, aux, naux);
-    inside = mlf_tregion_inside_split(b, d, q, nq, tr_A, tr_ctr, tr_fixed, tr_enlarge) ? 1 : 0;
-  }
-  const bool pass = __builtin_amdgcn_readfirstlane(inside) != 0;   // all 64 lanes are active: lane 0 is the first
-#elif MLF_USER_TREGION
-  int inside = 0;
-  if (lane == 0) inside = mlf_tregion_inside(b, d, tr_A, tr_ctr, tr_fixed, tr_enlarge) ? 1 : 0;
+  if (lane == 0) inside = gate_row(b, d, b + d, nq, aux, naux MLF_USER_GATE_ARGS) ? 1 : 0;   // (q behind the p row)
   const bool pass = __builtin_amdgcn_readfirstlane(inside) != 0;   // all 64 lanes are active: lane 0 is the first
 #else
+  (void)nq;
   const bool pass = true;
 #endif
   if (p != nullptr) {
     double *dst = p + i * d;
     for (int e = lane; e < d; e += 64) dst[e] = b[e];
   }
-#ifdef MLF_USER_NSUMS
-  double s = neg_inf();   // L: the finish function of the sums
+  double s = neg_inf();
   if (L != nullptr && pass) {
+#ifdef MLF_USER_NSUMS
     double acc[MLF_USER_NSUMS];   // registers: every loop over j is unrolled
 #pragma unroll
     for (int j = 0; j < MLF_USER_NSUMS; ++j) acc[j] = 0.0;
@@ -564,16 +465,13 @@ extern "C" __global__ __launch_bounds__(64) void MLF_USER_SUM_ENTRY(const double
       for (int j = 0; j < MLF_USER_NSUMS; ++j) acc[j] = acc[j] + __shfl_xor(acc[j], m);
     }
     s = mlf_user_loglike_finish(acc, MLF_USER_NSUMS, b, d, aux, naux);   // every lane, the same arguments; lane 0's is L
-  }
 #else
-  double s = neg_inf();
-  if (L != nullptr && pass) {
     s = 0.0;
     for (long long k = lane; k < nterms; k += 64) s = s + mlf_user_loglike_term(b, d, aux, naux, k);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m);
-  }
 #endif
+  }
   if (lane == 0) {
     if (L != nullptr) L[i] = s;
 #if MLF_USER_TREGION

@@ -366,19 +366,23 @@ class Form(collections.namedtuple("Form", "has_transform gated summed nsums deri
                 (" sum" if self.summed else "") + ("" if self.nsums is None else " sums=%d" % self.nsums) +
                 (" derived" if self.derived == "derive" else "") + ("" if self.ncov is None else " cov=%d" % self.ncov))
 
+    @property
+    def headers(self):
+        """the headers the form's program includes, in the order a cache key hashes them"""
+        return (HEADER if self.ncov is None else COV_HEADER,) + ((GATE_HEADER,) if self.gated else ())
+
 
 DERIVE = Form(False, derived="derive")
 
 
 def _cache_key(source, form, *flags, **more):
-    """sha256 over the source, the options and the headers the program includes (the gate's only where it is gated).  `form`: a
+    """sha256 over the source, the options and the headers the program includes (``Form.headers``).  `form`: a
     Form, or the arguments of one (``has_transform, gated, summed, nsums``)"""
     if not isinstance(form, Form):
         form = Form(form, *flags, **more)
     h = hashlib.sha256()
     header = b""
-    main = HEADER if form.ncov is None else COV_HEADER      # (a covariance program includes its own header instead)
-    for path in (main, GATE_HEADER) if form.gated else (main,):
+    for path in form.headers:
         with open(path, "rb") as fh:
             header += fh.read()
     options = repr((COMPILE_OPTIONS, form.has_transform)) + form.tags
