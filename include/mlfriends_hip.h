@@ -121,6 +121,10 @@ int mlf_get_option(const char *name, long long *value);
  * that the next launch of every kernel grants again -- what a second device would need; *grants_so_far (optional) receives
  * the number of grants issued by the process up to now. */
 int mlf_debug_forget_grants(unsigned long long *grants_so_far);
+/* test hook: on != 0 sends every batch of sampling method 3 through the kernel for rows too wide for the staged one
+ * (k_generate_around_points_wide), whatever its dimensionality; 0 = by the device's per-workgroup LDS limit again.  The draws
+ * are the same bit for bit, which is what the hook lets a test see below the limit. */
+int mlf_debug_around_points_wide(int on);
 int mlf_option_name(int index, char *buf, size_t buflen);
 
 /* ---- K1: find_nearby -- ultranest/mlfriends.pyx:143-183 -----------------------------------

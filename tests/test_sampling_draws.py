@@ -8,6 +8,11 @@ What runs: every instantiation of k_generate_ellipsoid<CH> and k_rows_affine<CH>
 128 dimensions (k_generate_ball -> k_prep -> k_center_and_cube; k_untransform_rows), the fmod branch of rows_times_matrix
 in two CH classes, counters across a multiple of 2^32 with a key whose high word is set, and the second trip of
 k_scan_counts (more than 262 144 rows) bit for bit.  Each case prints the rows it compared and its undecided draws.
+
+Above 130 dimensions (the last section): method 3 at d = 131, 200, 317, 318, 512 and 1024 -- 317 | 318 is where the 64 staged
+rows of k_generate_around_points outgrow the LDS of an MI355X workgroup and k_generate_around_points_wide takes over --, the
+two kernels against each other bit for bit below that seam, method 1 at d = 200 and 512, the batches of methods 1 and 2 that
+leave no row at these dimensions, and a refill at d = 318.
 """
 import functools
 
@@ -253,3 +258,178 @@ def test_refill_past_one_scan_trip_is_the_host_pipeline(d, thin):
     err = np.abs(Lgot.astype(L.ref.dtype) - L.ref[keep]).astype(np.float64)
     assert (err <= LR.RTOL * L.scale[keep]).all(), float((err / L.scale[keep]).max())
     print("refill d=%d thin=%d n=%d: %d rows compared, 0 undecided draws" % (d, thin, NSCAN, len(u)))
+
+
+# ------------------------------------------------------------------------------------------------ 131 ... 1024 dimensions
+NW = 449                                    # seven workgroups of 64 rows and a ragged one of 1
+D_POINTS_WIDE = (131, 200, 317, 318, 512)   # 317 | 318: the last row width k_generate_around_points stages in the 160 KiB of LDS
+                                            # of an MI355X workgroup, and the first of k_generate_around_points_wide
+
+
+@functools.lru_cache(maxsize=None)
+def wide_region(kind, d, nlive=None):
+    """Above 130 dimensions the cloud of live_points (spread 0.08) and the bootstrap of build_region decide nothing in: the
+    bootstrapped enlargement of 700 live points cuts off 446 of 449 method 3 draws at d = 131 and 324 at d = 200 (the
+    reference alone, on the CPU).  So: spread 0.02, 700 live points up to d = 318 and 1100 above, and radius and enlargement set
+    by hand, as the driver sets them -- radius^2 = 1.05 x the largest nearest-neighbour distance^2, enlargement = 6 x the
+    largest Mahalanobis value of a live point.  With these the reference decides 449 of 449 method 3 draws in and leaves
+    none undecided at every dimension used here (assert_caps, below, on the region itself), every method 1 draw of the
+    ellipsoid alone in, and no method 1 or method 2 draw of the MLFriends region in."""
+    import ultranest_amd.mlfriends as m
+    u, rng = live_points(d, 600 + d, nlive=nlive or (700 if d <= 318 else 1100), spread=0.02)
+    region = getattr(m, kind)(u, S.affine_layer(u))
+    t = region.unormed
+    norm2 = (t * t).sum(axis=1)
+    dist2 = norm2[:, None] + norm2[None, :] - 2 * np.dot(t, t.T)
+    np.fill_diagonal(dist2, np.inf)
+    region.maxradiussq = 1.05 * float(dist2.min(axis=1).max()) if region._uses_scan() else 1e300
+    region.enlarge = 1.0                    # (create_ellipsoid does not read it; it only wants it set)
+    region.create_ellipsoid()
+    dl = u - region.ellipsoid_center
+    region.enlarge = 6 * float((np.dot(dl, region.ellipsoid_invcov) * dl).sum(axis=1).max())
+    return region
+
+
+@gpu
+@pytest.mark.parametrize("d", D_POINTS_WIDE)
+def test_draws_around_the_live_points_above_130_dimensions(d):
+    """k_generate_around_points up to d = 317 and k_generate_around_points_wide from 318 on; k_untransform_rows"""
+    ref, got = check_draws(wide_region("MLFriends", d), 3, NW, seed=31 + d, label="around points, wide")
+    assert len(np.unique(ref.which)) > 50 and ref.decided_in == NW
+
+
+@gpu
+@pytest.mark.parametrize("d", [200, 512])
+def test_wrapping_ellipsoid_draws_above_130_dimensions(d):
+    """k_generate_ball -> k_prep wide -> k_center_and_cube"""
+    ref, got = check_draws(wide_region("RobustEllipsoidRegion", d), 1, NW, seed=17 + d, label="ellipsoid region, wide")
+    assert (got > 0).all() and (got < 1).all()
+
+
+@gpu
+@pytest.mark.parametrize("d", [1, 2, 3, 5, 64, 129, 256, 257, 317])
+def test_the_two_forms_of_the_draws_around_the_live_points_are_one_function(d):
+    """k_generate_around_points_wide below the LDS limit, where the staged kernel runs (the library's test hook sends the
+    batch through it): the same rows and the same offset, bit for bit.  d = 1 ... 3: fewer columns than the four lanes that
+    add up |z|^2; 256 | 257: one piece of the row, and one more column; an odd d: the unused sine of the last pair."""
+    from ultranest_amd import _lib
+    region = points_region(d) if d <= 129 else wide_region("MLFriends", d)
+    n = N if d <= 129 else NW
+    staged, nxt = device_draw(region, 3, n, 31 + d, 3)
+    _lib.around_points_wide(True)
+    try:
+        wide, wide_nxt = device_draw(region, 3, n, 31 + d, 3)
+    finally:
+        _lib.around_points_wide(False)
+    assert len(staged) > 50 and wide_nxt == nxt
+    assert wide.shape == staged.shape and np.array_equal(wide, staged)
+    print("two forms method 3 d=%d n=%d: %d rows compared bit for bit" % (d, n, len(staged)))
+
+
+def check_no_draws(region, method, n, seed, offset, label):
+    """a batch of which the reference decides every draw out: no row, and the reference's next offset"""
+    ref = S.Reference(S.Geometry.of_region(region), method, n, seed, offset)
+    assert ref.decided_in == 0 and ref.undecided == 0, (ref.decided_in, ref.undecided)
+    got, nxt = device_draw(region, method, n, seed, offset)
+    assert nxt == ref.next_offset and got.shape == (0, region.u.shape[1]), got.shape
+    print("%s method %d d=%d n=%d: 0 rows compared (0 decided in), 0 undecided draws" % (label, method, region.u.shape[1], n))
+
+
+@gpu
+def test_wrapping_ellipsoid_draws_of_a_friends_region_at_200_dimensions():
+    """a uniform draw of the ellipsoid lies in no ball at this dimension"""
+    check_no_draws(wide_region("MLFriends", 200), 1, NW, 17, 0, "friends region, wide")
+
+
+@gpu
+@pytest.mark.parametrize("d", [129, 318])
+def test_draws_in_the_transformed_bounding_box_above_128_dimensions(d):
+    """the padded box leaves the cube and no draw lies in a ball: the generator, the neighbour scan and the empty compaction"""
+    check_no_draws(wide_region("MLFriends", d), 2, NW, 23, 77, "t-space box, wide")
+
+
+@gpu
+def test_draws_around_the_live_points_at_the_largest_dimension():
+    """d = 1024 = MLF_MAX_DIM, 129 draws.  Whitening all 1300 live points in long double takes half a minute, so the verdicts
+    are taken in binary64 on the host, of inputs for which none of them is close: every draw has multiplicity 1 and margins
+    of at least 1e-6 of their scales (a thousand bands) to the cube, the ellipsoid and the nearest ball it is not in.  Its OWN
+    ball it cannot leave by that much: the draw lies at r U^(1/d) from the live point, a shell of 2 (-ln U) / d of r^2 under the
+    surface, and the scale of the test is 2 r (|s_t| + |s_l|) = 17 000 here (the whitened coordinates are sums of 1024 terms
+    taken positive), so 1e-6 of it would ask for U < 0.013 in all 129 draws.  The seed is the one of 1000 ... 1199 whose
+    largest radial uniform is smallest (0.953): ten bands (1e-8 of the scale) there.  Every draw is then a row of the
+    device, compared with the reference restricted to the drawn live points."""
+    from ultranest_amd import kernels
+    d, n, seed = 1024, 129, 1111
+    region = wide_region("MLFriends", d, 1300)
+    g = S.Geometry.of_region(region)
+    layer, r2 = region.transformLayer, region.maxradiussq
+    t64, thin, which, nxt = philox.around_points(seed, 0, n, d, region.unormed, r2)
+    mult = np.empty(n, dtype=np.int64)
+    kernels.count_nearby(region.unormed, t64, r2, mult)
+    assert (mult == 1).all() and (thin < 1).all()
+    w64 = layer.untransform(t64)
+    assert np.logical_and(w64 > 0, w64 < 1).all() and region.inside_ellipsoid(w64).all()
+    t, ts, thin_ref, which_ref, nxt_ref = S.around_draws(g, seed, 0, n)
+    assert nxt_ref == nxt and np.array_equal(which_ref, which) and np.array_equal(thin_ref, thin)
+    w, ws = S.untransform(S.REFERENCE, g, t, ts)
+    # the margins, in the scales of sampling_reference's verdicts
+    assert (np.minimum(w64, 1 - w64) >= 1e-6 * ws).all()
+    dl = w64 - g.center
+    Pd = np.dot(dl, g.invcov)
+    ell_scale = 2 * ((ws + np.abs(g.center)) * np.abs(Pd)).sum(axis=1) + (np.dot(np.abs(dl), np.abs(g.invcov)) * np.abs(dl)).sum(axis=1)
+    assert (g.enlarge - (Pd * dl).sum(axis=1) >= 1e-6 * ell_scale).all()
+    live_scale = np.sqrt((np.dot(np.abs(g.u) + np.abs(g.ctr), np.abs(g.T)) ** 2).sum(axis=1))
+    t_scale = np.sqrt((ts ** 2).sum(axis=1))
+    for i in range(n):
+        dist2 = ((region.unormed - t64[i]) ** 2).sum(axis=1)
+        own = np.arange(len(dist2)) == which[i]
+        margin = np.where(own, r2 - dist2, dist2 - r2)
+        assert (margin >= np.where(own, 1e-8, 1e-6) * (2 * np.sqrt(dist2) * (t_scale[i] + live_scale) + dist2)).all(), i
+    got, got_nxt = device_draw(region, 3, n, seed, 0)
+    assert got_nxt == nxt and got.shape == (n, d)
+    worst = S.excess(got, w, ws)
+    print("around points, widest method 3 d=%d n=%d: %d rows compared, 0 undecided draws (largest error %.3g of the tolerance)"
+          % (d, n, len(got), worst))
+    assert worst <= 1.0
+
+
+@gpu
+@pytest.mark.parametrize("user", [False, True])
+def test_refill_around_the_live_points_at_318_dimensions_is_the_host_pipeline(user):
+    """region.refill with method 3 on k_generate_around_points_wide, identity transform and a Gaussian likelihood, built in
+    and as a user model: u and p are the rows of sample() that the callbacks keep, bit for bit; L within 1e-12 * scale of the
+    long double Gaussian, the threshold clear of every value by the band"""
+    from ultranest_amd import likelihoods, usermodels
+    from ultranest_amd.regions import DeviceRNG
+    d, sigma, seed = 318, 0.1, 41
+    region = wide_region("MLFriends", d)
+    rows, nxt = device_draw(region, 3, NW, seed, 5)
+    assert len(rows) > 400
+    if user:
+        model = usermodels.gauss(d, sigma)
+        loglike, centers = model.loglike, usermodels.gauss_centers(d, sigma)
+    else:
+        loglike = likelihoods.GaussLikelihood(0.5, sigma, d)
+        centers = loglike.centers
+    L = LR.Reference("gauss", rows, centers, sigma, with_mpmath=False)
+    order = np.sort(L.ref)
+    Lmin = float((order[len(order) // 2] + order[len(order) // 2 + 1]) / 2)
+    assert (np.abs(L.ref - Lmin) > S.BAND * L.scale).all(), "a likelihood within 1e-9 * scale of the threshold: choose another Lmin"
+    keep = L.ref > Lmin
+    p_host = likelihoods.identity_transform(rows)
+    L_host = loglike(p_host)
+    assert np.array_equal(L_host > Lmin, keep)
+    region.device_rng = DeviceRNG(seed)
+    region.device_rng.offset = 5
+    region.current_sampling_method = region.sample_from_points
+    try:
+        u, p, Lgot, nc = region.refill(NW, Lmin, likelihoods.identity_transform, loglike)
+        assert region.device_rng.offset == nxt and nc == len(rows)
+    finally:
+        region.device_rng = None
+        if user:
+            model.close()
+    assert u.shape == (int(keep.sum()), d) and np.array_equal(u, rows[keep]) and np.array_equal(p, p_host[keep])
+    err = np.abs(Lgot.astype(L.ref.dtype) - L.ref[keep]).astype(np.float64)
+    assert (err <= LR.RTOL * L.scale[keep]).all(), float((err / L.scale[keep]).max())
+    print("refill method 3 d=%d user=%d n=%d: %d rows compared, 0 undecided draws" % (d, user, NW, len(u)))

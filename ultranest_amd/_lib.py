@@ -30,6 +30,7 @@ SIGNATURES = {
     "mlf_set_option": [ctypes.c_char_p, ctypes.c_longlong],
     "mlf_get_option": [ctypes.c_char_p, _vp],
     "mlf_debug_forget_grants": [_vp],
+    "mlf_debug_around_points_wide": [ctypes.c_int],
     "mlf_region_get_option": [_vp, ctypes.c_char_p, _vp],
     "mlf_find_nearby": [_vp, _sz, _vp, _sz, _sz, _dbl, _vp],
     "mlf_count_nearby": [_vp, _sz, _vp, _sz, _sz, _dbl, _vp],
@@ -281,6 +282,12 @@ def forget_grants():
     n = ctypes.c_ulonglong(0)
     check(lib().mlf_debug_forget_grants(ctypes.byref(n)))
     return int(n.value)
+
+
+def around_points_wide(on):
+    """Test hook (mlf_debug_around_points_wide): sampling method 3 through its wide kernel at every dimensionality (True), or
+    chosen by the device's LDS limit (False, the default).  The draws do not depend on it."""
+    check(lib().mlf_debug_around_points_wide(int(bool(on))))
 
 
 def draw_selection(rng, npoints, nbootstraps):

@@ -18,6 +18,11 @@ int mlf_debug_forget_grants(unsigned long long *grants_so_far) {
   return 0;
 }
 
+int mlf_debug_around_points_wide(int on) {
+  force_around_points_wide(on != 0);
+  return 0;
+}
+
 int mlf_debug_philox(uint64_t seed, unsigned stream, size_t nblocks, uint32_t *out) {
   if (!out) return fail_arg(MLF_E_BADARG, "null pointer");
   if (nblocks == 0) return 0;

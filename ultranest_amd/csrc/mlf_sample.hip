@@ -310,6 +310,68 @@ __global__ __launch_bounds__(256) void k_generate_around_points(double *t, doubl
   }
 }
 
+// The same draws for rows too wide for the 64 staged rows of k_generate_around_points: one WAVE per row, four rows per workgroup,
+// the row passing through LDS in pieces of 256 columns (8 KiB per workgroup whatever d is).  Same counters (stream 6, npairs + 2
+// blocks per proposal: block 0 = live index + radial uniform, block 1 = thinning uniform, blocks 2.. = Box-Muller pairs) and the
+// same operations on every element.  |z|^2 in the staged kernel's order: lane p < 4 adds up the squares of columns p, p + 4,
+// p + 8, ... in ascending order (a piece starts at a multiple of 4, so the lane keeps its columns from piece to piece), then
+// (s0 + s1) + (s2 + s3).  A piece's z values wait in the output row, each element written and read back by the same lane.
+__global__ __launch_bounds__(256) void k_generate_around_points_wide(double *t, double *thin_u, long long n, int d, const double *refR,
+                                                                     int nlive, int dp, double r2, unsigned long long seed,
+                                                                     unsigned long long offset) {
+  constexpr int PIECE = 256;
+  __shared__ double zs[4][PIECE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long row = (long long)blockIdx.x * 4 + wv;
+  const bool live = row < n;   // wave-uniform; the waves without a row keep the barriers company
+  const int npairs = (d + 1) / 2;
+  const unsigned long long base = offset + (unsigned long long)(live ? row : 0) * (unsigned long long)(npairs + 2);
+  double *dst = t + (live ? row : 0) * d;
+  double acc = 0.0;
+  for (int k0 = 0; k0 < d; k0 += PIECE) {
+    const int m = d - k0 < PIECE ? d - k0 : PIECE;
+    if (live)
+      for (int jl = lane; 2 * jl < m; jl += 64) {
+        const int j = k0 / 2 + jl;
+        unsigned r4[4];
+        philox_block(seed, 6u, base + 2 + j, r4);
+        const double rad = sqrt(-2.0 * log(u01(r4[0], r4[1])));
+        double sn, cs;
+        sincospi(2.0 * u01(r4[2], r4[3]), &sn, &cs);
+        zs[wv][2 * jl] = rad * cs;
+        if (2 * jl + 1 < m) zs[wv][2 * jl + 1] = rad * sn;
+      }
+    __syncthreads();
+    if (live) {
+      if (lane < 4)
+        for (int k = lane; k < m; k += 4) {
+          const double v = zs[wv][k];
+          acc += v * v;
+        }
+      for (int k = lane; k < m; k += 64) dst[k0 + k] = zs[wv][k];
+    }
+    __syncthreads();   // the piece is read: the next one may take its place
+  }
+  acc += __shfl_xor(acc, 1, 64);
+  acc += __shfl_xor(acc, 2, 64);
+  if (!live) return;
+  unsigned which = 0u;
+  double fac = 0.0;
+  if (lane == 0) {
+    unsigned w0[4], w1[4];
+    philox_block(seed, 6u, base, w0);
+    philox_block(seed, 6u, base + 1, w1);
+    which = below(w0[0], (unsigned)nlive);
+    const double radial = u01(w0[2], w0[3]);
+    thin_u[row] = u01(w1[0], w1[1]);
+    fac = pow(radial, 1.0 / (double)d) / sqrt(acc) * sqrt(r2);
+  }
+  which = __shfl(which, 0, 64);
+  fac = __shfl(fac, 0, 64);
+  const double *centre = refR + (size_t)which * dp;
+  for (int k = lane; k < d; k += 64) dst[k] = centre[k] + dst[k] * fac;   // k0 + (lane, lane + 64, ...): this lane's own elements
+}
+
 // keep a proposal with probability 1 / multiplicity (reference :1089: uniform(high=multiplicity) < 1)
 __global__ void k_thin_by_multiplicity(const long long *count, const double *thin_u, long long n, uint8_t *mask) {
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -625,16 +687,29 @@ hipError_t launch_generate_tbox(double *t, long long n, int d, const double *lo,
   return hipGetLastError();
 }
 
+static std::atomic<bool> g_around_points_wide{false};
+void force_around_points_wide(bool on) { g_around_points_wide.store(on, std::memory_order_relaxed); }
+
 hipError_t launch_generate_around_points(double *t, double *thin_u, long long n, int d, const double *refR, int nlive, int dp,
                                          double r2, unsigned long long seed, unsigned long long offset, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int npairs = (d + 1) / 2;
   const unsigned pmagic = npairs > 1 ? (unsigned)((0x100000000ull + (unsigned)npairs - 1) / (unsigned)npairs) : 0u;
   const unsigned dmagic = d > 1 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u;
+  // the staged kernel holds 64 rows in LDS: 512 d + 1280 bytes, 103 680 at d = 200.  What one workgroup may have is the device's to
+  // say (160 KiB on the MI355X: d <= 317); wider rows go through the kernel whose LDS does not grow with d
   const size_t lds = ((size_t)64 * (d + 1) + 64) * sizeof(double) + 64 * sizeof(unsigned);
-  static DeviceGrant grant;
-  if (hipError_t e = grant.ensure([] {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_generate_around_points), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
+  int dev = 0, lds_limit = 0;
+  if (hipError_t e = hipGetDevice(&dev)) return e;
+  if (hipError_t e = hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev)) return e;
+  if (lds > (size_t)lds_limit || g_around_points_wide.load(std::memory_order_relaxed)) {
+    hipLaunchKernelGGL(k_generate_around_points_wide, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, t, thin_u, n, d, refR, nlive, dp,
+                       r2, seed, offset);
+    return hipGetLastError();
+  }
+  static DeviceGrant grant;   // once per device: all a workgroup may have, which covers every staged launch
+  if (hipError_t e = grant.ensure([lds_limit] {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_generate_around_points), hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
       }))
     return e;
   hipLaunchKernelGGL(k_generate_around_points, dim3((unsigned)((n + 63) / 64)), dim3(256), lds, s, t, thin_u, n, d, refR,

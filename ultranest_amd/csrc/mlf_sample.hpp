@@ -21,8 +21,11 @@ hipError_t launch_rows_affine(const double *t, long long n, int d, const double 
 void launch_center_and_cube(double *w, long long n, int d, const double *center, uint8_t *in_cube, hipStream_t s);
 hipError_t launch_generate_tbox(double *t, long long n, int d, const double *lo, const double *hi, double pad,
                                 unsigned long long seed, unsigned long long offset, hipStream_t s);
+// method 3: rows whose 64-row staging fits the device's per-workgroup LDS go through k_generate_around_points, wider ones through
+// k_generate_around_points_wide -- the same draws, bit for bit.  force_around_points_wide (tests): every row through the latter.
 hipError_t launch_generate_around_points(double *t, double *thin_u, long long n, int d, const double *refR, int nlive, int dp,
                                          double r2, unsigned long long seed, unsigned long long offset, hipStream_t s);
+void force_around_points_wide(bool on);
 void launch_thin_by_multiplicity(const long long *count, const double *thin_u, long long n, uint8_t *mask, hipStream_t s);
 void launch_untransform_rows(const double *t, long long n, int d, const double *invT, const double *ctr,
                              const double *wrap_shift, double *w, uint8_t *in_cube, hipStream_t s);
